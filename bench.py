@@ -38,6 +38,10 @@ PREROLL = 6000            # untimed steps of every game BEFORE the warm-up, what
                           # is 1.7 %); after 6 000 steps (~50 rounds of RandomAgent play, 0.22 s at 65 536 games) a 20-step window
                           # holds the long-run share (measured: 0.0169 at 6 000, 0.0167 at 8 000, 0.0165 at 12 000; DESIGN.md
                           # section 11.1) - the steady state the metric is defined on.  Reported as "preroll_steps".
+DUMP_GAMES = 4096         # --dump-outputs: the games whose outputs are written (all of a smaller batch, else a fixed seeded sample) ...
+DUMP_OBS_GAMES = 512      # ... and, with --encode, those of them whose feature rows are written (a seeded sample again)
+DUMP_SEED = 0x5EED
+DUMP_MAX_BYTES = 64 * 10 ** 6
 
 
 def parse_args(argv=None):
@@ -69,7 +73,13 @@ def parse_args(argv=None):
     ap.add_argument("--encode", action="store_true",
                     help="also produce the feature tensor of the acting seats every step (BASELINE configs[4]: sanma with "
                          "feature-encoding tensor output): one step launch + one encode launch per step")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed rollout left for its caller (status, legal lists, masks, waits, "
+                         "scores, step counts; with --encode the feature rows) as DIR/<name>.npy: see dump_outputs()")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 def free_port():
@@ -102,6 +112,8 @@ def launcher_command(args, port, script=None):
         cmd.append("--reference-rng")
     if getattr(args, "oversubscribe", False):
         cmd.append("--oversubscribe")
+    if getattr(args, "dump_outputs", None):
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")   # dmabuf IPC only on this pool (RCCL barrier between the ranks)
     env["MASTER_ADDR"] = "127.0.0.1"
@@ -279,6 +291,68 @@ class Dev:
 def acting_seats(env):
     act, _, dn = env.status()
     return int(sum(bin(int(a)).count("1") for a, d in zip(act, dn) if not d))
+
+
+def _hip_runtime():
+    """The HIP runtime the library runs on (one per process: vecenv._share_torch_hip_runtime), opened again by the path it is
+    mapped from - the same handle, no second runtime."""
+    import ctypes as C
+
+    with open("/proc/self/maps") as f:
+        for ln in f:
+            path = ln.split()[-1]
+            if os.path.basename(path).startswith("libamdhip64.so"):
+                hip = C.CDLL(path)
+                hip.hipSetDevice.argtypes = [C.c_int]
+                hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+                return hip
+    raise RuntimeError("bench.py: no HIP runtime is loaded in this process")
+
+
+def dump_outputs(env, out_dir, obs=None):
+    """--dump-outputs DIR: what the timed rollout left for its caller after its last step, one DIR/<name>.npy per array, every value
+    exact in its float32 / float64.  The games are `game_index`: all of them up to DUMP_GAMES, else a fixed seeded sample.
+      active_mask, phase, done, step_counts [k]; scores, waits, legal_counts [k, 4]; action_mask [k, 4, 82];
+      legal_actions [k, 4, 64, 2]: the ordered legal lists, every packed 64-bit action as (bits 0-31, bits 32-63); entries past
+        legal_counts are not part of a list and are written as 0.
+    With --encode (`obs` = (dev, device pointer, row stride in floats) of the resident tensor), also obs [k', 4, 74, W]: the rows of
+    the games obs_game_index as the rollout left them (the seats that were not to act keep their earlier rows: only_active = 2).
+    Inputs are seeded, so two builds run with the same arguments can be compared array for array.  Returns the line's record."""
+    import numpy as np
+
+    n = env.n
+    rng = np.random.default_rng(DUMP_SEED)
+    idx = np.arange(n) if n <= DUMP_GAMES else np.sort(rng.choice(n, DUMP_GAMES, replace=False))
+    act, ph, dn = env.status()
+    legal, cnt = env.legal()
+    legal, cnt = legal[idx], cnt[idx]
+    legal[np.arange(legal.shape[2])[None, None, :] >= cnt[:, :, None]] = 0
+    f64 = {"game_index": idx, "step_counts": env.step_counts()[idx], "scores": env.scores()[idx], "waits": env.waits()[idx],
+           "legal_actions": np.stack([legal & np.uint64(0xFFFFFFFF), legal >> np.uint64(32)], axis=-1)}
+    f32 = {"active_mask": act[idx], "phase": ph[idx], "done": dn[idx], "legal_counts": cnt, "action_mask": env.mask()[idx]}
+    if obs is not None:
+        dev, ptr, stride = obs
+        w = 27 if env.game_mode >= 3 else 34
+        oidx = idx if len(idx) <= DUMP_OBS_GAMES else np.sort(rng.choice(idx, DUMP_OBS_GAMES, replace=False))
+        rows = np.empty((len(oidx), 4, stride), np.float32)
+        hip = _hip_runtime()
+        if hip.hipSetDevice(dev.device):
+            raise RuntimeError("bench.py --dump-outputs: hipSetDevice failed")
+        dev.sync()
+        for j, g in enumerate(oidx):   # game g's four rows: floats [g * 4 * stride, (g + 1) * 4 * stride) of the [games][4][stride] tensor
+            if hip.hipMemcpy(rows[j].ctypes.data, ptr + int(g) * 4 * stride * 4, 4 * stride * 4, 2):   # 2 = hipMemcpyDeviceToHost
+                raise RuntimeError(f"bench.py --dump-outputs: hipMemcpy of the feature rows of game {g} failed")
+        f64["obs_game_index"] = oidx
+        f32["obs"] = rows[:, :, : 74 * w].reshape(len(oidx), 4, 74, w)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in f64.items()}
+    arrays.update({k: np.ascontiguousarray(v, dtype=np.float32) for k, v in f32.items()})
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"bench.py --dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES} of a dump")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {"dir": os.path.abspath(out_dir), "games": int(len(idx)), "bytes": total, "arrays": sorted(arrays)}
 
 
 def rollout_roofline(r, games, steps, sanma, encode=False, acting=0, greedy=False, enc_step_ms=None):
@@ -497,6 +571,7 @@ def in_process_leg(args):
     env._map(timed)
     wall = time.perf_counter() - t0
     made = [b - a for a, b in zip(s0, env._map(lambda i, e: e.total_steps()))]
+    dumped = dump_outputs(env, args.dump_outputs) if args.dump_outputs else None
     env.close()
     line = {"metric": metric_name(args), "value": sum(made) / wall, "unit": "env.step/s", "n_gpus": len(set(devices)), "shards": k, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": wall * 1e3 / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8",
@@ -505,6 +580,8 @@ def in_process_leg(args):
             "config": {"workload": f"{k} x {args.games} parallel {MODES[args.mode]} games, device RandomAgent, auto-reset, MJAI logging on", "games_per_shard": args.games,
                        "parallelism": f"{k} in-process shards on {len(set(devices))} device(s)"},
             "note": "shards that share a device are time-sliced by it: on one GPU this line shows that the path runs, not a scaling figure"}
+    if dumped is not None:
+        line["dump_outputs"] = dumped
     print(json.dumps(line))
     return 0
 
@@ -628,6 +705,10 @@ def main(argv=None):
     full_steps = env.total_full_path() - full0
     gm = shard.gather_measurement(dist, rank, t1 - t0, steps_local, device="cpu" if (shared_gpus or torch is None) else "cuda")
     wall, steps_total = gm["wall"], gm["steps"]
+    # what the timed steps computed (rank 0's shard), read back before a side measurement steps the environment again
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(env, args.dump_outputs, obs=(dev, obs, stride) if args.encode else None)
 
     # ---- side measurements, outside the timed region (rank 0 of a 1-GPU run only)
     extras = {}
@@ -744,6 +825,8 @@ def main(argv=None):
         out.update(extras)
         if cpu_line is not None:
             out["cpu_baseline"] = cpu_line
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         sys.stdout.flush()
         os.dup2(saved_stdout, 1)
         print(json.dumps(out), flush=True)

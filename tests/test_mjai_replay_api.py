@@ -58,7 +58,7 @@ def test_real_hanchan_log():  # tests/test_mjai_replay.py:79-102 on tests/data/1
     assert sum(last["end_scores"]) + 1000 * 0 <= 100000 and len(last["delta_scores"]) == 4
 
 
-def test_wliqi_and_double_ron_end_scores():
+def test_wliqi_and_double_ron_end_scores(tmp_path):
     """mjai_replay.rs:412-418 (double riichi = riichi on the first discard with no call before) and :581-599 (the first
     hora starts from the scores minus accepted deposits, later hora events add up)"""
     tehai = ["1s"] * 13
@@ -74,7 +74,7 @@ def test_wliqi_and_double_ron_end_scores():
         {"type": "hora", "actor": 0, "target": 1, "deltas": [2000, -2000, 0, 0]},
         {"type": "end_kyoku"},
     ]
-    path = os.path.join(os.environ.get("TMPDIR", "/tmp"), "rmj_wliqi_test.jsonl")
+    path = str(tmp_path / "wliqi.jsonl")
     with open(path, "w") as f:
         f.write("".join(json.dumps(e) + "\n" for e in log))
     k = list(MjaiReplay.from_jsonl(path).take_kyokus())[0]
