@@ -430,14 +430,18 @@ int rmj_step_ids_encode_device(rmj_handle h, const int32_t* d_action_ids, int au
 /* rmj_sample_ids_device(h, d_logits, stride, seed, d_ids) + rmj_step_ids_encode_device(h, d_ids, auto_reset, d_out) as ONE launch (round 5):
  * every wave draws the ids of its own four games from the policy's logits (the same keyed draw: the ids are the ones the two calls
  * produce, and they are written to d_ids [n][4] for the caller's log-probabilities), steps under them and encodes the seats that act
- * next - the whole environment side of a trainer iteration (trainers/_ppo_worker.py:151-239) between two policy forward passes. */
+ * next - the whole environment side of a trainer iteration (trainers/_ppo_worker.py:151-239) between two policy forward passes.
+ * Non-finite logits are drawn as rmj_sample_ids_device describes. */
 int rmj_step_sample_encode_device(rmj_handle h, const float* d_logits, uint32_t stride, uint64_t seed, int auto_reset, int32_t* d_ids, float* d_out);
 /* Masked categorical sampling for a policy on the same GPU (what riichienv-ml's PPO worker does per game on the host with
  * obs.mask(), trainers/_ppo_worker.py:164-239): for every seat that is to act, one action id drawn from
  * softmax(logits) restricted to the seat's legal ids (Gumbel-max on the resident mask slab); d_logits [n][4][stride] f32 on
  * the device (stride >= 82 / 60; masked entries are never read as candidates), NULL = uniform over the legal ids.
  * d_ids [n][4] int32, -1 for seats that do not act: the input of rmj_step_ids_device.  Counter-based noise: the same
- * (seed, state) gives the same ids.  Asynchronous on the handle's stream. */
+ * (seed, state) gives the same ids.  Asynchronous on the handle's stream.
+ * Non-finite logits (here and in rmj_step_sample_encode_device): a -inf or NaN logit is never drawn while a finite one is legal;
+ * if every legal id is -inf or NaN, the lowest legal id is drawn; among several +inf logits the lowest of them wins.  The noise
+ * u of every id lies strictly inside (0, 1), so every finite logit gets a finite key. */
 int rmj_sample_ids_device(rmj_handle h, const float* d_logits, uint32_t stride, uint64_t seed, int32_t* d_ids);
 /* Round boundaries and per-round score deltas for a trainer on the same GPU (what riichienv-ml's PPO worker computes on the host
  * between steps: trainers/_ppo_worker.py:100-116 GRP features, :240-266 the reward at a kyoku boundary, :283-291 rank rewards).

@@ -96,6 +96,8 @@ __global__ void k_random_actions(Env E, uint64_t policy_seed, uint64_t* out) {
 // draw of an id costs the same wherever it runs, but a wave per game left 64 lanes to 82 ids of (mostly) one seat.  The same keys, the same
 // arg-max rule (ties to the lower id) as the wave-per-game kernel of rounds 3-4: identical ids.
 // One id per acting seat of the row's game g (in: the row has a game): lane p of the row returns seat p's id, -1 where nobody acts.
+// Non-finite logits: a -inf or NaN logit is never drawn while a finite one is legal; if every legal id is -inf or NaN the lowest legal
+// id is drawn; among several +inf logits the lowest id wins.  tests/sampler_ref.py restates the draw in float64.
 __device__ __forceinline__ int32_t sample_ids_row(const uint32_t* status, const GState* core, const uint8_t* nlegal, const uint8_t* mask, uint64_t game_offset,
                                                   int game_mode, uint32_t g, bool in, const float* __restrict__ logits, uint32_t stride, uint64_t seed, int lane) {
     const int r = lane & 15;
@@ -117,8 +119,11 @@ __device__ __forceinline__ int32_t sample_ids_row(const uint32_t* status, const 
             for (int id = r; id < A; id += 16) {
                 if (m[id]) {
                     const uint64_t h = sm64(base + ((uint64_t)p << 8) + (uint64_t)id);
-                    const float u = ((float)(uint32_t)(h >> 40) + 0.5f) * (1.0f / 16777216.0f);   // (0, 1), 24 bits
-                    const float key = (lg ? lg[id] : 0.0f) - __logf(-__logf(u));
+                    // u in (0, 1), 24 bits: 0xFFFFFF + 0.5f rounds to 2^24 (u = 1, a +inf key whatever the logit), so the top value is
+                    // clamped to the largest float below 1 - the only hash value whose u this changes
+                    const float u = fminf(((float)(uint32_t)(h >> 40) + 0.5f) * (1.0f / 16777216.0f), 0x1.fffffep-1f);
+                    const float k = (lg ? lg[id] : 0.0f) - __logf(-__logf(u));
+                    const float key = __builtin_isnan(k) ? -INFINITY : k;   // a NaN logit is drawn like -inf (the arg-max stays a function of the keys)
                     if (key > best || bid < 0) { best = key; bid = id; }
                 }
             }

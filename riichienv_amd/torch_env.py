@@ -297,7 +297,9 @@ class TorchVecEnv:
         from the compact observation batch, scattered here into the [n, 4, A'] layout (rows of seats that do not act are never
         read by the sampler).  `count`: the device count tensor of obs_compact(sync_count=False) - rows of `index` behind it hold stale
         (game, seat) values that may repeat live ones, so they are sent to a sink row instead of racing with the live rows; without
-        `count` every row of `index` must be live (the sync_count=True form)."""
+        `count` every row of `index` must be live (the sync_count=True form).
+        Non-finite logits: a -inf or NaN logit is never drawn while a finite one is legal; if every legal id is -inf or NaN the
+        lowest legal id is drawn; among several +inf logits the lowest of them wins (step_sample_obs draws the same way)."""
         t = self.torch
         if not hasattr(self, "_ids"):
             self._ids = t.full((self.n, 4), -1, dtype=t.int32, device=self.device)
