@@ -68,6 +68,10 @@ def lib():
         L.orc_bench_rollout.restype = C.c_uint64
         L.orc_bench_rollout.argtypes = [C.c_int, C.c_uint32, C.c_int, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32,
                                         C.c_int, C.POINTER(C.c_double)]
+        L.orc_rollout_policy.argtypes = ([C.c_int, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.c_uint64, C.c_uint32,
+                                          C.c_uint32, C.c_int] + [C.c_void_p] * 6 + [C.c_int] + [C.c_void_p] * 9)
+        L.orc_log_digest.restype = C.c_uint64
+        L.orc_log_digest.argtypes = [C.c_char_p, C.c_uint64]
         L.orc_game_wall_meta.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
         L.orc_chacha_block.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]
         L.orc_seed_from_u64.argtypes = [C.c_uint64, C.c_void_p]
@@ -323,3 +327,54 @@ def bench_rollout(game_mode, rule_bits, skip_log, n_games, base_seed, policy_see
     steps = lib().orc_bench_rollout(game_mode, rule_bits, int(skip_log), n_games, base_seed, policy_seed,
                                     steps_per_game, threads, C.byref(secs))
     return steps, secs.value
+
+
+def log_digest(lines):
+    """FNV-1a 64 of MJAI lines joined with '\\n' (orc_rollout_policy's digest)"""
+    return text_digest("\n".join(lines).encode())
+
+
+def text_digest(text: bytes):
+    """FNV-1a 64 of a byte string (offset basis 0xCBF29CE484222325, prime 0x100000001B3)"""
+    return lib().orc_log_digest(text, len(text))
+
+
+POLICIES = {"random": 0, "greedy": 1}
+
+
+def rollout_policy(game_mode, rule_bits, seed, n, policy, policy_seed, n_steps, call_rate_256=64, auto_reset=True, game_offset=0,
+                   walls=None, oya=None, round_wind=None, scores=None, honba=None, kyotaku=None, threads=None):
+    """n games (global indices game_offset + g, episode seeds shard.game_seed(seed, game_offset + g)) stepped n_steps env steps under a
+    device policy's oracle twin ("random": Game.random_actions, "greedy": Game.greedy_actions), each as a test steps a Game after
+    Game(...).reset(<its reset arguments>): a finished game restarts with the defaults (auto_reset; that step acts on nothing) or waits.
+    Reset arguments are per game, as VecRiichiEnv.reset takes them (oya / round_wind / honba / kyotaku [n], -1 = default; scores [n][NP];
+    walls [n][136 or 108], a row that starts with 255 = the game shuffles its own).  Returns a dict of arrays: status [n, 3] (active mask, phase, done), views (StateView * n), steps [n],
+    scores [n, 4], legal [n, 4, MAX_LEGAL] and legal_count [n, 4], mask [n, 4, 82], waits [n, 4] (acting seats; others zero), and
+    digest [n]: log_digest of every line the game logged, the finished games' logs and the current one in order."""
+    sanma = game_mode >= 3
+
+    def per_game(a, dt, width=None):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(np.asarray(a).reshape((n,) if width is None else (n, -1)), dtype=dt)
+        if width is not None and a.shape[1] < width:
+            a = np.ascontiguousarray(np.concatenate([a, np.zeros((n, width - a.shape[1]), dt)], axis=1))
+        return a
+
+    args = [per_game(walls, np.uint8, 136), per_game(oya, np.int32), per_game(round_wind, np.int32), per_game(scores, np.int32, 4),
+            per_game(honba, np.int32), per_game(kyotaku, np.int32)]
+    if scores is not None and np.asarray(scores).reshape(n, -1).shape[1] != (3 if sanma else 4):
+        raise ValueError("scores: one per seat")
+    out = dict(status=np.zeros((n, 3), np.uint8), views=(abi.StateView * max(n, 1))(), steps=np.zeros(n, np.uint64),
+               scores=np.zeros((n, 4), np.int32), legal=np.zeros((n, 4, abi.MAX_LEGAL), np.uint64),
+               legal_count=np.zeros((n, 4), np.uint32), mask=np.zeros((n, 4, 82), np.uint8), waits=np.zeros((n, 4), np.uint64),
+               digest=np.zeros(n, np.uint64))
+    threads = threads or max(1, min(os.cpu_count() or 1, 32))
+    rc = lib().orc_rollout_policy(game_mode, rule_bits, seed, game_offset, n, POLICIES[policy], policy_seed, call_rate_256, n_steps,
+                                  int(auto_reset), *[None if a is None else a.ctypes.data for a in args], threads,
+                                  out["status"].ctypes.data, out["views"], out["steps"].ctypes.data, out["scores"].ctypes.data,
+                                  out["legal"].ctypes.data, out["legal_count"].ctypes.data, out["mask"].ctypes.data,
+                                  out["waits"].ctypes.data, out["digest"].ctypes.data)
+    if rc:
+        raise ValueError(f"orc_rollout_policy: {rc}")
+    return out

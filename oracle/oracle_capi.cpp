@@ -1267,4 +1267,81 @@ uint64_t orc_bench_rollout(int game_mode, uint32_t rule_bits, int skip_log, uint
     return sum;
 }
 
+
+// ---------------------------------------------------------------- batch rollout under a device policy (tests)
+// FNV-1a 64 over a log's lines joined with '\n' (tests/round_end_census.py log_digest): `first` is false once a line went in
+static void fnv1a_line(uint64_t& h, bool& first, const std::string& s) {
+    if (!first) { h ^= (uint8_t)'\n'; h *= 0x100000001B3ull; }
+    for (unsigned char ch : s) { h ^= ch; h *= 0x100000001B3ull; }
+    first = false;
+}
+// the same over text that is already joined (tests: the device's drained logs)
+uint64_t orc_log_digest(const uint8_t* text, uint64_t len) {
+    uint64_t h = 0xCBF29CE484222325ull;
+    for (uint64_t i = 0; i < len; i++) { h ^= text[i]; h *= 0x100000001B3ull; }
+    return h;
+}
+// Steps n games g (global index game_offset + g, episode seed splitmix64(base_seed + game_offset + g) = shard.game_seed) for n_steps env
+// steps under a device policy's oracle twin - policy 0: the RandomAgent (orc_game_random_actions), 1: greedy (orc_game_greedy_actions with
+// call_rate_256) - exactly as a test steps oracle.Game: a finished game is reset (auto_reset; that step acts on nothing) or left alone.
+// Reset arguments of the first deal (GameState::env_reset, VecRiichiEnv.reset): walls [n][136] (3P: first 108; a row that starts with 0xFF:
+// the game shuffles its own) or NULL; oya / round_wind /
+// honba / kyotaku [n], < 0 or NULL = default; scores [n][4] or NULL.  Restarts take the defaults, as the device's auto-reset does.
+// Out, per game: status [n][3] (active mask, phase, done), views [n], step counts [n], scores [n][4], legal [n][4][RMJ_MAX_LEGAL] with counts
+// [n][4] (acting seats; others 0), masks [n][4][82] (acting seats), waits [n][4] (acting seats), digest [n] of every line the game slot logged:
+// the finished games' logs and the current one, in order (what drain_logs hands out across restarts).  Games are spread over `threads`.
+int orc_rollout_policy(int game_mode, uint32_t rule_bits, uint64_t base_seed, uint64_t game_offset, uint32_t n, int policy,
+                       uint64_t policy_seed, uint32_t call_rate_256, uint32_t n_steps, int auto_reset, const uint8_t* walls,
+                       const int32_t* oya, const int32_t* round_wind, const int32_t* scores, const int32_t* honba, const int32_t* kyotaku,
+                       int threads, uint8_t* status, RmjStateView* views, uint64_t* step_counts, int32_t* scores_out,
+                       rmj_action_t* legal, uint32_t* legal_cnt, uint8_t* masks, uint64_t* waits, uint64_t* digest) {
+    if (policy != 0 && policy != 1) return -1;
+    if (threads < 1) threads = 1;
+    auto work = [&](int tid) {
+        for (uint32_t g = tid; g < n; g += threads) {
+            const uint64_t G = game_offset + g;
+            GameState* s = new GameState((uint8_t)game_mode, false, splitmix64(base_seed + G), 0, GameRule::from_bits(rule_bits),
+                                         (rule_bits & RMJ_RULE_REFERENCE_RNG) != 0);
+            orc_game_reset(s, walls && walls[(size_t)g * 136] != 0xFF ? walls + (size_t)g * 136 : nullptr, oya ? oya[g] : -1, round_wind ? round_wind[g] : -1,
+                           scores ? scores + (size_t)g * 4 : nullptr, honba ? honba[g] : -1, kyotaku ? kyotaku[g] : -1);
+            uint64_t h = 0xCBF29CE484222325ull;
+            bool first = true;
+            rmj_action_t acts[4];
+            for (uint32_t k = 0; k < n_steps; k++) {
+                if (s->is_done) {
+                    if (auto_reset) {
+                        for (const auto& line : s->mjai_log) fnv1a_line(h, first, line);
+                        s->env_reset(-1, nullptr, -1, nullptr, -1, -1);
+                    }
+                    continue;
+                }
+                if (policy == 0) orc_game_random_actions(s, policy_seed, G, acts);
+                else orc_game_greedy_actions(s, policy_seed, G, call_rate_256, acts);
+                orc_game_step(s, acts);
+            }
+            for (const auto& line : s->mjai_log) fnv1a_line(h, first, line);
+            digest[g] = h;
+            orc_game_status(s, status + (size_t)g * 3, status + (size_t)g * 3 + 1, status + (size_t)g * 3 + 2);
+            orc_game_peek(s, views + g);
+            step_counts[g] = s->step_count;
+            for (int p = 0; p < 4; p++) scores_out[(size_t)g * 4 + p] = p < s->NP ? s->players[p].score : 0;
+            std::memset(legal + (size_t)g * 4 * RMJ_MAX_LEGAL, 0, 4 * RMJ_MAX_LEGAL * sizeof(rmj_action_t));
+            std::memset(legal_cnt + (size_t)g * 4, 0, 4 * sizeof(uint32_t));
+            std::memset(masks + (size_t)g * 4 * 82, 0, 4 * 82);
+            std::memset(waits + (size_t)g * 4, 0, 4 * sizeof(uint64_t));
+            if (!s->is_done)
+                for (uint8_t p : s->active_players) {
+                    legal_cnt[(size_t)g * 4 + p] = (uint32_t)std::min(orc_game_legal(s, p, legal + ((size_t)g * 4 + p) * RMJ_MAX_LEGAL), RMJ_MAX_LEGAL);
+                    orc_game_mask(s, p, masks + ((size_t)g * 4 + p) * 82);
+                    waits[(size_t)g * 4 + p] = orc_game_waits(s, p);
+                }
+            delete s;
+        }
+    };
+    std::vector<std::thread> th;
+    for (int t = 0; t < threads; t++) th.emplace_back(work, t);
+    for (auto& t : th) t.join();
+    return 0;
+}
+
 }  // extern "C"

@@ -973,6 +973,11 @@ class MjaiReplay:
             events = load_mjai_jsonl(path)
         except OSError as e:
             raise ValueError(f"Failed to open file: {e}")
+        return cls.from_events(events, rule)
+
+    @classmethod
+    def from_events(cls, events, rule=None):
+        """from_jsonl over MJAI event dicts already in memory"""
         rounds, cur = [], None
         for ev in events:
             ty = ev.get("type")

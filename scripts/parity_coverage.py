@@ -8,12 +8,12 @@ import collections
 import json
 import os
 import sys
-import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from riichienv_amd import abi, vecenv  # noqa: E402
 from riichienv_amd.replay import MjaiReplay, evaluate_win_contexts  # noqa: E402
+from tests.round_end_census import win_contexts  # noqa: E402
 
 
 def rollout_logs(mode, rule, n, steps, seed=99):
@@ -32,68 +32,21 @@ def census_logs(logs, label=""):
     types, reasons, wins = collections.Counter(), collections.Counter(), collections.Counter()
     yaku = collections.Counter()
     ctx_all, expect = [], []
-    with tempfile.TemporaryDirectory() as td:
-        for g, log in enumerate(logs):
-            for e in log:
-                types[e["type"]] += 1
-                if e["type"] == "ryukyoku":
-                    r = e.get("reason", "")
-                    reasons[r if not r.startswith("Error") else "illegal action"] += 1
-            p = os.path.join(td, f"{g}.jsonl")
-            with open(p, "w") as f:
-                for e in log:
-                    f.write(json.dumps(e) + "\n")
-            for k in MjaiReplay.from_jsonl(p).take_kyokus():
-                horas = [e for e in k.mjai_events if e.get("type") == "hora"]
-                ctxs = list(k.take_win_result_contexts())
-                if len(ctxs) != len(horas):
-                    wins["context count mismatch"] += 1
-                    continue
-                if len(horas) > 1:
-                    wins[f"{len(horas)}-fold ron"] += 1
-                # A tsumo on the replacement draw of a kan / kita: the reference's iterator recognises it by the `doras` list of a
-                # Mahjong Soul DealTile (replay/mod.rs:1806-1809) and drops the flag at any other draw (:1735-1736), so for MJAI
-                # logs it never sets rinshan; the census marks those wins itself
-                hist = [e for e in k.mjai_events if e.get("type") not in ("dora", "reach", "reach_accepted")]
-                for i, (c, h) in enumerate(zip(ctxs, horas)):
-                    at = next(j for j, e in enumerate(hist) if e is h)
-                    if h["actor"] == h["target"] and at >= 2 and hist[at - 1]["type"] == "tsumo" and hist[at - 2]["type"] in ("ankan", "kakan", "daiminkan", "kita"):
-                        c.conditions["rinshan"], c.conditions["haitei"] = True, False
-                        wins["rinshan (marked by the census)"] += 1
-                    # Two more places where the reference's MJAI reader and its own environment disagree (both mirrored by
-                    # riichienv_amd.replay, both set right here so that the device's bookings can be checked):
-                    # a kita before the riichi ends the first turn in the environment (state_3p/sanma.rs:39) but is no "call" for
-                    # the reader's double-riichi flag (mjai_replay.rs:415, :606-611) ...
-                    if c.conditions["double_riichi"]:
-                        reach_at = next(j for j, e in enumerate(k.mjai_events) if e.get("type") == "reach" and e.get("actor") == c.seat)
-                        # (up to the riichi DISCARD: a seat may declare, take a kita and only then discard)
-                        reach_at = next(j for j, e in enumerate(k.mjai_events) if j > reach_at and e.get("type") == "dahai" and e.get("actor") == c.seat)
-                        if any(e.get("type") == "kita" for e in k.mjai_events[:reach_at]):
-                            c.conditions["double_riichi"] = False
-                            wins["riichi after a kita (reader says double)"] += 1
-                    # ... and a Ron on a kita finds no winning tile in a hora event without `pai` (mjai_replay.rs:541-559 has no
-                    # BaBei case: tile 0)
-                    if h["actor"] != h["target"] and at >= 1 and hist[at - 1]["type"] in ("kita", "hora") and h.get("pai") is None:
-                        prev = next(e for e in reversed(hist[:at]) if e["type"] != "hora")
-                        if prev["type"] == "kita":
-                            north = abi.mjai_to_tid("N")
-                            c.tiles = list(c.tiles[:-1]) + [north]
-                            c.agari_tile = north
-                            wins["ron on a kita"] += 1
-                    # ... nor does a Ron on a kakan whose kan flushed the pending indicator of an earlier open kan: the `dora` event
-                    # sits between the kakan and the hora, the reader's last action is Dora (tile 0, and no chankan)
-                    if h["actor"] != h["target"] and h.get("pai") is None:
-                        full = [e for e in k.mjai_events if e.get("type") not in ("reach", "reach_accepted")]
-                        at_f = next(j for j, e in enumerate(full) if e is h)
-                        before = [e for e in full[:at_f] if e["type"] != "hora"]
-                        if len(before) >= 2 and before[-1]["type"] == "dora" and before[-2]["type"] == "kakan":
-                            t = abi.mjai_to_tid(before[-2]["pai"])
-                            c.tiles = list(c.tiles[:-1]) + [t]
-                            c.agari_tile = t
-                            c.conditions["chankan"] = True
-                            wins["chankan behind a dora event"] += 1
-                    ctx_all.append(c)
-                    expect.append((k, h, i))
+    for g, log in enumerate(logs):
+        for e in log:
+            types[e["type"]] += 1
+            if e["type"] == "ryukyoku":
+                r = e.get("reason", "")
+                reasons[r if not r.startswith("Error") else "illegal action"] += 1
+        for k in MjaiReplay.from_events(log).take_kyokus():
+            ctxs = win_contexts(k, wins)
+            if ctxs is None:
+                continue
+            if len(ctxs) > 1:
+                wins[f"{len(ctxs)}-fold ron"] += 1
+            for c, h, i in ctxs:
+                ctx_all.append(c)
+                expect.append((k, h, i))
     evaluate_win_contexts(ctx_all)
     bad = 0
     for c, (k, h, i) in zip(ctx_all, expect):
