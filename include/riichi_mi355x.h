@@ -325,6 +325,29 @@ typedef struct RmjEventViews {
 } RmjEventViews;
 int rmj_event_views(rmj_handle h, RmjEventViews* out);
 int rmj_get_events_lost(rmj_handle h, uint32_t* lost /*[n]*/); /* host copy of RmjEventViews.lost */
+/* MJAI text formatted on the device: the same bytes and offsets as rmj_drain_format / rmj_format_events (the host formatter), written
+ * by a HIP formatter, every game's log at text[text_offsets[g] .. text_offsets[g + 1]) (its events' strings, each followed by '\n').
+ * rmj_drain_text: the drain contract above - cursors are stream positions and survive restarts, a lapped window starts at the oldest
+ * record still held and the loss is booked in RmjEventViews.lost by the call that hands the text over, RMJ_DRAIN_PEEK moves nothing,
+ * cursors advance exactly as rmj_drain_format advances them - with the records read in place from the rings (no record copy).
+ * rmj_format_events_device: the device analogue of rmj_format_events, over caller records already on the device (game g's records
+ * d_ev[d_offsets[g] .. d_offsets[g + 1])).
+ * The text and its offsets live in buffers owned by the handle (not its scratch): the view stays valid until the next rmj_drain_text /
+ * rmj_format_events_device on the handle, or rmj_destroy.  Without RMJ_TEXT_ON_DEVICE the view points at pinned host memory (the device
+ * text plus ONE copy); with it, at device memory.  Both calls synchronise the handle's stream before they return: the text is complete
+ * and a consumer on any stream may read the view at once.  ms: device format, copy to the host (0 on device delivery), total.
+ * Either call ends what a size call of rmj_drain_format staged (as rmj_drain_events does). */
+typedef struct RmjTextView {
+    const char* text;             /* [bytes]: game g's log is text[text_offsets[g] .. text_offsets[g + 1]) */
+    const uint64_t* text_offsets; /* [n_games + 1] */
+    uint64_t bytes;
+    uint32_t n_games, n_events;
+    double ms[3]; /* device format, copy to host (0 on device delivery), total */
+} RmjTextView;
+#define RMJ_TEXT_ON_DEVICE 2u /* with RMJ_DRAIN_PEEK (1u): the view's pointers are device pointers */
+int rmj_drain_text(rmj_handle h, uint32_t* cursor /*[n] in/out*/, int seat, uint32_t flags, RmjTextView* out);
+int rmj_format_events_device(rmj_handle h, const RmjEvent* d_ev, const uint32_t* d_offsets /*[n_games + 1]*/, uint32_t n_games, int seat,
+                             uint32_t flags, RmjTextView* out);
 
 /* ------------------------------------------------------------------ batched hand math (kernel gate) */
 typedef struct RmjHandCase {

@@ -203,6 +203,14 @@ class EventViews(C.Structure):   # RmjEventViews
                 ("ev_count_stride", C.c_uint32), ("reserved", C.c_uint32), ("lost", C.c_void_p), ("ev_base", C.c_void_p)]
 
 
+class TextView(C.Structure):     # RmjTextView (rmj_drain_text / rmj_format_events_device)
+    _fields_ = [("text", C.c_void_p), ("text_offsets", C.c_void_p), ("bytes", C.c_uint64), ("n_games", C.c_uint32), ("n_events", C.c_uint32),
+                ("ms", C.c_double * 3)]
+
+
+TEXT_ON_DEVICE = 2   # RMJ_TEXT_ON_DEVICE: the view's pointers are device pointers (with DRAIN_PEEK = 1)
+
+
 class Config(C.Structure):
     _fields_ = [("n_games", C.c_uint32), ("game_mode", C.c_uint8), ("skip_mjai_logging", C.c_uint8),
                 ("round_wind", C.c_uint8), ("reserved0", C.c_uint8), ("rule_bits", C.c_uint32),

@@ -21,6 +21,7 @@
 #include "rmj_encode.hip.h"
 #include "rmj_seq.hip.h"
 #include "rmj_host.h"
+#include "rmj_evtext.h"
 
 using namespace rmj;
 
@@ -1039,6 +1040,17 @@ struct rmj_env {
     std::vector<uint32_t> stage_cursor;
     void* h_pin = nullptr;          // pinned host staging of the host-buffer entry points (rmj_get_legal_compact, rmj_drain_*), grown on demand
     size_t pin_bytes = 0;
+    // buffers of the text calls (rmj_drain_text / rmj_format_events_device): what the last call's RmjTextView points at, grown on demand
+    char* d_txt = nullptr;          // device text
+    uint64_t txt_cap = 0;
+    uint64_t* d_txt_offs = nullptr; // device text offsets [games + 1]
+    size_t txt_offs_slots = 0;
+    void* d_txt_work = nullptr;     // sizes, stops and scan of the text calls
+    size_t txt_work_bytes = 0;
+    void* h_txt = nullptr;          // pinned text (host delivery)
+    uint64_t txt_pin_bytes = 0;
+    void* h_txt_offs = nullptr;     // pinned text offsets [games + 1], then the new cursors
+    size_t txt_pin_offs_bytes = 0;
     int enc_streams = 0;            // RMJ_ENC_STREAMS at create (0: want_streams): parts of the step + encode rollout
     int enc_parts_quad = -1;        // RMJ_ENC_PARTS_QUAD at create (-1: follow `quad`)
     int enc_fused = 1;              // RMJ_ENC_FUSED at create: the step + encode rollout as ONE launch (k_step4_enc / k_step4_queue_enc); 0 = parts on streams
@@ -1234,6 +1246,9 @@ int rmj_destroy(rmj_handle h) {
     hipFree(h->d.core); hipFree(h->d.wall); hipFree(h->d.wall_dg); hipFree(h->d.legal); hipFree(h->d.nlegal); hipFree(h->d_decay); if (h->d_scratch) hipFree(h->d_scratch); hipFree(h->d.mask);
     hipFree(h->d.waits); hipFree(h->d.status); hipFree(h->d.events); hipFree(h->d.win); hipFree(h->d_actions); hipFree(h->d_counter); hipFree(h->d_obs_offs); hipFree(h->d_env); hipFree(h->d_qheads);   // (d_qdone lives in the same allocation)
     hipFree(h->d_ev_lost); hipFree(h->d_track); hipFree(h->d_heavy);
+    hipFree(h->d_txt); hipFree(h->d_txt_offs); hipFree(h->d_txt_work);
+    if (h->h_txt) hipHostFree(h->h_txt);
+    if (h->h_txt_offs) hipHostFree(h->h_txt_offs);
     for (int i = 0; i < 2; i++) if (h->ev_time[i]) hipEventDestroy(h->ev_time[i]);
     if (h->own_stream) hipStreamDestroy(h->own_stream);
     for (int i = 0; i < RMJ_MAX_ROLLOUT_STREAMS - 1; i++) {
@@ -2321,6 +2336,320 @@ int rmj_drain_format(rmj_handle h, uint32_t* cursor, int seat, char* buf, uint64
         }
         memcpy(cursor, pin + ((size_t)n + 1) * 4, (size_t)n * 4);
     }
+    return RMJ_OK;
+}
+// ---- MJAI text on the device (rmj_drain_text / rmj_format_events_device) -------------------------
+// The host formatter's text (rmjh::format_events), byte for byte, written by the GPU with the per-record functions of rmj_evtext.h (the
+// host test holds them to the host formatter).  A game's window is either a run of its ring - stream positions [first[g], ev_count), as
+// k_ev_count computes them, read in place: no dense gather - or a run of caller records ev[offsets[g] .. offsets[g + 1]).
+//   k_text_size   one wave per game, a record per lane: evt_len; the game's stop = the min over its failing indices (the first set bit
+//                 of the first failing chunk's ballot); the game's bytes; the position behind the window (the new cursor).
+//   k_text_scan1 / k_text_scan2   the games' bytes to uint64 bases: an exclusive scan inside blocks of 256 games, then the block sums
+//                 by one workgroup of 1 024 (any number of blocks - 524 288 games are 2 048).
+//   k_text_write  one wave per game: chunks of up to 64 records - as many as fit the wave's LDS staging - are sized again and scanned in
+//                 the wave, each lane writes its record's text into the staging, and the staging goes out as aligned 16-byte stores;
+//                 only the unaligned head and tail bytes of the game's span are stored narrow.
+// The per-record rule (rmj_evtext.h): a TEHAI record gives 0 bytes, a START_KYOKU is a head iff the next two records of the window are
+// TEHAI, the log ends before the first other record that cannot be formatted.  A head in front of the stop has its two TEHAI records in
+// front of it too (the stop is not a TEHAI), so the write pass bounds the window by the stop.
+struct TextSrc {
+    const RmjEvent* ev;     // ring mode: the rings [n][ring]; records mode: the caller's records
+    uint32_t ring;          // ring size (a power of two); 0 = records mode
+    uint32_t rec_bytes;     // sizeof(RmjEvent), as an argument: record addresses are 32 x 32 -> 64-bit multiplies, not 64-bit shifts
+    const uint32_t* lo;     // ring mode: first[g] (a stream position); records mode: offsets [n + 1]
+    const GState* core;     // ring mode: core[g].ev_count ends the window
+};
+__device__ inline uint32_t text_end(const TextSrc& s, uint32_t g) { return s.ring ? s.core[g].ev_count : s.lo[g + 1]; }
+__device__ inline const RmjEvent* text_rec(const TextSrc& s, uint32_t g, uint32_t pos) {
+    const char* b = reinterpret_cast<const char*>(s.ev);
+    if (s.ring) return reinterpret_cast<const RmjEvent*>(b + (uint64_t)g * (s.ring * s.rec_bytes) + (pos & (s.ring - 1u)) * s.rec_bytes);
+    return reinterpret_cast<const RmjEvent*>(b + (uint64_t)pos * s.rec_bytes);
+}
+__device__ inline RmjEvent text_load(const RmjEvent* p) {   // one record in two 16-byte loads
+    union { uint4 q[2]; RmjEvent e; } u;
+    const uint4* q = reinterpret_cast<const uint4*>(p);
+    u.q[0] = q[0];
+    u.q[1] = q[1];
+    return u.e;
+}
+__device__ inline uint32_t text_incl_scan(uint32_t v, int lane) {
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t u = (uint32_t)__shfl_up((int)v, d, 64);
+        if (lane >= d) v += u;
+    }
+    return v;
+}
+__global__ __launch_bounds__(256) void k_text_size(TextSrc s, uint32_t n, int seat, uint32_t* __restrict__ nrec, uint32_t* __restrict__ bytes,
+                                                   uint32_t* __restrict__ newcur) {
+    const uint32_t g = blockIdx.x * 4u + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (g >= n) return;
+    const uint32_t lo = s.lo[g], cnt = text_end(s, g) - lo;
+    uint32_t total = 0, stop = cnt;
+    for (uint32_t k0 = 0; k0 < cnt; k0 += 64u) {
+        const uint32_t k = k0 + (uint32_t)lane;
+        int32_t len = 0;
+        if (k < cnt) {
+            const RmjEvent e = text_load(text_rec(s, g, lo + k));
+            len = rmjt::evt_len(e, k + 1u < cnt ? text_rec(s, g, lo + k + 1u) : nullptr, k + 2u < cnt ? text_rec(s, g, lo + k + 2u) : nullptr, seat);
+        }
+        const unsigned long long bad = __ballot(len < 0);
+        if (bad) {
+            const uint32_t f = (uint32_t)__ffsll(bad) - 1u;
+            stop = k0 + f;
+            if ((uint32_t)lane >= f) len = 0;
+        }
+        total += (uint32_t)__shfl((int)text_incl_scan((uint32_t)len, lane), 63, 64);
+        if (bad) break;
+    }
+    if (lane == 0) {
+        nrec[g] = stop;
+        bytes[g] = total;
+        if (newcur) newcur[g] = lo + cnt;
+    }
+}
+__global__ __launch_bounds__(256) void k_text_scan1(const uint32_t* __restrict__ bytes, uint32_t n, uint64_t* __restrict__ pre, uint64_t* __restrict__ blk) {
+    __shared__ uint64_t sc[256];
+    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+    const uint64_t c = g < n ? bytes[g] : 0u;
+    sc[threadIdx.x] = c;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {
+        uint64_t a = 0;
+        if ((int)threadIdx.x >= off) a = sc[threadIdx.x - off];
+        __syncthreads();
+        sc[threadIdx.x] += a;
+        __syncthreads();
+    }
+    if (g < n) pre[g] = sc[threadIdx.x] - c;
+    if (threadIdx.x == 255) blk[blockIdx.x] = sc[255];
+}
+// blk[0 .. blocks) -> exclusive bases; the total -> offs[n]
+__global__ __launch_bounds__(1024) void k_text_scan2(uint64_t* __restrict__ blk, uint32_t blocks, uint64_t* __restrict__ offs, uint32_t n,
+                                                     uint64_t* __restrict__ total) {
+    __shared__ uint64_t sc[1024];
+    const uint32_t per = (blocks + 1023u) / 1024u, b0 = threadIdx.x * per;
+    uint64_t c = 0;
+    for (uint32_t i = 0; i < per; i++)
+        if (b0 + i < blocks) c += blk[b0 + i];
+    sc[threadIdx.x] = c;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {
+        uint64_t a = 0;
+        if ((int)threadIdx.x >= off) a = sc[threadIdx.x - off];
+        __syncthreads();
+        sc[threadIdx.x] += a;
+        __syncthreads();
+    }
+    uint64_t r = sc[threadIdx.x] - c;
+    for (uint32_t i = 0; i < per; i++)
+        if (b0 + i < blocks) {
+            const uint64_t v = blk[b0 + i];
+            blk[b0 + i] = r;
+            r += v;
+        }
+    if (threadIdx.x == 1023) {
+        offs[n] = sc[1023];
+        total[0] = sc[1023];
+    }
+}
+#define TEXT_STAGE 4096u   // bytes of LDS staging per wave: 64 records of the longest kind do not fit, so a chunk takes what does (>= 1)
+static_assert(TEXT_STAGE >= 16u + rmjt::RMJT_MAX_EVENT_BYTES, "a record must fit behind a partial block");
+struct LdsSink {
+    char* p;
+    __device__ void put(char c) { *p++ = c; }
+};
+__global__ __launch_bounds__(64) void k_text_write(TextSrc s, uint32_t n, int seat, const uint32_t* __restrict__ nrec, const uint32_t* __restrict__ bytes,
+                                                   const uint64_t* __restrict__ pre, const uint64_t* __restrict__ blk, uint64_t* __restrict__ offs,
+                                                   char* __restrict__ text) {
+    __shared__ uint4 stage4[TEXT_STAGE / 16u];
+    char* const stage = reinterpret_cast<char*>(stage4);
+    const uint32_t g = blockIdx.x;
+    const int lane = threadIdx.x;
+    const uint64_t base = blk[g >> 8] + pre[g];
+    if (lane == 0) offs[g] = base;
+    const uint32_t lo = s.lo[g], m = nrec[g], span = bytes[g];
+    char* gp = text + (base & ~(uint64_t)15);    // the global address of stage[0]: 16-byte aligned
+    uint32_t fill = (uint32_t)base & 15u;        // bytes staged (the first `skip` of them are not this game's)
+    uint32_t skip = fill, done = 0;              // done: bytes of the span staged so far (never more than the size pass gave)
+    for (uint32_t k0 = 0; k0 < m;) {
+        const uint32_t k = k0 + (uint32_t)lane;
+        uint32_t len = 0;
+        RmjEvent e;
+        const RmjEvent *t1 = nullptr, *t2 = nullptr;
+        if (k < m) {
+            e = text_load(text_rec(s, g, lo + k));
+            if (e.type == RMJ_EV_START_KYOKU) {
+                t1 = k + 1u < m ? text_rec(s, g, lo + k + 1u) : nullptr;
+                t2 = k + 2u < m ? text_rec(s, g, lo + k + 2u) : nullptr;
+            }
+            const int32_t l = rmjt::evt_len(e, t1, t2, seat);
+            len = l > 0 ? (uint32_t)l : 0u;
+        }
+        const uint32_t incl = text_incl_scan(len, lane);
+        const bool fits = k < m && fill + incl <= TEXT_STAGE && done + incl <= span;
+        const uint32_t take = (uint32_t)__popcll(__ballot(fits));   // the lanes that fit are a prefix of the chunk
+        if (take == 0) break;                                         // (only if the records changed since the size pass)
+        if (fits && len) {
+            LdsSink o{stage + fill + incl - len};
+            rmjt::evt_write(o, e, t1, t2, seat);
+        }
+        const uint32_t chunk = (uint32_t)__shfl((int)incl, (int)take - 1, 64);
+        fill += chunk;
+        done += chunk;
+        k0 += take;
+        __syncthreads();
+        const uint32_t nb = fill >> 4;
+        for (uint32_t b = (uint32_t)lane; b < nb; b += 64u) {
+            if (b == 0 && skip) {   // the span's unaligned head: the block's first bytes belong to the game before
+                for (uint32_t j = skip; j < 16u; j++) gp[j] = stage[j];
+            } else {
+                *reinterpret_cast<uint4*>(gp + b * 16u) = stage4[b];
+            }
+        }
+        const uint32_t rem = fill & 15u;
+        if (nb) {   // the partial block moves to the front of the staging
+            const char c = (uint32_t)lane < rem ? stage[nb * 16u + lane] : 0;
+            __syncthreads();
+            if ((uint32_t)lane < rem) stage[lane] = c;
+            __syncthreads();
+            gp += nb * 16u;
+            fill = rem;
+            skip = 0;
+        }
+    }
+    if ((uint32_t)lane < fill && (uint32_t)lane >= skip) gp[lane] = stage[lane];   // the unaligned tail
+}
+// handle-owned buffers of the text calls: device text / offsets / work, pinned text / offsets + cursors; grown on demand
+static int text_device_room(rmj_env* h, uint32_t n_games) {
+    const uint32_t blocks = (n_games + 255u) / 256u;
+    const size_t work = (((size_t)n_games * 8 + 15) & ~(size_t)15) + (size_t)n_games * 8 + ((size_t)blocks + 2) * 8;
+    if (work > h->txt_work_bytes) {
+        HIPCHK(hipStreamSynchronize(h->stream));
+        hipFree(h->d_txt_work);
+        h->d_txt_work = nullptr; h->txt_work_bytes = 0;
+        HIPCHK(hipMalloc(&h->d_txt_work, work));
+        h->txt_work_bytes = work;
+    }
+    if ((size_t)n_games + 1 > h->txt_offs_slots) {
+        HIPCHK(hipStreamSynchronize(h->stream));
+        hipFree(h->d_txt_offs);
+        h->d_txt_offs = nullptr; h->txt_offs_slots = 0;
+        HIPCHK(hipMalloc(&h->d_txt_offs, ((size_t)n_games + 1) * 8));
+        h->txt_offs_slots = (size_t)n_games + 1;
+    }
+    return RMJ_OK;
+}
+// size, scan and write the text of n games (n > 0) into the handle's device buffers; *bytes = the text's size
+static int text_format_device(rmj_env* h, const TextSrc& s, uint32_t n, int seat, uint32_t* d_newcur, uint64_t* bytes) {
+    int rc = text_device_room(h, n);
+    if (rc) return rc;
+    const uint32_t blocks = (n + 255u) / 256u;
+    uint8_t* w = (uint8_t*)h->d_txt_work;
+    uint32_t* d_nrec = (uint32_t*)w;
+    uint32_t* d_bytes = d_nrec + n;
+    uint64_t* d_pre = (uint64_t*)(w + (((size_t)n * 8 + 15) & ~(size_t)15));
+    uint64_t* d_blk = d_pre + n;   // [blocks] + the total
+    hipLaunchKernelGGL(k_text_size, dim3((n + 3u) / 4u), dim3(256), 0, h->stream, s, n, seat, d_nrec, d_bytes, d_newcur);
+    hipLaunchKernelGGL(k_text_scan1, dim3(blocks), dim3(256), 0, h->stream, (const uint32_t*)d_bytes, n, d_pre, d_blk);
+    hipLaunchKernelGGL(k_text_scan2, dim3(1), dim3(1024), 0, h->stream, d_blk, blocks, h->d_txt_offs, n, d_blk + blocks);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(bytes, d_blk + blocks, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (*bytes > h->txt_cap || !h->d_txt) {
+        hipFree(h->d_txt);
+        h->d_txt = nullptr; h->txt_cap = 0;
+        const uint64_t cap = *bytes + *bytes / 8 + (1u << 20);   // growth headroom: the next drain of a similar batch fits
+        HIPCHK(hipMalloc(&h->d_txt, cap));
+        h->txt_cap = cap;
+    }
+    hipLaunchKernelGGL(k_text_write, dim3(n), dim3(64), 0, h->stream, s, n, seat, (const uint32_t*)d_nrec, (const uint32_t*)d_bytes, (const uint64_t*)d_pre,
+                       (const uint64_t*)d_blk, h->d_txt_offs, h->d_txt);
+    HIPCHK(hipGetLastError());
+    return RMJ_OK;
+}
+// device view, or the one copy to pinned memory owned by the handle; returns with the stream synchronised
+static int text_deliver(rmj_env* h, uint32_t n, uint64_t bytes, uint32_t flags, const uint32_t* d_newcur, uint32_t* cursor, RmjTextView* out,
+                        std::chrono::steady_clock::time_point t0) {
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    HIPCHK(hipStreamSynchronize(h->stream));
+    auto t1 = now();
+    const size_t offs_b = ((size_t)n + 1) * 8, cur_b = cursor ? (size_t)n * 4 : 0;
+    if (offs_b + cur_b > h->txt_pin_offs_bytes) {
+        if (h->h_txt_offs) hipHostFree(h->h_txt_offs);
+        h->h_txt_offs = nullptr; h->txt_pin_offs_bytes = 0;
+        HIPCHK(hipHostMalloc(&h->h_txt_offs, offs_b + cur_b, hipHostMallocDefault));
+        h->txt_pin_offs_bytes = offs_b + cur_b;
+    }
+    const bool host = !(flags & RMJ_TEXT_ON_DEVICE);
+    if (host && bytes > h->txt_pin_bytes) {
+        if (h->h_txt) hipHostFree(h->h_txt);
+        h->h_txt = nullptr; h->txt_pin_bytes = 0;
+        const uint64_t cap = bytes + bytes / 8 + (1u << 20);
+        HIPCHK(hipHostMalloc(&h->h_txt, cap, hipHostMallocDefault));
+        h->txt_pin_bytes = cap;
+    }
+    uint8_t* pin = (uint8_t*)h->h_txt_offs;
+    if (host) {
+        if (bytes) HIPCHK(hipMemcpyAsync(h->h_txt, h->d_txt, bytes, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(pin, h->d_txt_offs, offs_b, hipMemcpyDeviceToHost, h->stream));
+    }
+    if (cur_b) HIPCHK(hipMemcpyAsync(pin + offs_b, d_newcur, cur_b, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    auto t2 = now();
+    if (cur_b) memcpy(cursor, pin + offs_b, cur_b);
+    out->text = host ? (const char*)h->h_txt : (const char*)h->d_txt;
+    out->text_offsets = host ? (const uint64_t*)pin : (const uint64_t*)h->d_txt_offs;
+    out->bytes = bytes;
+    out->n_games = n;
+    out->ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    out->ms[1] = host ? std::chrono::duration<double, std::milli>(t2 - t1).count() : 0.0;
+    out->ms[2] = std::chrono::duration<double, std::milli>(t2 - t0).count();
+    return RMJ_OK;
+}
+int rmj_drain_text(rmj_handle h, uint32_t* cursor, int seat, uint32_t flags, RmjTextView* out) {
+    if (!h || !cursor || !out) return fail(RMJ_ERR_ARG, "null argument");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    auto t0 = std::chrono::steady_clock::now();
+    const uint32_t n = h->cfg.n_games;
+    h->stage_valid = false;
+    DrainPlan P;
+    uint32_t n_ev = 0;
+    int rc = drain_device(h, cursor, 0, &P, &n_ev);   // the windows: first[g] (no record buffer)
+    if (rc) return rc;
+    const TextSrc s{(const RmjEvent*)h->d.events, h->ring, (uint32_t)sizeof(RmjEvent), P.d_first, (const GState*)h->d.core};
+    uint64_t bytes = 0;
+    rc = text_format_device(h, s, n, seat, P.d_new, &bytes);
+    if (rc) return rc;
+    const bool peek = (flags & RMJ_DRAIN_PEEK) != 0;
+    if (!peek) drain_book(h, P);
+    HIPCHK(hipGetLastError());
+    rc = text_deliver(h, n, bytes, flags, P.d_new, peek ? nullptr : cursor, out, t0);
+    if (rc) return rc;
+    out->n_events = n_ev;
+    return RMJ_OK;
+}
+int rmj_format_events_device(rmj_handle h, const RmjEvent* d_ev, const uint32_t* d_offsets, uint32_t n_games, int seat, uint32_t flags, RmjTextView* out) {
+    if (!h || !d_offsets || !out || (!d_ev && n_games)) return fail(RMJ_ERR_ARG, "null argument");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    auto t0 = std::chrono::steady_clock::now();
+    h->stage_valid = false;
+    uint64_t bytes = 0;
+    if (n_games) {
+        const TextSrc s{d_ev, 0u, (uint32_t)sizeof(RmjEvent), d_offsets, nullptr};
+        int rc = text_format_device(h, s, n_games, seat, nullptr, &bytes);
+        if (rc) return rc;
+    } else {
+        int rc = text_device_room(h, 0);
+        if (rc) return rc;
+        HIPCHK(hipMemsetAsync(h->d_txt_offs, 0, 8, h->stream));
+    }
+    uint32_t ends[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(&ends[0], d_offsets, 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(&ends[1], d_offsets + n_games, 4, hipMemcpyDeviceToHost, h->stream));
+    int rc = text_deliver(h, n_games, bytes, flags, nullptr, nullptr, out, t0);
+    if (rc) return rc;
+    out->n_events = ends[1] - ends[0];
     return RMJ_OK;
 }
 static int round_track_impl(rmj_env* h, int baseline, uint8_t* d_ended, int32_t* d_delta, int32_t* d_meta, uint8_t* d_kyoku_idx) {

@@ -272,6 +272,21 @@ class TorchVecEnv:
         if not self.shared:
             vecenv._chk(self.env.L.rmj_sync(self.env.h))
 
+    def drain_text(self, seat=-1, cursor=None, peek=False, timings=None):
+        """The MJAI text every game logged since the last drain, formatted on the GPU and left there (rmj_drain_text with
+        RMJ_TEXT_ON_DEVICE): (text torch.uint8 [bytes], offsets torch.int64 [n + 1]) on this device - game g's log is
+        text[offsets[g]:offsets[g + 1]], its events each followed by a newline; the same bytes as VecRiichiEnv.drain_logs(raw=True).
+        Both tensors are zero-copy views of the library's buffers: valid until the next drain_text on this environment (clone what must
+        outlive it).  The call returns with the text complete, so any stream may read it at once.  Cursor, peek and timings as in
+        VecRiichiEnv.drain_text.  Note: TorchVecEnv defaults to skip_mjai_logging=True, which logs nothing - the logs are then empty;
+        create it with skip_mjai_logging=False to have them."""
+        v = self.env._text_call(seat, cursor, peek, True)
+        if timings is not None:
+            timings[:] = [v.ms[0], v.ms[1], v.ms[2]]
+        wrap = lambda ptr, shape, ts: self.torch.as_tensor(_CudaArray(ptr, shape, ts, self), device=self.device)  # noqa: E731
+        text = wrap(v.text, (int(v.bytes),), "|u1") if v.bytes else self.torch.zeros(0, dtype=self.torch.uint8, device=self.device)
+        return text, wrap(v.text_offsets, (v.n_games + 1,), "<i8")
+
     def copy_games(self, dst_idx, src_env, src_idx):
         """rmj_copy_games_device: the complete state of src_env's games `src_idx` into this environment's games `dst_idx` (int32 /
         int64 tensors on this device; src_env may be self when the two index sets are disjoint) - forks for a tree search that

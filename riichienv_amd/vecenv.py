@@ -34,6 +34,7 @@ EXPORTS = [
     "rmj_encode_compact_device", "rmj_step_random_encode_compact", "rmj_bench_encode_compact",
     "rmj_get_win_results",
     "rmj_drain_events", "rmj_format_events", "rmj_drain_format", "rmj_event_views", "rmj_round_track_device", "rmj_round_track_reset", "rmj_get_events_lost", "rmj_get_log_positions",
+    "rmj_drain_text", "rmj_format_events_device",
 ]
 
 
@@ -156,6 +157,8 @@ def load_lib():
     L.rmj_get_events_lost.argtypes = [vp, vp]
     L.rmj_round_track_device.argtypes = [vp, vp, vp, vp, vp]
     L.rmj_round_track_reset.argtypes = [vp]
+    L.rmj_drain_text.argtypes = [vp, vp, C.c_int, C.c_uint32, C.POINTER(abi.TextView)]
+    L.rmj_format_events_device.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, C.c_uint32, C.POINTER(abi.TextView)]
     _LIB = L
     return L
 
@@ -538,6 +541,43 @@ class VecRiichiEnv:
             timings[:] = [ms[0], ms[1], ms[2]]
         self.last_drain_events = n_ev.value
         return (buf, toffs) if raw else self._split_logs(buf, toffs)
+
+    def _text_call(self, seat, cursor, peek, on_device):
+        """rmj_drain_text into the handle's buffers: the RmjTextView (cursor None: the env's running cursor)"""
+        cur = self._log_cursor() if cursor is None else cursor
+        v = abi.TextView()
+        fl = (1 if peek else 0) | (abi.TEXT_ON_DEVICE if on_device else 0)
+        _chk(self.L.rmj_drain_text(self.h, cur.ctypes.data, int(seat), fl, C.byref(v)))
+        self.last_drain_events = v.n_events
+        return v
+
+    @staticmethod
+    def _host_text(v):
+        """zero-copy numpy views of a host-delivered RmjTextView: (uint8 [bytes], uint64 [n + 1])"""
+        offs = np.ctypeslib.as_array((C.c_uint64 * (v.n_games + 1)).from_address(v.text_offsets))
+        text = np.ctypeslib.as_array((C.c_uint8 * v.bytes).from_address(v.text)) if v.bytes else np.zeros(0, np.uint8)
+        return text, offs
+
+    def drain_text(self, seat=-1, cursor=None, peek=False, timings=None, split=False):
+        """The MJAI text every slot logged since the last drain, formatted on the GPU (rmj_drain_text): the same bytes and offsets as
+        drain_logs(raw=True), delivered with ONE copy from the device into pinned memory owned by the library.  Returns (text uint8 [bytes],
+        offsets uint64 [n + 1]) - game g's log is text[offsets[g]:offsets[g + 1]], its events each followed by a newline.  Both arrays are
+        zero-copy views of the library's pinned buffers: valid until the next drain_text / format_events_device on this env (copy what
+        must outlive it).  Cursor, peek and the loss counting as in drain_logs (the env's running cursor by default).  timings: a list that
+        receives [device format, copy, total] ms.  split=True: the list of lists of strings drain_logs returns."""
+        v = self._text_call(seat, cursor, peek, False)
+        if timings is not None:
+            timings[:] = [v.ms[0], v.ms[1], v.ms[2]]
+        text, offs = self._host_text(v)
+        return self._split_logs(text, offs) if split else (text, offs)
+
+    def format_events_device(self, d_events, d_offsets, n_games, seat=-1, on_device=False):
+        """rmj_format_events_device: the text of records already on the device (d_events: device address of RmjEvent records, d_offsets:
+        device address of [n_games + 1] u32 offsets).  Returns the RmjTextView (on_device=False: host pointers, readable with _host_text)."""
+        v = abi.TextView()
+        _chk(self.L.rmj_format_events_device(self.h, C.c_void_p(int(d_events)), C.c_void_p(int(d_offsets)), int(n_games), int(seat),
+                                             abi.TEXT_ON_DEVICE if on_device else 0, C.byref(v)))
+        return v
 
     def mjai_logs(self, seat=-1):
         """The current game's log of every slot as far as its ring still holds it (RiichiEnv.mjai_log of every env): a peek from the
