@@ -70,6 +70,13 @@ def lib():
                                         C.c_int, C.POINTER(C.c_double)]
         L.orc_rollout_policy.argtypes = ([C.c_int, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.c_uint64, C.c_uint32,
                                           C.c_uint32, C.c_int] + [C.c_void_p] * 6 + [C.c_int] + [C.c_void_p] * 9)
+        L.orc_batch_new.restype = C.c_void_p
+        L.orc_batch_new.argtypes = [C.c_int, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32] + [C.c_void_p] * 6 + [C.c_int]
+        L.orc_batch_free.argtypes = [C.c_void_p]
+        L.orc_batch_step.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int]
+        L.orc_batch_state.argtypes = [C.c_void_p] * 10
+        L.orc_batch_encode_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]
+        L.orc_batch_aux.argtypes = [C.c_void_p] * 3
         L.orc_log_digest.restype = C.c_uint64
         L.orc_log_digest.argtypes = [C.c_char_p, C.c_uint64]
         L.orc_game_wall_meta.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
@@ -342,6 +349,33 @@ def text_digest(text: bytes):
 POLICIES = {"random": 0, "greedy": 1}
 
 
+def default_threads():
+    """host threads of the batch calls: OMP_NUM_THREADS, else the CPUs this process may run on, at most 16 (the CPU share of one job
+    on a GPU machine; os.cpu_count() counts the whole machine)"""
+    n = int(os.environ.get("OMP_NUM_THREADS") or 0) or len(os.sched_getaffinity(0))
+    return max(1, min(n, 16))
+
+
+def _reset_args(n, sanma, walls, oya, round_wind, scores, honba, kyotaku):
+    """per-game reset arguments as contiguous arrays (walls padded to 136 tiles, scores to 4 seats) or None"""
+    def per_game(a, dt, width=None):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(np.asarray(a).reshape((n,) if width is None else (n, -1)), dtype=dt)
+        if width is not None and a.shape[1] < width:
+            a = np.ascontiguousarray(np.concatenate([a, np.zeros((n, width - a.shape[1]), dt)], axis=1))
+        return a
+
+    if scores is not None and np.asarray(scores).reshape(n, -1).shape[1] != (3 if sanma else 4):
+        raise ValueError("scores: one per seat")
+    return [per_game(walls, np.uint8, 136), per_game(oya, np.int32), per_game(round_wind, np.int32), per_game(scores, np.int32, 4),
+            per_game(honba, np.int32), per_game(kyotaku, np.int32)]
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
 def rollout_policy(game_mode, rule_bits, seed, n, policy, policy_seed, n_steps, call_rate_256=64, auto_reset=True, game_offset=0,
                    walls=None, oya=None, round_wind=None, scores=None, honba=None, kyotaku=None, threads=None):
     """n games (global indices game_offset + g, episode seeds shard.game_seed(seed, game_offset + g)) stepped n_steps env steps under a
@@ -351,30 +385,79 @@ def rollout_policy(game_mode, rule_bits, seed, n, policy, policy_seed, n_steps, 
     walls [n][136 or 108], a row that starts with 255 = the game shuffles its own).  Returns a dict of arrays: status [n, 3] (active mask, phase, done), views (StateView * n), steps [n],
     scores [n, 4], legal [n, 4, MAX_LEGAL] and legal_count [n, 4], mask [n, 4, 82], waits [n, 4] (acting seats; others zero), and
     digest [n]: log_digest of every line the game logged, the finished games' logs and the current one in order."""
-    sanma = game_mode >= 3
-
-    def per_game(a, dt, width=None):
-        if a is None:
-            return None
-        a = np.ascontiguousarray(np.asarray(a).reshape((n,) if width is None else (n, -1)), dtype=dt)
-        if width is not None and a.shape[1] < width:
-            a = np.ascontiguousarray(np.concatenate([a, np.zeros((n, width - a.shape[1]), dt)], axis=1))
-        return a
-
-    args = [per_game(walls, np.uint8, 136), per_game(oya, np.int32), per_game(round_wind, np.int32), per_game(scores, np.int32, 4),
-            per_game(honba, np.int32), per_game(kyotaku, np.int32)]
-    if scores is not None and np.asarray(scores).reshape(n, -1).shape[1] != (3 if sanma else 4):
-        raise ValueError("scores: one per seat")
+    args = _reset_args(n, game_mode >= 3, walls, oya, round_wind, scores, honba, kyotaku)
     out = dict(status=np.zeros((n, 3), np.uint8), views=(abi.StateView * max(n, 1))(), steps=np.zeros(n, np.uint64),
                scores=np.zeros((n, 4), np.int32), legal=np.zeros((n, 4, abi.MAX_LEGAL), np.uint64),
                legal_count=np.zeros((n, 4), np.uint32), mask=np.zeros((n, 4, 82), np.uint8), waits=np.zeros((n, 4), np.uint64),
                digest=np.zeros(n, np.uint64))
-    threads = threads or max(1, min(os.cpu_count() or 1, 32))
     rc = lib().orc_rollout_policy(game_mode, rule_bits, seed, game_offset, n, POLICIES[policy], policy_seed, call_rate_256, n_steps,
-                                  int(auto_reset), *[None if a is None else a.ctypes.data for a in args], threads,
+                                  int(auto_reset), *[_ptr(a) for a in args], threads or default_threads(),
                                   out["status"].ctypes.data, out["views"], out["steps"].ctypes.data, out["scores"].ctypes.data,
                                   out["legal"].ctypes.data, out["legal_count"].ctypes.data, out["mask"].ctypes.data,
                                   out["waits"].ctypes.data, out["digest"].ctypes.data)
     if rc:
         raise ValueError(f"orc_rollout_policy: {rc}")
     return out
+
+
+class Batch:
+    """n oracle games kept between calls (orc_batch_*): set up as rollout_policy sets them up (the same arguments), stepped k env steps
+    at a time under a device policy's twin - k calls of step(1) reach what rollout_policy(n_steps=k) returns - and read in between:
+    state() (rollout_policy's outputs), encode / encode_extended of chosen (game, seat) rows, and the aux blocks of every game.  Every
+    call spreads its games or rows over `threads` host threads (default_threads())."""
+
+    def __init__(self, game_mode, rule_bits, seed, n, game_offset=0, walls=None, oya=None, round_wind=None, scores=None, honba=None,
+                 kyotaku=None, threads=None):
+        self.L = lib()
+        self.n, self.sanma = n, game_mode >= 3
+        self.np_, self.w = (3, 27) if self.sanma else (4, 34)
+        args = _reset_args(n, self.sanma, walls, oya, round_wind, scores, honba, kyotaku)
+        self.h = self.L.orc_batch_new(game_mode, rule_bits, seed, game_offset, n, *[_ptr(a) for a in args], threads or default_threads())
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            self.L.orc_batch_free(self.h)
+            self.h = None
+
+    def step(self, policy, policy_seed, n_steps=1, call_rate_256=64, auto_reset=True):
+        if self.L.orc_batch_step(self.h, POLICIES[policy], policy_seed, call_rate_256, n_steps, int(auto_reset)):
+            raise ValueError(f"policy {policy}")
+
+    def status(self):
+        st = np.zeros((self.n, 3), np.uint8)
+        self.L.orc_batch_state(self.h, st.ctypes.data, *[None] * 8)
+        return st
+
+    def state(self):
+        """rollout_policy's outputs for the games as they stand"""
+        n = self.n
+        out = dict(status=np.zeros((n, 3), np.uint8), views=(abi.StateView * max(n, 1))(), steps=np.zeros(n, np.uint64),
+                   scores=np.zeros((n, 4), np.int32), legal=np.zeros((n, 4, abi.MAX_LEGAL), np.uint64),
+                   legal_count=np.zeros((n, 4), np.uint32), mask=np.zeros((n, 4, 82), np.uint8), waits=np.zeros((n, 4), np.uint64),
+                   digest=np.zeros(n, np.uint64))
+        self.L.orc_batch_state(self.h, out["status"].ctypes.data, C.addressof(out["views"]), out["steps"].ctypes.data,
+                               out["scores"].ctypes.data, out["legal"].ctypes.data, out["legal_count"].ctypes.data,
+                               out["mask"].ctypes.data, out["waits"].ctypes.data, out["digest"].ctypes.data)
+        return out
+
+    def _rows(self, games, seats, extended):
+        rows = np.ascontiguousarray(np.stack([np.asarray(games, np.int32).ravel(), np.asarray(seats, np.int32).ravel()], axis=1))
+        out = np.zeros((len(rows), 215 if extended else 74, self.w), np.float32)
+        if len(rows) and self.L.orc_batch_encode_rows(self.h, rows.ctypes.data, len(rows), int(extended), out.ctypes.data):
+            raise IndexError("a row names a game or seat the batch does not have")
+        return out
+
+    def encode_extended(self, games, seats):
+        """Game.encode_extended of the rows (games[i], seats[i]): [m, 215, W]"""
+        return self._rows(games, seats, True)
+
+    def encode(self, games, seats):
+        """Game.encode of the rows (games[i], seats[i]): [m, 74, W]"""
+        return self._rows(games, seats, False)
+
+    def aux(self):
+        """(encode_kawa_overview [n, NP, 7, W], encode_yaku_possibility [n, NP, 21, 2]) of every game"""
+        kawa = np.zeros((self.n, self.np_, 7, self.w), np.float32)
+        yaku = np.zeros((self.n, self.np_, 21, 2), np.float32)
+        self.L.orc_batch_aux(self.h, kawa.ctypes.data, yaku.ctypes.data)
+        return kawa, yaku

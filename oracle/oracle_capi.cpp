@@ -2,7 +2,11 @@
 // C wrapper (ctypes-friendly) around the CPU restatement in riichi_core.hpp /
 // riichi_state.hpp.  Uses the POD views of include/riichi_mi355x.h so tests can
 // compare the oracle and the HIP path byte for byte.
+#include <atomic>
 #include <chrono>
+#include <condition_variable>
+#include <functional>
+#include <mutex>
 #include <cmath>
 #include <algorithm>
 #include <cstdio>
@@ -1281,6 +1285,91 @@ uint64_t orc_log_digest(const uint8_t* text, uint64_t len) {
     for (uint64_t i = 0; i < len; i++) { h ^= text[i]; h *= 0x100000001B3ull; }
     return h;
 }
+// One game of a batch rolled out under a device policy's oracle twin: the GameState, its global index and the FNV-1a 64 of every line
+// it logged before its last restart (what drain_logs hands out across restarts).
+struct RolloutGame {
+    GameState* s = nullptr;
+    uint64_t G = 0, h = 0xCBF29CE484222325ull;
+    bool first = true;
+};
+// global index game_offset + g, episode seed splitmix64(base_seed + game_offset + g) = shard.game_seed; reset arguments of the first deal
+// as orc_rollout_policy takes them
+static void rollout_game_init(RolloutGame& r, int game_mode, uint32_t rule_bits, uint64_t base_seed, uint64_t game_offset, uint32_t g,
+                              const uint8_t* walls, const int32_t* oya, const int32_t* round_wind, const int32_t* scores, const int32_t* honba,
+                              const int32_t* kyotaku) {
+    r.G = game_offset + g;
+    r.s = new GameState((uint8_t)game_mode, false, splitmix64(base_seed + r.G), 0, GameRule::from_bits(rule_bits),
+                        (rule_bits & RMJ_RULE_REFERENCE_RNG) != 0);
+    orc_game_reset(r.s, walls && walls[(size_t)g * 136] != 0xFF ? walls + (size_t)g * 136 : nullptr, oya ? oya[g] : -1, round_wind ? round_wind[g] : -1,
+                   scores ? scores + (size_t)g * 4 : nullptr, honba ? honba[g] : -1, kyotaku ? kyotaku[g] : -1);
+}
+// n_steps env steps, exactly as a test steps oracle.Game: a finished game is reset with the defaults (auto_reset; that step acts on
+// nothing) or left alone
+static void rollout_game_steps(RolloutGame& r, int policy, uint64_t policy_seed, uint32_t call_rate_256, uint32_t n_steps, int auto_reset) {
+    GameState* s = r.s;
+    rmj_action_t acts[4];
+    for (uint32_t k = 0; k < n_steps; k++) {
+        if (s->is_done) {
+            if (auto_reset) {
+                for (const auto& line : s->mjai_log) fnv1a_line(r.h, r.first, line);
+                s->env_reset(-1, nullptr, -1, nullptr, -1, -1);
+            }
+            continue;
+        }
+        if (policy == 0) orc_game_random_actions(s, policy_seed, r.G, acts);
+        else orc_game_greedy_actions(s, policy_seed, r.G, call_rate_256, acts);
+        orc_game_step(s, acts);
+    }
+}
+// the per-game outputs of orc_rollout_policy (any pointer may be NULL)
+static void rollout_game_outputs(const RolloutGame& r, uint32_t g, uint8_t* status, RmjStateView* views, uint64_t* step_counts,
+                                 int32_t* scores_out, rmj_action_t* legal, uint32_t* legal_cnt, uint8_t* masks, uint64_t* waits,
+                                 uint64_t* digest) {
+    GameState* s = r.s;
+    if (digest) {
+        uint64_t h = r.h;
+        bool first = r.first;
+        for (const auto& line : s->mjai_log) fnv1a_line(h, first, line);
+        digest[g] = h;
+    }
+    if (status) orc_game_status(s, status + (size_t)g * 3, status + (size_t)g * 3 + 1, status + (size_t)g * 3 + 2);
+    if (views) orc_game_peek(s, views + g);
+    if (step_counts) step_counts[g] = s->step_count;
+    if (scores_out)
+        for (int p = 0; p < 4; p++) scores_out[(size_t)g * 4 + p] = p < s->NP ? s->players[p].score : 0;
+    if (legal) std::memset(legal + (size_t)g * 4 * RMJ_MAX_LEGAL, 0, 4 * RMJ_MAX_LEGAL * sizeof(rmj_action_t));
+    if (legal_cnt) std::memset(legal_cnt + (size_t)g * 4, 0, 4 * sizeof(uint32_t));
+    if (masks) std::memset(masks + (size_t)g * 4 * 82, 0, 4 * 82);
+    if (waits) std::memset(waits + (size_t)g * 4, 0, 4 * sizeof(uint64_t));
+    if (!s->is_done)
+        for (uint8_t p : s->active_players) {
+            rmj_action_t tmp[RMJ_MAX_LEGAL];
+            const int nl = std::min(orc_game_legal(s, p, legal ? legal + ((size_t)g * 4 + p) * RMJ_MAX_LEGAL : tmp), RMJ_MAX_LEGAL);
+            if (legal_cnt) legal_cnt[(size_t)g * 4 + p] = (uint32_t)nl;
+            if (masks) orc_game_mask(s, p, masks + ((size_t)g * 4 + p) * 82);
+            if (waits) waits[(size_t)g * 4 + p] = orc_game_waits(s, p);
+        }
+}
+// f(i) for i < n over `threads` host threads, items handed out in chunks from a shared counter (rows differ a lot in cost)
+}  // extern "C"
+template <class F>
+static void parallel_for(int threads, uint32_t n, F f) {
+    if (threads < 1) threads = 1;
+    std::atomic<uint32_t> next{0};
+    auto work = [&]() {
+        for (;;) {
+            const uint32_t i0 = next.fetch_add(8);
+            if (i0 >= n) return;
+            for (uint32_t i = i0; i < n && i < i0 + 8; i++) f(i);
+        }
+    };
+    std::vector<std::thread> th;
+    for (int t = 1; t < threads; t++) th.emplace_back(work);
+    work();
+    for (auto& t : th) t.join();
+}
+extern "C" {
+
 // Steps n games g (global index game_offset + g, episode seed splitmix64(base_seed + game_offset + g) = shard.game_seed) for n_steps env
 // steps under a device policy's oracle twin - policy 0: the RandomAgent (orc_game_random_actions), 1: greedy (orc_game_greedy_actions with
 // call_rate_256) - exactly as a test steps oracle.Game: a finished game is reset (auto_reset; that step acts on nothing) or left alone.
@@ -1296,52 +1385,138 @@ int orc_rollout_policy(int game_mode, uint32_t rule_bits, uint64_t base_seed, ui
                        int threads, uint8_t* status, RmjStateView* views, uint64_t* step_counts, int32_t* scores_out,
                        rmj_action_t* legal, uint32_t* legal_cnt, uint8_t* masks, uint64_t* waits, uint64_t* digest) {
     if (policy != 0 && policy != 1) return -1;
-    if (threads < 1) threads = 1;
-    auto work = [&](int tid) {
-        for (uint32_t g = tid; g < n; g += threads) {
-            const uint64_t G = game_offset + g;
-            GameState* s = new GameState((uint8_t)game_mode, false, splitmix64(base_seed + G), 0, GameRule::from_bits(rule_bits),
-                                         (rule_bits & RMJ_RULE_REFERENCE_RNG) != 0);
-            orc_game_reset(s, walls && walls[(size_t)g * 136] != 0xFF ? walls + (size_t)g * 136 : nullptr, oya ? oya[g] : -1, round_wind ? round_wind[g] : -1,
-                           scores ? scores + (size_t)g * 4 : nullptr, honba ? honba[g] : -1, kyotaku ? kyotaku[g] : -1);
-            uint64_t h = 0xCBF29CE484222325ull;
-            bool first = true;
-            rmj_action_t acts[4];
-            for (uint32_t k = 0; k < n_steps; k++) {
-                if (s->is_done) {
-                    if (auto_reset) {
-                        for (const auto& line : s->mjai_log) fnv1a_line(h, first, line);
-                        s->env_reset(-1, nullptr, -1, nullptr, -1, -1);
-                    }
-                    continue;
-                }
-                if (policy == 0) orc_game_random_actions(s, policy_seed, G, acts);
-                else orc_game_greedy_actions(s, policy_seed, G, call_rate_256, acts);
-                orc_game_step(s, acts);
-            }
-            for (const auto& line : s->mjai_log) fnv1a_line(h, first, line);
-            digest[g] = h;
-            orc_game_status(s, status + (size_t)g * 3, status + (size_t)g * 3 + 1, status + (size_t)g * 3 + 2);
-            orc_game_peek(s, views + g);
-            step_counts[g] = s->step_count;
-            for (int p = 0; p < 4; p++) scores_out[(size_t)g * 4 + p] = p < s->NP ? s->players[p].score : 0;
-            std::memset(legal + (size_t)g * 4 * RMJ_MAX_LEGAL, 0, 4 * RMJ_MAX_LEGAL * sizeof(rmj_action_t));
-            std::memset(legal_cnt + (size_t)g * 4, 0, 4 * sizeof(uint32_t));
-            std::memset(masks + (size_t)g * 4 * 82, 0, 4 * 82);
-            std::memset(waits + (size_t)g * 4, 0, 4 * sizeof(uint64_t));
-            if (!s->is_done)
-                for (uint8_t p : s->active_players) {
-                    legal_cnt[(size_t)g * 4 + p] = (uint32_t)std::min(orc_game_legal(s, p, legal + ((size_t)g * 4 + p) * RMJ_MAX_LEGAL), RMJ_MAX_LEGAL);
-                    orc_game_mask(s, p, masks + ((size_t)g * 4 + p) * 82);
-                    waits[(size_t)g * 4 + p] = orc_game_waits(s, p);
-                }
-            delete s;
-        }
-    };
-    std::vector<std::thread> th;
-    for (int t = 0; t < threads; t++) th.emplace_back(work, t);
-    for (auto& t : th) t.join();
+    parallel_for(threads, n, [&](uint32_t g) {
+        RolloutGame r;
+        rollout_game_init(r, game_mode, rule_bits, base_seed, game_offset, g, walls, oya, round_wind, scores, honba, kyotaku);
+        rollout_game_steps(r, policy, policy_seed, call_rate_256, n_steps, auto_reset);
+        rollout_game_outputs(r, g, status, views, step_counts, scores_out, legal, legal_cnt, masks, waits, digest);
+        delete r.s;
+    });
     return 0;
+}
+
+// ---------------------------------------------------------------- a batch of oracle games kept between calls (tests)
+// orc_rollout_policy cut into steps: the handle owns n games set up as orc_rollout_policy sets them up (same arguments), orc_batch_step
+// advances every game k env steps under a policy twin (k calls of 1 step = one call of k steps = orc_rollout_policy with the sum), and
+// between steps the caller reads the state and the encoders.  Every call spreads its games or rows over the handle's `threads`.
+// Its threads live as long as the handle: the shanten memo of the extended encoder is per thread (riichi_shanten.hpp suit_cost_memo)
+// and would start cold in threads made for one call.
+struct OrcPool {
+    std::vector<std::thread> th;
+    std::mutex mu;
+    std::condition_variable wake, idle;
+    std::function<void(uint32_t)> job;
+    std::atomic<uint32_t> next{0};
+    uint32_t n = 0;
+    int gen = 0, busy = 0;
+    bool stop = false;
+    explicit OrcPool(int threads) {
+        for (int t = 1; t < threads; t++)
+            th.emplace_back([this] {
+                int seen = 0;
+                for (;;) {
+                    {
+                        std::unique_lock<std::mutex> l(mu);
+                        wake.wait(l, [&] { return stop || gen != seen; });
+                        if (stop) return;
+                        seen = gen;
+                    }
+                    drain();
+                    std::lock_guard<std::mutex> l(mu);
+                    if (--busy == 0) idle.notify_all();
+                }
+            });
+    }
+    void drain() {
+        for (;;) {
+            const uint32_t i0 = next.fetch_add(8);
+            if (i0 >= n) return;
+            for (uint32_t i = i0; i < n && i < i0 + 8; i++) job(i);
+        }
+    }
+    // f(i) for i < n_items over the pool and the calling thread; returns when every item is done
+    void run(uint32_t n_items, std::function<void(uint32_t)> f) {
+        {
+            std::lock_guard<std::mutex> l(mu);
+            job = std::move(f);
+            n = n_items;
+            next = 0;
+            busy = (int)th.size();
+            gen++;
+        }
+        wake.notify_all();
+        drain();
+        std::unique_lock<std::mutex> l(mu);
+        idle.wait(l, [&] { return busy == 0; });
+    }
+    ~OrcPool() {
+        {
+            std::lock_guard<std::mutex> l(mu);
+            stop = true;
+        }
+        wake.notify_all();
+        for (auto& t : th) t.join();
+    }
+};
+struct OrcBatch {
+    std::vector<RolloutGame> games;
+    int NP = 4, W = 34;
+    OrcPool* pool = nullptr;
+};
+void* orc_batch_new(int game_mode, uint32_t rule_bits, uint64_t base_seed, uint64_t game_offset, uint32_t n, const uint8_t* walls,
+                    const int32_t* oya, const int32_t* round_wind, const int32_t* scores, const int32_t* honba, const int32_t* kyotaku,
+                    int threads) {
+    OrcBatch* b = new OrcBatch;
+    b->games.resize(n);
+    b->pool = new OrcPool(std::max(threads, 1));
+    b->NP = game_mode >= 3 ? 3 : 4;
+    b->W = game_mode >= 3 ? 27 : 34;
+    b->pool->run(n, [&](uint32_t g) {
+        rollout_game_init(b->games[g], game_mode, rule_bits, base_seed, game_offset, g, walls, oya, round_wind, scores, honba, kyotaku);
+    });
+    return b;
+}
+void orc_batch_free(void* bp) {
+    OrcBatch* b = (OrcBatch*)bp;
+    delete b->pool;
+    for (auto& r : b->games) delete r.s;
+    delete b;
+}
+int orc_batch_step(void* bp, int policy, uint64_t policy_seed, uint32_t call_rate_256, uint32_t n_steps, int auto_reset) {
+    if (policy != 0 && policy != 1) return -1;
+    OrcBatch* b = (OrcBatch*)bp;
+    b->pool->run((uint32_t)b->games.size(),
+                 [&](uint32_t g) { rollout_game_steps(b->games[g], policy, policy_seed, call_rate_256, n_steps, auto_reset); });
+    return 0;
+}
+// the outputs of orc_rollout_policy for every game (any pointer may be NULL)
+void orc_batch_state(void* bp, uint8_t* status, RmjStateView* views, uint64_t* step_counts, int32_t* scores_out, rmj_action_t* legal,
+                     uint32_t* legal_cnt, uint8_t* masks, uint64_t* waits, uint64_t* digest) {
+    OrcBatch* b = (OrcBatch*)bp;
+    b->pool->run((uint32_t)b->games.size(), [&](uint32_t g) {
+        rollout_game_outputs(b->games[g], g, status, views, step_counts, scores_out, legal, legal_cnt, masks, waits, digest);
+    });
+}
+// encode_extended (extended != 0: out [m][215][W]) or encode (out [m][74][W]) of the rows (game, seat) = rows[2i], rows[2i + 1]
+int orc_batch_encode_rows(void* bp, const int32_t* rows, uint32_t m, int extended, float* out) {
+    OrcBatch* b = (OrcBatch*)bp;
+    for (uint32_t i = 0; i < m; i++)
+        if (rows[2 * i] < 0 || rows[2 * i] >= (int32_t)b->games.size() || rows[2 * i + 1] < 0 || rows[2 * i + 1] >= b->NP) return -1;
+    const size_t sz = (size_t)(extended ? 215 : 74) * b->W;
+    b->pool->run(m, [&](uint32_t i) {
+        GameState* s = b->games[rows[2 * i]].s;
+        if (extended) orc_game_encode_extended(s, rows[2 * i + 1], out + i * sz);
+        else orc_game_encode(s, rows[2 * i + 1], out + i * sz);
+    });
+    return 0;
+}
+// encode_kawa_overview [n][NP][7][W] and encode_yaku_possibility [n][NP][21][2] of every game (either may be NULL)
+void orc_batch_aux(void* bp, float* kawa, float* yaku) {
+    OrcBatch* b = (OrcBatch*)bp;
+    b->pool->run((uint32_t)b->games.size(), [&](uint32_t g) {
+        if (kawa) orc_game_encode_kawa_overview(b->games[g].s, kawa + (size_t)g * b->NP * 7 * b->W);
+        if (yaku) orc_game_encode_yaku_possibility(b->games[g].s, yaku + (size_t)g * b->NP * 21 * 2);
+    });
 }
 
 }  // extern "C"

@@ -183,6 +183,11 @@ __device__ __forceinline__ uint64_t mk_action(uint32_t type, uint32_t tile, uint
     return (uint64_t)type | ((uint64_t)tile << 8) | ((uint64_t)n << 16) | ((uint64_t)c0 << 24) | ((uint64_t)c1 << 32) |
            ((uint64_t)c2 << 40) | ((uint64_t)c3 << 48);
 }
+// Kakan of a pon's three tiles: consume sorted, as Action::new sorts it (a pon made by an MJAI event keeps [called, consumed...] order)
+__device__ __forceinline__ uint64_t mk_kakan(uint32_t tile, uint32_t a, uint32_t b, uint32_t c) {
+    const uint32_t lo = min(a, min(b, c)), hi = max(a, max(b, c));
+    return mk_action(RMJ_KAKAN, tile, 3, lo, a + b + c - lo - hi, hi);
+}
 __device__ __forceinline__ uint32_t a_type(uint64_t a) { return (uint32_t)(a & 0xFF); }
 __device__ __forceinline__ uint32_t a_tile(uint64_t a) { return (uint32_t)((a >> 8) & 0xFF); }
 __device__ __forceinline__ uint32_t a_n(uint64_t a) { return (uint32_t)((a >> 16) & 0xFF); }
@@ -396,15 +401,18 @@ __device__ inline MeldAgg build_meld_agg(const PState& P) {
             uint8_t ty = P.meld_type[i];
             int nt = (ty >= RMJ_MELD_DAIMINKAN) ? 4 : 3;
             uint64_t mm = 0;
+            int tmin = 99;
             for (int k = 0; k < nt; k++) {
                 int t = P.meld_tiles[i][k];
                 mm |= 1ull << (t >> 2);
                 m.aka += is_aka(t);
+                tmin = min(tmin, t >> 2);
             }
             m.mtypes[i] = mm;
             m.types |= mm;
             m.mtype[i] = ty;
-            int t0 = P.meld_tiles[i][0] >> 2;  // tiles sorted by id -> lowest type first (== chi sort)
+            // chi: the lowest type (hand_evaluator.rs:63-65) - a chi replayed from MJAI events keeps [called, consumed...] order
+            int t0 = ty == RMJ_MELD_CHI ? tmin : (P.meld_tiles[i][0] >> 2);
             m.t0[i] = (uint8_t)t0;
             bool opened = ty != RMJ_MELD_ANKAN;
             if (opened) m.menzen = false;

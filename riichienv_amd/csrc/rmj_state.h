@@ -35,7 +35,7 @@ struct alignas(16) PState {  // 128 bytes
     uint8_t meld_type[4];    // RMJ_MELD_*
     uint8_t meld_from[4];    // from_who, 0xFF = -1
     uint8_t meld_called[4];  // called_tile, 0xFF = None
-    uint8_t meld_tiles[4][4];// sorted 136-ids (3 for chi/pon, 4 for kans)
+    uint8_t meld_tiles[4][4];// 136-ids (3 for chi/pon, 4 for kans): sorted, except melds made by MJAI events ([called, consumed...])
     uint8_t n_discards;
     uint8_t flags;           // PF_*
     uint8_t pao37, pao50;    // liable seat for daisangen / daisuushi, 0xFF = none

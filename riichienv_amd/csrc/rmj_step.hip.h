@@ -803,7 +803,7 @@ __device__ __forceinline__ void gen_act_legal(Ctx& c, int pid) {
                         int pos = n + __popcll(kb & lanemask_lt(lane));
                         if (pos < RMJ_MAX_LEGAL)
                             c.X.legal[pid][pos] =
-                                mk_action(RMJ_KAKAN, ht, 3, P.meld_tiles[m][0], P.meld_tiles[m][1], P.meld_tiles[m][2]);
+                                mk_kakan(ht, P.meld_tiles[m][0], P.meld_tiles[m][1], P.meld_tiles[m][2]);
                     }
                     n += __popcll(kb);
                 }
@@ -1327,15 +1327,18 @@ __device__ inline void pao_check(Ctx& c, int claimer, int discarder, int tile) {
     }
 }
 
-__device__ inline void push_meld(PState& P, int type, uint32_t t0, uint32_t t1, uint32_t t2, uint32_t t3, int n, int from, int called) {
+// sorted = false keeps the tiles in the order given (the MJAI event path: [called, consumed...], event_handler.rs:157-289)
+__device__ inline void push_meld(PState& P, int type, uint32_t t0, uint32_t t1, uint32_t t2, uint32_t t3, int n, int from, int called,
+                                 bool sorted = true) {
     int m = P.n_melds;
     if (m >= 4) return;
     uint32_t v[4] = {t0, t1, t2, n == 4 ? t3 : 0xFFFFu};
+    if (sorted)
 #pragma unroll
-    for (int i = 0; i < 4; i++)
+        for (int i = 0; i < 4; i++)
 #pragma unroll
-        for (int j = 0; j < 3; j++)
-            if (v[j] > v[j + 1]) { uint32_t t = v[j]; v[j] = v[j + 1]; v[j + 1] = t; }
+            for (int j = 0; j < 3; j++)
+                if (v[j] > v[j + 1]) { uint32_t t = v[j]; v[j] = v[j + 1]; v[j + 1] = t; }
     for (int i = 0; i < 4; i++) P.meld_tiles[m][i] = (i < n) ? (uint8_t)v[i] : 0;
     P.meld_type[m] = (uint8_t)type;
     P.meld_from[m] = (uint8_t)from;
@@ -2033,7 +2036,8 @@ __device__ __forceinline__ void step_game(Ctx& c, const uint64_t mine, bool trus
 // binary records of one game (a start_kyoku is START_KYOKU + two TEHAI records, like the emitted log).  This is the
 // reference's replay state machine, NOT step(): no validation, no wall (a zero placeholder), melds keep from_who = -1,
 // discards carry no tsumogiri/riichi flags, is_first_turn is never cleared, scoring never happens.
-// Deviation: meld tiles are stored sorted (the reference keeps [called, consumed...] order on this path).
+// Meld tiles keep the reference's order on this path: [called, consumed...] for pon / chi / daiminkan, the consumed tiles for ankan,
+// the added tile last for kakan (the step path sorts them, as the reference's step does).
 __device__ inline void apply_remove_first(Ctx& c, PState& P, int tile) {
     int idx = hand_find(c, P, tile);
     if (idx >= 0) hand_remove_at(c, P, idx);
@@ -2199,7 +2203,7 @@ __device__ inline void apply_event(Ctx& c, const RmjEvent* ev) {
             apply_remove_first(c, P, c1);
             apply_remove_first(c, P, c2);
             waits_invalidate(P);
-            push_meld(P, ty == RMJ_EV_PON ? RMJ_MELD_PON : RMJ_MELD_CHI, (uint32_t)tile, (uint32_t)c1, (uint32_t)c2, 0, 3, 0xFF, tile);
+            push_meld(P, ty == RMJ_EV_PON ? RMJ_MELD_PON : RMJ_MELD_CHI, (uint32_t)tile, (uint32_t)c1, (uint32_t)c2, 0, 3, 0xFF, tile, false);
             S.drawn_tile = 0xFF;
             S.phase = RMJ_WAIT_ACT;
             S.active_mask = (uint8_t)(1u << actor);
@@ -2228,7 +2232,7 @@ __device__ inline void apply_event(Ctx& c, const RmjEvent* ev) {
             const int n = (ev[0].flags >> 4) & 15;
             for (int k = 0; k < n && k < 3; k++) apply_remove_first(c, P, ev[0].consumed[k]);
             waits_invalidate(P);
-            push_meld(P, RMJ_MELD_DAIMINKAN, (uint32_t)tile, ev[0].consumed[0], ev[0].consumed[1], ev[0].consumed[2], 4, 0xFF, tile);
+            push_meld(P, RMJ_MELD_DAIMINKAN, (uint32_t)tile, ev[0].consumed[0], ev[0].consumed[1], ev[0].consumed[2], 4, 0xFF, tile, false);
             S.phase = RMJ_WAIT_ACT;
             S.active_mask = (uint8_t)(1u << actor);
             S.needs_tsumo = 1;
@@ -2238,7 +2242,7 @@ __device__ inline void apply_event(Ctx& c, const RmjEvent* ev) {
             const int n = (ev[0].flags >> 4) & 15;
             for (int k = 0; k < n && k < 4; k++) apply_remove_first(c, P, ev[0].consumed[k]);
             waits_invalidate(P);
-            push_meld(P, RMJ_MELD_ANKAN, ev[0].consumed[0], ev[0].consumed[1], ev[0].consumed[2], ev[0].consumed[3], 4, 0xFF, 0xFF);
+            push_meld(P, RMJ_MELD_ANKAN, ev[0].consumed[0], ev[0].consumed[1], ev[0].consumed[2], ev[0].consumed[3], 4, 0xFF, 0xFF, false);
             S.current_player = (uint8_t)actor;
             S.phase = RMJ_WAIT_ACT;
             S.active_mask = (uint8_t)(1u << actor);
@@ -2251,11 +2255,7 @@ __device__ inline void apply_event(Ctx& c, const RmjEvent* ev) {
             for (int m = 0; m < P.n_melds; m++)
                 if (P.meld_type[m] == RMJ_MELD_PON && (P.meld_tiles[m][0] >> 2) == (tile >> 2)) {
                     P.meld_type[m] = RMJ_MELD_KAKAN;
-                    uint32_t v[4] = {P.meld_tiles[m][0], P.meld_tiles[m][1], P.meld_tiles[m][2], (uint32_t)tile};
-                    for (int a = 0; a < 4; a++)
-                        for (int b = 0; b < 3; b++)
-                            if (v[b] > v[b + 1]) { uint32_t t = v[b]; v[b] = v[b + 1]; v[b + 1] = t; }
-                    for (int a = 0; a < 4; a++) P.meld_tiles[m][a] = (uint8_t)v[a];
+                    P.meld_tiles[m][3] = (uint8_t)tile;   // appended (event_handler.rs:290-305)
                     break;
                 }
             S.current_player = (uint8_t)actor;

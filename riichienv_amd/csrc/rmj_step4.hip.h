@@ -704,7 +704,9 @@ __device__ __forceinline__ E4Out r4_seat_eval(uint32_t on, uint32_t seat, uint32
                 }
             }
         }
-        mp = e4_meld_lane(mv, type, nt, t0, t1, t2, t3, (int)(t0 >> 2), type != RMJ_MELD_CHI, type != RMJ_MELD_ANKAN);
+        // (a chi made by an MJAI event keeps [called, consumed...] order: its lowest tile is not always first)
+        mp = e4_meld_lane(mv, type, nt, t0, t1, t2, t3, (int)((type == RMJ_MELD_CHI ? min(t0, min(t1, t2)) : t0) >> 2), type != RMJ_MELD_CHI,
+                          type != RMJ_MELD_ANKAN);
     }
     const E4Meld ma = e4_meld_reduce(mp, rb);
     aka += e4m_aka(ma);
@@ -1172,7 +1174,7 @@ __device__ __forceinline__ void r4_gen_act_legal(R4& q, int& nl_mine) {
                     const uint32_t kb = rballot(hit, rb);
                     if (hit)
                         r4_put(q, pid, n + __popc(kb & ((1u << r) - 1u)),
-                               mk_action(RMJ_KAKAN, ht, 3, P->meld_tiles[m][0], P->meld_tiles[m][1], P->meld_tiles[m][2]),
+                               mk_kakan(ht, P->meld_tiles[m][0], P->meld_tiles[m][1], P->meld_tiles[m][2]),
                                (KSANMA ? 29 : 42) + r4_tile_id(target));
                     n += __popc(kb);
                 }

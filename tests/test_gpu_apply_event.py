@@ -1,7 +1,10 @@
 """Row N1 on the GPU: rmj_apply_events against the oracle's apply_mjai_event.  Event streams = the reference-test flows
-and whole MJAI logs of finished random rollouts (each game is fed its own log, one event per launch)."""
-from riichienv_amd.shard import game_seed
+and whole MJAI logs of finished random rollouts (each game is fed its own log, one event per launch); the two golden hanchan logs
+and rollout logs replayed with the log walker's bookkeeping (replay=True), every encoder compared after every event."""
 import json
+import os
+
+from riichienv_amd.shard import game_seed
 
 import numpy as np
 import pytest
@@ -14,10 +17,7 @@ pytestmark = pytest.mark.gpu
 
 
 def _norm(v):
-    d = normalize_view(v)
-    for p in d["players"]:
-        for m in p["melds"]:
-            m["tiles"] = sorted(m["tiles"])     # the device stores meld tiles sorted (documented deviation of this path)
+    d = normalize_view(v)       # (meld tiles as stored: [called, consumed...] on this path, as in the reference)
     d.pop("wall_seed", None)
     d.pop("hand_index", None)
     return d
@@ -150,3 +150,112 @@ def test_start_kyoku_after_a_depleted_round(mode, npl):
     sk2 = start_kyoku([tehai] + [["1z"] * 13 for _ in range(npl - 1)], oya=0, scores=score)
     sk2["kyoku"], sk2["dora_marker"] = 2, "9s"
     _run_streams(mode, [[sk1, {"type": "tsumo", "actor": 1, "pai": "5p"}], [sk2, {"type": "tsumo", "actor": 0, "pai": "E"}]], prepare=deplete)
+
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def _rollout_logs(mode, n, seed, steps, greedy):
+    from oracle import oracle
+
+    logs = []
+    for g in range(n):
+        o = oracle.Game(game_mode=mode, seed=seed + g)
+        o.reset()
+        for _ in range(steps):
+            if o.status()[2]:
+                break
+            o.step([int(x) for x in (o.greedy_actions(seed, g, 96) if greedy else o.random_actions(seed, g))])
+        logs.append([json.loads(x) for x in o.log()])
+    return logs
+
+
+def _replay_and_encode(mode, streams):
+    """every stream fed to the device (apply_events, replay=True: what ReplayBatch feeds) and to the oracle (apply_event, replay=True),
+    one event per launch; after every event the state view, the legal lists, and encode_extended / encode of every acting seat and
+    the aux blocks of every game are compared.  Returns the number of (event, seat) rows compared and of rows holding a chi whose
+    tiles are not in ascending order."""
+    from oracle import oracle
+    from riichienv_amd import vecenv
+    from tests.test_gpu_encode_extended import _first_difference
+
+    n = len(streams)
+    sanma = mode >= 3
+    env = vecenv.VecRiichiEnv(n, game_mode=mode, seed=1, skip_mjai_logging=True)
+    games = [oracle.Game(game_mode=mode, seed=game_seed(1, g)) for g in range(n)]
+    env.reset()
+    for o in games:
+        o.reset()
+    rows = unsorted_chi = 0
+    for k in range(max(len(s) for s in streams)):
+        evs = [s[k] if k < len(s) else None for s in streams]
+        env.apply_events(evs, replay=True)
+        for o, ev in zip(games, evs):
+            if ev is not None:
+                o.apply_event(ev, replay=True)
+        _compare(env, games, k)
+        act, ph, dn = env.status()
+        ext, enc = env.encode_extended(), env.encode()
+        kawa, yaku = env.encode_kawa_overview(), env.encode_yaku_possibility()
+        for g, o in enumerate(games):
+            if evs[g] is None:
+                continue
+            assert kawa[g].tobytes() == o.encode_kawa_overview().tobytes(), (k, g, "kawa_overview")
+            assert yaku[g].tobytes() == o.encode_yaku_possibility().tobytes(), (k, g, "yaku_possibility")
+            if dn[g]:
+                continue
+            v = o.peek()
+            chi = any(list(m.tiles[: m.n_tiles]) != sorted(m.tiles[: m.n_tiles]) for p in v.players for m in p.melds[: p.n_melds]
+                      if m.meld_type == abi.MELD_CHI)
+            for s in range(4):
+                if not (act[g] >> s) & 1:
+                    continue
+                want = o.encode_extended(s)[None]
+                if ext[g, s].tobytes() != want[0].tobytes():
+                    raise AssertionError(_first_difference(ext[g, s][None], want, [g], [s], f"event {k} ({evs[g]['type']})"))
+                assert enc[g, s].tobytes() == o.encode(s, sanma).tobytes(), (k, g, s, "encode")
+                rows += 1
+                unsorted_chi += chi
+    env.close()
+    return rows, unsorted_chi
+
+
+def test_golden_logs_encode_extended_after_every_event():
+    """The two real hanchan logs: 6 of the 9 chi of 126_204_0 hold their called tile above a consumed one, and the fuuro overview
+    (channels 98..177) writes meld tiles by slot - the device must keep the reference's [called, consumed...] order."""
+    from riichienv_amd.replay import load_mjai_jsonl
+
+    streams = [load_mjai_jsonl(os.path.join(GOLDEN, f)) for f in ("126_204_0_mjai.jsonl", "ui_example_after_injection.jsonl")]
+    rows, unsorted_chi = _replay_and_encode(2, streams)
+    assert rows > 1200 and unsorted_chi > 50, (rows, unsorted_chi)
+
+
+@pytest.mark.parametrize("mode", [2, 5])
+def test_rollout_logs_encode_extended_after_every_event(mode):
+    streams = _rollout_logs(mode, 4, 1300 + mode, 500, greedy=False) + _rollout_logs(mode, 4, 1400 + mode, 600, greedy=True)
+    rows, unsorted_chi = _replay_and_encode(mode, streams)
+    assert rows > 2000, rows
+    if mode < 3:
+        assert unsorted_chi > 0
+
+
+def test_replay_batch_extended_samples_equal_oracle():
+    """ReplayBatch(extended=True) over the golden log: every sample's features are the oracle's encode_extended of that seat in the
+    state before the event that holds the decision"""
+    from oracle import oracle
+    from riichienv_amd import replay
+
+    events = replay.load_mjai_jsonl(os.path.join(GOLDEN, "126_204_0_mjai.jsonl"))
+    rb = replay.ReplayBatch([events], game_mode=2, include_pass=True, extended=True)
+    o = oracle.Game(game_mode=2, seed=game_seed(0, 0))
+    o.reset()
+    done, n = 0, 0
+    for smp in rb.samples():
+        while done < smp["index"]:
+            o.apply_event(events[done], replay=True)
+            done += 1
+        for j, s in enumerate(smp["seat"]):
+            want = o.encode_extended(int(s))
+            assert smp["obs"][j].tobytes() == want.tobytes(), (smp["index"], int(s), np.argwhere(smp["obs"][j] != want)[:4].tolist())
+            n += 1
+    assert n > 500, n
