@@ -415,6 +415,48 @@ int rmj_step_random_encode_compact(rmj_handle h, uint64_t policy_seed, uint32_t 
 int rmj_encode_extended(rmj_handle h, int only_active, float* out);
 int rmj_encode_extended_device(rmj_handle h, int only_active, float* d_out); /* device pointer, asynchronous on the handle's stream */
 
+/* Observation batches for a trainer: the ACTING seats' tensors of one feature set, written as the policy consumes them.
+ *   RMJ_FEATURES_BASE             Observation.encode() (observation/python.rs:457-806): 74 x W.
+ *   RMJ_FEATURES_DISCARD_SHANTEN  riichienv-ml feat_v2.DiscardHistoryShantenEncoder (configs/4p/ppo_v2.yml, in_channels 94): encode()
+ *                                 (rows 0..73), then encode_discard_history_decay() (74..77, decay rate 0.2) and encode_shanten_efficiency()
+ *                                 broadcast over the columns (78..93) - rows 74..93 of encode_extended().  94 x 34, 4P only: the
+ *                                 reference's 3P observation has 3 decay rows and a (3, 4) efficiency block that feat_v2 cannot reshape.
+ *   RMJ_FEATURES_EXTENDED         Observation.encode_extended() (riichienv-ml feat_v3.ExtendedEncoder): 215 x W, the rows of
+ *                                 rmj_encode_extended_device.
+ * compact = 0: out[n][4][row_stride], the rows of the acting seats (the others untouched, like only_active = 2).
+ * compact = 1: out[capacity][row_stride] holding the acting seats one after the other in (game, seat) order, index[slot] = game * 4 + seat,
+ *              *count (device u32) = the number of acting seats of this state; when it exceeds `capacity` only the first `capacity`
+ *              rows (and index entries) were written - what rmj_encode_compact_device does for encode().
+ * row_stride: floats from one row to the next, even and >= C x W; 0 = C x W (dense rows; 215 x 27 is odd: such rows may start 4-byte
+ * aligned).  The pad floats are never written.  All pointers are device pointers. */
+#define RMJ_FEATURES_BASE 0            /* Observation.encode(): 74 x W */
+#define RMJ_FEATURES_DISCARD_SHANTEN 1 /* riichienv-ml feat_v2: encode() + decay (4) + shanten efficiency (16, broadcast); 94 x 34, 4P only */
+#define RMJ_FEATURES_EXTENDED 2        /* Observation.encode_extended(): 215 x W */
+#define RMJ_FEATURES_DISCARD_SHANTEN_CHANNELS 94
+typedef struct RmjObsBatch {
+    int32_t features;     /* RMJ_FEATURES_* */
+    int32_t compact;      /* 0: out[n][4][row_stride], acting rows only; 1: out[capacity][row_stride] + index + count */
+    uint32_t row_stride;  /* floats; 0 = C x W */
+    uint32_t capacity;    /* compact only */
+    float* d_out;
+    int32_t* d_index;     /* compact only: [capacity] game * 4 + seat */
+    uint32_t* d_count;    /* compact only: device u32 */
+} RmjObsBatch;
+/* The batch of the current state, asynchronous on the handle's stream.  RMJ_ERR_ARG for DISCARD_SHANTEN on a 3P handle, an unknown
+ * feature set, a bad row stride or a missing pointer (d_index / d_count are needed with compact = 1 only). */
+int rmj_encode_batch_device(rmj_handle h, const RmjObsBatch* b);
+/* The same with host pointers (d_out / d_index / d_count of `b` point to host memory): staged on the device, returns when the rows are
+ * there.  Dense: rows of seats that do not act keep what `d_out` held. */
+int rmj_encode_batch(rmj_handle h, const RmjObsBatch* b);
+/* rmj_step_ids_device(h, d_action_ids, auto_reset) + rmj_encode_batch_device(h, b): the trainer loop's iteration (riichienv-ml
+ * trainers/_ppo_worker.py:151-239: step, then the encoder of the returned observations) for every feature set.  The same state and rows
+ * as the two calls; separate launches on the handle's stream, no host synchronisation between them. */
+int rmj_step_ids_encode_batch_device(rmj_handle h, const int32_t* d_action_ids, int auto_reset, const RmjObsBatch* b);
+/* rmj_sample_ids_device(h, d_logits, stride, seed, d_ids) + rmj_step_ids_device(h, d_ids, auto_reset) + rmj_encode_batch_device(h, b):
+ * the whole environment side of a trainer iteration between two policy forward passes.  d_ids [n][4] receives the drawn ids. */
+int rmj_step_sample_encode_batch_device(rmj_handle h, const float* d_logits, uint32_t stride, uint64_t seed, int auto_reset,
+                                        int32_t* d_ids, const RmjObsBatch* b);
+
 /* shanten.rs:244-261 calculate_shanten / :470-484 calculate_shanten_3p over raw 34-histograms
  * (len_div3 = tile count / 3; -1 = complete hand).  Tables are generated at first use, on the host. */
 int rmj_shanten(int device, const uint8_t* counts /*[n][34]*/, uint32_t n, int sanma, int8_t* out /*[n]*/);

@@ -225,6 +225,18 @@ class SeqBuffers(C.Structure):
 
 SEQ_SPARSE, SEQ_PROG, SEQ_CAND, SEQ_DELTA_PROG = 25, 256, 64, 64
 
+# feature sets of the observation batches (RMJ_FEATURES_*, rmj_encode_batch_device)
+FEATURES_BASE = 0              # Observation.encode(): 74 x W
+FEATURES_DISCARD_SHANTEN = 1   # riichienv-ml feat_v2: encode() + decay (4) + shanten efficiency (16, broadcast); 94 x 34, 4P only
+FEATURES_EXTENDED = 2          # Observation.encode_extended(): 215 x W
+FEATURES = {"base": FEATURES_BASE, "discard_shanten": FEATURES_DISCARD_SHANTEN, "extended": FEATURES_EXTENDED}
+FEATURE_CHANNELS = {FEATURES_BASE: 74, FEATURES_DISCARD_SHANTEN: 94, FEATURES_EXTENDED: 215}
+
+
+class ObsBatch(C.Structure):   # RmjObsBatch
+    _fields_ = [("features", C.c_int32), ("compact", C.c_int32), ("row_stride", C.c_uint32), ("capacity", C.c_uint32),
+                ("out", C.c_void_p), ("index", C.c_void_p), ("count", C.c_void_p)]
+
 
 class BenchResult(C.Structure):
     _fields_ = [("total_ms", C.c_double), ("step_kernel_ms", C.c_double), ("env_steps", C.c_uint64),

@@ -790,6 +790,76 @@ __global__ __launch_bounds__(64) RMJ_ENCX_OCC void k_encode_ext(Env E, int only_
         enc_emit_bytes<W, ENC_EXT_C_SLOTS>(d, cells, lut, lane, head);
     }
 }
+// Observation batches (rmj_encode_batch_device): the acting seats' rows of one feature set, FEAT = RMJ_FEATURES_*:
+//   BASE             encode()                                   74 x W  (channels 0..73, ext_base = false)
+//   DISCARD_SHANTEN  encode() + encode_extended()'s 74..93      94 x W  (riichienv-ml feat_v2; 4P only)
+//   EXTENDED         encode_extended()                          215 x W (k_encode_ext's rows, byte for byte)
+// in one of two layouts: dense out[n][4][RS] (rows of seats that do not act untouched) or, COMPACT, out[capacity][RS] in (game, seat)
+// order with index[slot] = game * 4 + seat and *count = the number of acting seats.  k_encode_ext's grid of one wave per (game, seat)
+// and its occupancy cap: the extended rows wait on the ukeire walk, and a wave per seat keeps the two or three claimants of a discard
+// in parallel.  A seat that does not act leaves on the 4-byte status word.  The compact slot is k_obs_offsets' offset of the game,
+// plus the totals of the scan blocks before it, plus the acting seats of the game below this one.
+template <bool SANMA, int FEAT, bool COMPACT>
+__global__ __launch_bounds__(64) RMJ_ENCX_OCC void k_encode_batch(Env E, const float* __restrict__ decay, float* __restrict__ out, uint32_t RS,
+                                                                  const uint32_t* __restrict__ offs, const uint32_t* __restrict__ totals,
+                                                                  int32_t* __restrict__ index, uint32_t capacity, uint32_t* __restrict__ count) {
+    constexpr int W = SANMA ? ENC_W3 : ENC_W4, NPP = SANMA ? 3 : 4;
+    constexpr bool EXT = FEAT == RMJ_FEATURES_EXTENDED;
+    constexpr int SLOTS = EXT ? ENC_EXT_C_SLOTS : ENC_CH;
+    __shared__ GState st;
+    __shared__ __attribute__((aligned(16))) uint8_t raw[(SLOTS * W + 4 + 15) / 16 * 16];
+    __shared__ float lut[ENC_LUT];
+    __shared__ float tab[ENC_EXT_B_SLOTS];
+    __shared__ float col4[4 * W];
+    __shared__ uint32_t hist[ENC_HIST_WORDS];
+    const int lane = threadIdx.x & 63;
+    const uint32_t g = blockIdx.x >> 2;
+    const int seat = blockIdx.x & 3;
+    if (COMPACT && blockIdx.x == 0) {   // the size of the batch: all block totals
+        const uint32_t all = obs_block_prefix(totals, (E.n_games + OBS_SCAN_BLOCK - 1) / OBS_SCAN_BLOCK, lane);
+        if (lane == 0) *count = all;
+    }
+    const uint32_t stw = E.status[g];
+    const uint32_t am = ((stw >> 16) & 0xFFu) ? 0u : (stw & 0xFu);   // the seats k_obs_offsets counts
+    if (seat >= NPP || !((am >> seat) & 1u)) return;
+    float* dst;
+    if (COMPACT) {
+        const uint32_t slot = offs[g] + obs_block_prefix(totals, g / OBS_SCAN_BLOCK, lane) + (uint32_t)__popc(am & ((1u << seat) - 1u));
+        if (slot >= capacity) return;                  // (the count tells the caller that the buffer was too small)
+        if (lane == 0) index[slot] = (int32_t)(g * 4u + (uint32_t)seat);
+        dst = out + (size_t)slot * RS;
+    } else {
+        dst = out + ((size_t)g * 4 + seat) * RS;
+    }
+    if (lane < (int)(sizeof(GState) / 16)) reinterpret_cast<uint4*>(&st)[lane] = reinterpret_cast<const uint4*>(E.core + g)[lane];
+    enc_lut_init(lut, lane);
+    wave_sync();
+    const GState& S = st;
+    auto head_of = [](const float* p) { return (int)(((16u - (uint32_t)(reinterpret_cast<uintptr_t>(p) & 15u)) & 15u) >> 2); };
+    {   // channels 0..73: encode() (channel 30 counts every meld tile) or encode_extended()'s base block
+        const int head = head_of(dst);
+        EncByteSink<W> o{raw + ((4 - head) & 3), lut, lane, -1.0f};
+        encode_seat_to<SANMA>(S, seat, lane, hist, o, true, EXT);
+        enc_emit_bytes<W>(dst, o.cells, lut, lane, head, o.big);
+        wave_sync();
+    }
+    if constexpr (FEAT != RMJ_FEATURES_BASE) {   // channels 74..93 (and 178..214 for EXTENDED)
+        const int n_legal = EXT && ((S.active_mask >> seat) & 1u) && !S.is_done ? (int)E.nlegal[(size_t)g * 4 + seat] : 0;
+        encode_ext_scalars<SANMA, EXT>(S, seat, tab, col4, lane, E.sh, decay, E.legal + ((size_t)g * 4 + seat) * RMJ_MAX_LEGAL, n_legal);
+        enc_emit_fn(dst + 74 * W, 20 * W, lane, [&](int e) { return e < 4 * W ? col4[e] : tab[e / W]; });
+        if (EXT) enc_emit_fn(dst + 178 * W, 37 * W, lane, [&](int e) { return tab[20 + e / W]; });
+        wave_sync();
+    }
+    if constexpr (EXT) {   // channels 94..177
+        float* d = dst + 94 * W;
+        const int head = head_of(d);
+        uint8_t* cells = raw + ((4 - head) & 3);
+        for (int i = lane; i < (int)sizeof(raw) / 16; i += 64) reinterpret_cast<uint4*>(raw)[i] = make_uint4(0u, 0u, 0u, 0u);
+        wave_sync();
+        encode_ext_melds<SANMA>(S, seat, cells, lane);
+        enc_emit_bytes<W, ENC_EXT_C_SLOTS>(d, cells, lut, lane, head);
+    }
+}
 
 // ---- auxiliary encoders (row N3): kawa overview, yaku possibility, furiten-ron possibility ----------------------
 // One wave per game; absolute seat order, public information only (the same for every observing seat).
@@ -2947,6 +3017,123 @@ int rmj_encode_extended(rmj_handle h, int only_active, float* out) {
     if ((rc = rmj_encode_extended_device(h, only_active, d))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpy(out, d, bytes, hipMemcpyDeviceToHost));
+    return RMJ_OK;
+}
+
+// ---- observation batches (k_encode_batch) ------------------------------------------------------------------
+// channels x width of a feature set on this handle and the row stride in floats; an error message for what is refused
+static int batch_shape(const rmj_env* h, const RmjObsBatch* b, uint32_t* ch, uint32_t* w, uint32_t* rs) {
+    if (!b) return fail(RMJ_ERR_ARG, "null argument");
+    const bool sanma = h->cfg.game_mode >= 3;
+    *w = sanma ? ENC_W3 : ENC_W4;
+    switch (b->features) {
+        case RMJ_FEATURES_BASE: *ch = ENC_CH; break;
+        case RMJ_FEATURES_EXTENDED: *ch = ENC_EXT_CH; break;
+        case RMJ_FEATURES_DISCARD_SHANTEN:
+            if (sanma) return fail(RMJ_ERR_ARG, "RMJ_FEATURES_DISCARD_SHANTEN is 4-player only (feat_v2 cannot reshape the 3P observation's 3 decay rows and (3, 4) efficiency block)");
+            *ch = RMJ_FEATURES_DISCARD_SHANTEN_CHANNELS;
+            break;
+        default: return fail(RMJ_ERR_ARG, "unknown feature set (RMJ_FEATURES_BASE, _DISCARD_SHANTEN or _EXTENDED)");
+    }
+    if (b->compact != 0 && b->compact != 1) return fail(RMJ_ERR_ARG, "compact must be 0 (dense) or 1");
+    const uint32_t dense = *ch * *w;
+    *rs = b->row_stride ? b->row_stride : dense;
+    if (b->row_stride && (b->row_stride < dense || (b->row_stride & 1u)))
+        return fail(RMJ_ERR_ARG, "row stride must be 0 or an even number of floats >= C x W (" + std::to_string(dense) + ")");
+    if (!b->d_out || (b->compact && (!b->d_index || !b->d_count))) return fail(RMJ_ERR_ARG, "null argument");
+    return RMJ_OK;
+}
+// (arguments checked by batch_shape)
+static void launch_encode_batch(rmj_env* h, const RmjObsBatch* b, uint32_t rs) {
+    const uint32_t n = h->cfg.n_games;
+    const dim3 grid(n * 4), block(64);
+    const bool sanma = h->cfg.game_mode >= 3;
+    const float* decay = h->d_decay;
+    uint32_t* totals = h->d_obs_offs + n;
+    if (b->compact)
+        hipLaunchKernelGGL(k_obs_offsets, dim3((n + OBS_SCAN_BLOCK - 1) / OBS_SCAN_BLOCK), dim3(OBS_SCAN_BLOCK), 0, h->stream, (const uint32_t*)h->d.status, n,
+                           h->d_obs_offs, totals);
+#define RMJ_LAUNCH_BATCH(SM, F)                                                                                                          \
+    do {                                                                                                                                  \
+        if (b->compact)                                                                                                                   \
+            hipLaunchKernelGGL((k_encode_batch<SM, F, true>), grid, block, 0, h->stream, h->d, decay, b->d_out, rs, (const uint32_t*)h->d_obs_offs, \
+                               (const uint32_t*)totals, b->d_index, b->capacity, b->d_count);                                            \
+        else                                                                                                                              \
+            hipLaunchKernelGGL((k_encode_batch<SM, F, false>), grid, block, 0, h->stream, h->d, decay, b->d_out, rs, (const uint32_t*)nullptr, \
+                               (const uint32_t*)nullptr, (int32_t*)nullptr, 0u, (uint32_t*)nullptr);                                     \
+    } while (0)
+    if (sanma && b->features == RMJ_FEATURES_EXTENDED) RMJ_LAUNCH_BATCH(true, RMJ_FEATURES_EXTENDED);
+    else if (sanma) RMJ_LAUNCH_BATCH(true, RMJ_FEATURES_BASE);
+    else if (b->features == RMJ_FEATURES_EXTENDED) RMJ_LAUNCH_BATCH(false, RMJ_FEATURES_EXTENDED);
+    else if (b->features == RMJ_FEATURES_DISCARD_SHANTEN) RMJ_LAUNCH_BATCH(false, RMJ_FEATURES_DISCARD_SHANTEN);
+    else RMJ_LAUNCH_BATCH(false, RMJ_FEATURES_BASE);
+#undef RMJ_LAUNCH_BATCH
+}
+int rmj_encode_batch_device(rmj_handle h, const RmjObsBatch* b) {
+    if (!h) return fail(RMJ_ERR_ARG, "null handle");
+    uint32_t ch, w, rs;
+    int rc = batch_shape(h, b, &ch, &w, &rs);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    launch_encode_batch(h, b, rs);
+    HIPCHK(hipGetLastError());
+    return RMJ_OK;
+}
+int rmj_encode_batch(rmj_handle h, const RmjObsBatch* b) {
+    if (!h) return fail(RMJ_ERR_ARG, "null handle");
+    uint32_t ch, w, rs;
+    int rc = batch_shape(h, b, &ch, &w, &rs);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const size_t rows = b->compact ? (size_t)b->capacity : (size_t)h->cfg.n_games * 4;
+    const size_t out_bytes = rows * rs * sizeof(float), out_al = (out_bytes + 255) & ~(size_t)255;
+    const size_t idx_bytes = b->compact ? (size_t)b->capacity * sizeof(int32_t) : 0, idx_al = (idx_bytes + 255) & ~(size_t)255;
+    void* sp;
+    if ((rc = scratch_for(h, out_al + idx_al + sizeof(uint32_t), &sp))) return rc;
+    char* base = (char*)sp;
+    RmjObsBatch d = *b;
+    d.d_out = (float*)base;
+    d.d_index = b->compact ? (int32_t*)(base + out_al) : nullptr;
+    d.d_count = b->compact ? (uint32_t*)(base + out_al + idx_al) : nullptr;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (!b->compact && out_bytes) HIPCHK(hipMemcpy(d.d_out, b->d_out, out_bytes, hipMemcpyHostToDevice));   // the rows that stay untouched
+    launch_encode_batch(h, &d, rs);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (b->compact) {
+        uint32_t k = 0;
+        HIPCHK(hipMemcpy(&k, d.d_count, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        const size_t m = k < b->capacity ? k : b->capacity;
+        if (m) {
+            HIPCHK(hipMemcpy(b->d_out, d.d_out, m * rs * sizeof(float), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(b->d_index, d.d_index, m * sizeof(int32_t), hipMemcpyDeviceToHost));
+        }
+        *b->d_count = k;
+    } else if (out_bytes) {
+        HIPCHK(hipMemcpy(b->d_out, d.d_out, out_bytes, hipMemcpyDeviceToHost));
+    }
+    return RMJ_OK;
+}
+int rmj_step_ids_encode_batch_device(rmj_handle h, const int32_t* d_action_ids, int auto_reset, const RmjObsBatch* b) {
+    if (!h || !d_action_ids) return fail(RMJ_ERR_ARG, "null argument");
+    uint32_t ch, w, rs;
+    int rc = batch_shape(h, b, &ch, &w, &rs);   // refused before anything is stepped
+    if (rc) return rc;
+    if ((rc = rmj_step_ids_device(h, d_action_ids, auto_reset))) return rc;
+    launch_encode_batch(h, b, rs);
+    HIPCHK(hipGetLastError());
+    return RMJ_OK;
+}
+int rmj_step_sample_encode_batch_device(rmj_handle h, const float* d_logits, uint32_t stride, uint64_t seed, int auto_reset,
+                                        int32_t* d_ids, const RmjObsBatch* b) {
+    if (!h || !d_ids) return fail(RMJ_ERR_ARG, "null argument");
+    uint32_t ch, w, rs;
+    int rc = batch_shape(h, b, &ch, &w, &rs);
+    if (rc) return rc;
+    if ((rc = rmj_sample_ids_device(h, d_logits, stride, seed, d_ids))) return rc;
+    if ((rc = rmj_step_ids_device(h, d_ids, auto_reset))) return rc;
+    launch_encode_batch(h, b, rs);
+    HIPCHK(hipGetLastError());
     return RMJ_OK;
 }
 

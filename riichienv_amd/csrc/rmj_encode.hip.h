@@ -409,7 +409,8 @@ __device__ inline void encode_seat(const GState& S, int pid, float* buf, int lan
 #define ENC_EXT_B_SLOTS 57
 #define ENC_EXT_C_SLOTS 84
 __device__ __forceinline__ int enc_ext_b_slot(int ch) { return ch < 94 ? ch - 74 : ch - 178 + 20; }
-template <bool SANMA>
+// ALL = false: channels 74..93 only (decay and shanten efficiency: riichienv-ml feat_v2's extra rows), slots 20..56 stay zero
+template <bool SANMA, bool ALL = true>
 __device__ inline void encode_ext_scalars(const GState& S, int pid, float* tab, float* col4, int lane, const ShantenTables& T, const float* decay,
                                           const uint64_t* legal, int n_legal) {
     constexpr int ENC_W = SANMA ? ENC_W3 : ENC_W4;
@@ -481,6 +482,7 @@ __device__ inline void encode_ext_scalars(const GState& S, int pid, float* tab, 
         }
     }
     wave_sync();
+    if (!ALL) return;
     // 178..188 action availability over the seat's legal list
     {
         uint32_t kind = 0xFFu;

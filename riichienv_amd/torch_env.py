@@ -35,11 +35,24 @@ class TorchVecEnv:
     obs(), mask, status … describe the state AFTER the last step; step(action_ids) takes an int32 tensor [n, 4] on the
     same device (-1 for seats that do not act)."""
 
-    def __init__(self, n_games, game_mode=2, seed=0, device=0, extended=False, skip_mjai_logging=True, share_stream=True, pad_rows=True, **kw):
+    def __init__(self, n_games, game_mode=2, seed=0, device=0, extended=False, skip_mjai_logging=True, share_stream=True, pad_rows=True,
+                 features=None, **kw):
         """share_stream: issue the library's kernels on torch's current stream of `device` (rmj_set_stream): policy and
         environment are then ordered by the stream, without host synchronisation between them.  With False the library keeps
-        its own stream and every call synchronises."""
+        its own stream and every call synchronises.
+        features: the observation every obs / step_obs / compact call returns - "base" (Observation.encode(), 74 x W),
+        "discard_shanten" (riichienv-ml feat_v2: encode() + discard decay + shanten efficiency, 94 x 34, 4P only) or "extended"
+        (Observation.encode_extended(), 215 x W); extended=True is a synonym for features="extended"."""
         import torch
+
+        if features is None:
+            features = "extended" if extended else "base"
+        if features not in abi.FEATURES:
+            raise ValueError(f"unknown feature set {features!r} (one of {', '.join(abi.FEATURES)})")
+        if extended and features != "extended":
+            raise ValueError(f"extended=True conflicts with features={features!r}")
+        if features == "discard_shanten" and vecenv._mode_id(game_mode) >= 3:
+            raise ValueError("the discard_shanten feature set (riichienv-ml feat_v2) is 4-player only")
 
         self.torch = torch
         self.device = torch.device("cuda", device)
@@ -52,8 +65,10 @@ class TorchVecEnv:
         L.rmj_sync.argtypes = [C.c_void_p]
         self.n = int(n_games)
         self.sanma = self.env.game_mode >= 3
-        self.extended = bool(extended)
-        self.channels = 215 if extended else 74
+        self.features = features
+        self._feat = abi.FEATURES[features]
+        self.extended = features == "extended"
+        self.channels = abi.FEATURE_CHANNELS[self._feat]
         self.width = 27 if self.sanma else 34
         v = DeviceViews()
         vecenv._chk(L.rmj_device_views(self.env.h, C.byref(v)))
@@ -66,7 +81,7 @@ class TorchVecEnv:
         # pad_rows (the default since round 5): every (game, seat) row of the 74-channel tensor padded to a multiple of 256 B
         # (rmj_set_encode_row_stride): the acting seats' rows are written 1.3-1.4 x faster (trainer loop 260 -> 274 M env.step/s); obs() then
         # returns a strided view [n, 4, 74, W] of the padded buffer (same values, same indexing; .contiguous() copies).  pad_rows=False: dense
-        self.pad_rows = bool(pad_rows) and not extended
+        self.pad_rows = bool(pad_rows) and features == "base"
         if self.pad_rows:
             self.row_stride = self.env.padded_row_stride()
             self.env.set_encode_row_stride(self.row_stride)
@@ -76,6 +91,8 @@ class TorchVecEnv:
             self.row_stride = self.channels * self.width
             self._obs_buf = torch.zeros((self.n, 4, self.channels, self.width), dtype=torch.float32, device=self.device)
             self._obs = self._obs_buf
+        # row stride of the batch entries (rmj_encode_batch_device): the padded rows of the base set, else C x W (0: 215 x 27 is odd)
+        self._batch_stride = self.row_stride if self.pad_rows else 0
         self._scores = torch.zeros((self.n, 4), dtype=torch.int32, device=self.device)
         self.shared = bool(share_stream)
         if self.shared:
@@ -97,40 +114,63 @@ class TorchVecEnv:
         return self._status()[2]
 
     def obs(self, only_active=True):
-        """encode() / encode_extended() into a resident tensor [n, 4, C, W].  only_active=True refreshes only the rows
-        of the seats that must act (rows of the other seats keep their previous contents: mask them with active())."""
+        """encode() / the feature set's encoder into a resident tensor [n, 4, C, W].  only_active=True refreshes only the rows
+        of the seats that must act (rows of the other seats keep their previous contents: mask them with active()).  The
+        discard_shanten set encodes acting seats only (rmj_encode_batch_device, dense)."""
         L = self.env.L
-        fn = L.rmj_encode_extended_device if self.extended else L.rmj_encode_device
-        vecenv._chk(fn(self.env.h, 2 if only_active else 0, C.c_void_p(self._obs_buf.data_ptr())))
+        if self.features == "discard_shanten":
+            if not only_active:
+                raise ValueError("the discard_shanten feature set encodes the acting seats only: obs(only_active=True)")
+            self.env.encode_batch_device(self._feat, self._obs_buf.data_ptr(), row_stride=self._batch_stride)
+        else:
+            fn = L.rmj_encode_extended_device if self.extended else L.rmj_encode_device
+            vecenv._chk(fn(self.env.h, 2 if only_active else 0, C.c_void_p(self._obs_buf.data_ptr())))
         self.sync()
         return self._obs
 
-    def obs_compact(self, capacity=None, sync_count=True):
-        """The batch a policy consumes: encode() of the acting seats only, dense, in (game, seat) order
-        (rmj_encode_compact_device).  Returns (obs [k, 74, W], index [k] int32 = game * 4 + seat); with sync_count=False the
-        full-capacity buffers and the device count tensor are returned instead (no host round trip: rows behind the count
-        hold old data).  capacity defaults to n + n // 2 rows and grows on demand."""
+    def _compact_buffers(self, capacity=None):
+        """the compact batch's buffers, at least `capacity` rows (default n + n // 2 + 1, or what an earlier call grew to)"""
         t = self.torch
-        if self.extended:
-            raise vecenv.RmjError("obs_compact() covers Observation.encode(); use obs() for encode_extended()")
         cap = int(capacity or getattr(self, "_cap", 0) or (self.n + self.n // 2 + 1))
         if getattr(self, "_cobs", None) is None or self._cobs.shape[0] < cap:
-            self._cobs_buf = t.zeros((cap, self.row_stride), dtype=t.float32, device=self.device)
-            self._cobs = self._cobs_buf[:, : 74 * self.width].unflatten(-1, (74, self.width))
+            ch = self.channels
+            self._cobs_buf = t.zeros((cap, self._batch_stride or ch * self.width), dtype=t.float32, device=self.device)
+            self._cobs = self._cobs_buf[:, : ch * self.width].unflatten(-1, (ch, self.width))
             self._cidx = t.zeros((cap,), dtype=t.int32, device=self.device)
             self._ccnt = t.zeros((1,), dtype=t.int32, device=self.device)
             self._cap = cap
             if not self.shared:
                 t.cuda.current_stream(self.device).synchronize()   # the buffers were zeroed on torch's stream
-        self.env.encode_compact_device(self._cobs_buf.data_ptr(), self._cidx.data_ptr(), self._cap, self._ccnt.data_ptr())
-        self.sync()
+
+    def _compact_batch_args(self):
+        return dict(compact=True, d_index_ptr=self._cidx.data_ptr(), capacity=self._cap, d_count_ptr=self._ccnt.data_ptr(),
+                    row_stride=self._batch_stride)
+
+    def _compact_result(self, sync_count):
+        """(obs [k, C, W], index [k]) after an encode into the compact buffers; the buffers grow (and the same state is encoded
+        again, without stepping) when the state had more acting seats than rows"""
         if not sync_count:
             return self._cobs, self._cidx, self._ccnt
         k = int(self._ccnt.item())
         if k > self._cap:                                          # more claimants than rows: grow once and encode again
             self._cobs = None
-            return self.obs_compact(capacity=k + k // 8, sync_count=True)
+            self._compact_buffers(k + k // 8)
+            self.env.encode_batch_device(self._feat, self._cobs_buf.data_ptr(), **self._compact_batch_args())
+            self.sync()
         return self._cobs[:k], self._cidx[:k]
+
+    def obs_compact(self, capacity=None, sync_count=True):
+        """The batch a policy consumes: the acting seats' observations only, dense, in (game, seat) order
+        (rmj_encode_compact_device for the base set, rmj_encode_batch_device for the others).  Returns (obs [k, C, W], index [k]
+        int32 = game * 4 + seat); with sync_count=False the full-capacity buffers and the device count tensor are returned instead
+        (no host round trip: rows behind the count hold old data).  capacity defaults to n + n // 2 rows and grows on demand."""
+        self._compact_buffers(capacity)
+        if self.features == "base":
+            self.env.encode_compact_device(self._cobs_buf.data_ptr(), self._cidx.data_ptr(), self._cap, self._ccnt.data_ptr())
+        else:
+            self.env.encode_batch_device(self._feat, self._cobs_buf.data_ptr(), **self._compact_batch_args())
+        self.sync()
+        return self._compact_result(sync_count)
 
     def scores(self):
         vecenv._chk(self.env.L.rmj_scores_device(self.env.h, C.c_void_p(self._scores.data_ptr()), None))
@@ -198,12 +238,11 @@ class TorchVecEnv:
         model's inputs are in info), plus the rank reward of _ppo_worker.py:283-291 in the step that ends the game (rank_rewards:
         a per-rank tuple, default 10 / 4 / -4 / -10; () for none).  terminated [n] bool: the game ended in this step (with auto_reset
         it restarts at the next one).  info: ended, delta, meta, kyoku_idx (round_track), scores, ranks of the games that ended.
-        obs: the resident feature tensor (step_obs) - rows of the seats that act next; None with with_obs=False (extended encoders:
-        call obs() yourself)."""
+        obs: the resident feature tensor of the feature set (step_obs) - rows of the seats that act next; None with with_obs=False."""
         t = self.torch
         if not hasattr(self, "_rt"):
             self.round_track()                       # baseline before the first transition
-        if with_obs and not self.extended:
+        if with_obs:
             obs = self.step_obs(action_ids, auto_reset=auto_reset)
         else:
             self.step(action_ids, auto_reset=auto_reset)
@@ -219,39 +258,77 @@ class TorchVecEnv:
         info = {"ended": ended, "delta": delta, "meta": meta, "kyoku_idx": kidx, "scores": self.scores(), "ranks": ranks}
         return obs, reward, terminated, info
 
-    def step_obs(self, action_ids, auto_reset=True):
-        """step(action_ids) and obs(only_active=True) as ONE launch (rmj_step_ids_encode_device): returns the resident tensor
-        [n, 4, 74, W] whose rows of the seats that are to act next have just been written.  Base encoding only."""
-        if self.extended:
-            raise vecenv.RmjError("step_obs() covers Observation.encode(); use step() + obs() for encode_extended()")
+    def _ids_in(self, action_ids):
         t = self.torch
         ids = action_ids.to(device=self.device, dtype=t.int32).contiguous()
         assert ids.shape == (self.n, 4)
         if not self.shared:
-            t.cuda.current_stream(self.device).synchronize()
-        vecenv._chk(self.env.L.rmj_step_ids_encode_device(self.env.h, C.c_void_p(ids.data_ptr()), int(auto_reset), C.c_void_p(self._obs_buf.data_ptr())))
+            t.cuda.current_stream(self.device).synchronize()   # the ids were produced on torch's stream
+        return ids
+
+    def _logits_in(self, logits):
+        t = self.torch
+        if not hasattr(self, "_ids"):
+            self._ids = t.full((self.n, 4), -1, dtype=t.int32, device=self.device)
+            if not self.shared:
+                t.cuda.current_stream(self.device).synchronize()
+        ptr, stride = None, 0
+        if logits is not None:
+            assert logits.dtype == t.float32 and logits.is_contiguous() and tuple(logits.shape[:2]) == (self.n, 4)
+            ptr, stride = logits.data_ptr(), int(logits.shape[2])
+            if not self.shared:
+                t.cuda.current_stream(self.device).synchronize()
+        return ptr, stride
+
+    def step_obs(self, action_ids, auto_reset=True):
+        """step(action_ids) and obs(only_active=True): returns the resident tensor [n, 4, C, W] whose rows of the seats that are to act
+        next have just been written.  Base set: ONE launch (rmj_step_ids_encode_device); the others: the step and the batch encoder
+        on one stream (rmj_step_ids_encode_batch_device)."""
+        ids = self._ids_in(action_ids)
+        if self.features == "base":
+            vecenv._chk(self.env.L.rmj_step_ids_encode_device(self.env.h, C.c_void_p(ids.data_ptr()), int(auto_reset),
+                                                              C.c_void_p(self._obs_buf.data_ptr())))
+        else:
+            self.env.step_ids_encode_batch_device(ids.data_ptr(), self._feat, self._obs_buf.data_ptr(), row_stride=self._batch_stride,
+                                                  auto_reset=auto_reset)
         self.sync()
         return self._obs
 
     def step_sample_obs(self, logits=None, seed=0, auto_reset=True):
-        """sample_ids(logits, seed) + step_obs(ids) as ONE launch (rmj_step_sample_encode_device): returns (ids [n, 4] int32 - the ids the
-        two calls would have produced -, the resident tensor [n, 4, 74, W] with the rows of the seats that act next).  logits: float32
-        [n, 4, A'] (A' >= 82; 60 in 3P) on this device, or None for the uniform policy.  Base encoding only."""
-        if self.extended:
-            raise vecenv.RmjError("step_sample_obs() covers Observation.encode(); use sample_ids() + step() + obs() for encode_extended()")
-        t = self.torch
-        if not hasattr(self, "_ids"):
-            self._ids = t.full((self.n, 4), -1, dtype=t.int32, device=self.device)
-        ptr, stride = None, 0
-        if logits is not None:
-            assert logits.dtype == t.float32 and logits.is_contiguous() and tuple(logits.shape[:2]) == (self.n, 4)
-            ptr, stride = C.c_void_p(logits.data_ptr()), int(logits.shape[2])
-            if not self.shared:
-                t.cuda.current_stream(self.device).synchronize()
-        vecenv._chk(self.env.L.rmj_step_sample_encode_device(self.env.h, ptr, stride, int(seed) & 0xFFFFFFFFFFFFFFFF, int(auto_reset),
-                                                             C.c_void_p(self._ids.data_ptr()), C.c_void_p(self._obs_buf.data_ptr())))
+        """sample_ids(logits, seed) + step_obs(ids): returns (ids [n, 4] int32 - the ids the two calls would have produced -, the resident
+        tensor [n, 4, C, W] with the rows of the seats that act next).  logits: float32 [n, 4, A'] (A' >= 82; 60 in 3P) on this device, or
+        None for the uniform policy.  Base set: ONE launch (rmj_step_sample_encode_device); the others: rmj_step_sample_encode_batch_device."""
+        ptr, stride = self._logits_in(logits)
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        if self.features == "base":
+            vecenv._chk(self.env.L.rmj_step_sample_encode_device(self.env.h, None if ptr is None else C.c_void_p(ptr), stride, seed, int(auto_reset),
+                                                                 C.c_void_p(self._ids.data_ptr()), C.c_void_p(self._obs_buf.data_ptr())))
+        else:
+            self.env.step_sample_encode_batch_device(ptr, stride, seed, self._ids.data_ptr(), self._feat, self._obs_buf.data_ptr(),
+                                                     row_stride=self._batch_stride, auto_reset=auto_reset)
         self.sync()
         return self._ids, self._obs
+
+    def step_obs_compact(self, action_ids, sync_count=True, auto_reset=True):
+        """step(action_ids) + obs_compact(): the step and the compact batch of the feature set on one stream
+        (rmj_step_ids_encode_batch_device).  Returns (obs [k, C, W], index [k]); with sync_count=False the full-capacity buffers and the
+        device count (obs_compact's form: no host round trip, capturable in a HIP graph once the buffers exist)."""
+        ids = self._ids_in(action_ids)
+        self._compact_buffers()
+        self.env.step_ids_encode_batch_device(ids.data_ptr(), self._feat, self._cobs_buf.data_ptr(), auto_reset=auto_reset,
+                                              **self._compact_batch_args())
+        self.sync()
+        return self._compact_result(sync_count)
+
+    def step_sample_obs_compact(self, logits=None, seed=0, sync_count=True, auto_reset=True):
+        """sample_ids(logits, seed) + step + obs_compact() (rmj_step_sample_encode_batch_device): returns (ids [n, 4], obs [k, C, W],
+        index [k]), or (ids, obs, index, count) - the full-capacity buffers and the device count - with sync_count=False."""
+        ptr, stride = self._logits_in(logits)
+        self._compact_buffers()
+        self.env.step_sample_encode_batch_device(ptr, stride, seed, self._ids.data_ptr(), self._feat, self._cobs_buf.data_ptr(),
+                                                 auto_reset=auto_reset, **self._compact_batch_args())
+        self.sync()
+        return (self._ids,) + tuple(self._compact_result(sync_count))
 
     def bind_stream(self, stream=None):
         """Issue the library's further work on `stream` (a torch.cuda.Stream; default: torch's current stream of the device) -
@@ -259,8 +336,8 @@ class TorchVecEnv:
         side stream the graph will be captured on, run one warm-up iteration there, then capture `sample_ids` / `step_obs` /
         `step` / `obs` / `scores` / `points` together with the policy's kernels (`with torch.cuda.graph(g, stream=s): ...`) - these
         calls only launch kernels on the bound stream (no allocation, no host synchronisation), and the sampler's noise is keyed by
-        every game's own step count, so each replay of the graph draws fresh actions.  `obs_compact(sync_count=True)` reads a count
-        on the host and cannot be captured."""
+        every game's own step count, so each replay of the graph draws fresh actions.  `step_obs_compact(sync_count=False)` captures too
+        (its buffers must exist before the capture); `obs_compact(sync_count=True)` reads a count on the host and cannot be captured."""
         t = self.torch
         s = stream if stream is not None else t.cuda.current_stream(self.device)
         vecenv._chk(self.env.L.rmj_set_stream(self.env.h, C.c_void_p(s.cuda_stream), 0))
@@ -429,7 +506,7 @@ class GymVectorAdapter:
     until the hero is to act again in every env or its game is over.  Envs that reach the hero's turn early wait: they send no action
     (-1) and stay where they are while the others catch up.  reward [n] = the hero's share of step_rl's rewards summed over the inner
     steps; terminated [n]: the game ended (it restarts with the next step: autoreset like gymnasium's NEXT_STEP mode).
-    observation: {"features": [n, 74, W] f32 (the hero's Observation.encode()), "mask": [n, A] bool}."""
+    observation: {"features": [n, C, W] f32 (the hero's observation in env's feature set: C = env.channels), "mask": [n, A] bool}."""
 
     def __init__(self, env: TorchVecEnv, hero=0, opponent=None, max_inner=256):
         self.env, self.t = env, env.torch
@@ -440,7 +517,8 @@ class GymVectorAdapter:
         self.opponent = opponent
         self.max_inner = int(max_inner)
         self.action_space_n = abi.ACTION_SPACE_3P if env.sanma else abi.ACTION_SPACE_4P
-        self.single_observation_shape = {"features": (74, env.width), "mask": (self.action_space_n,)}
+        self.single_observation_shape = {"features": (env.channels, env.width), "mask": (self.action_space_n,)}
+        self.features = env.features
         self._seat = t.arange(4, device=env.device)[None, :]
         self._seed = 0
 

@@ -35,6 +35,7 @@ EXPORTS = [
     "rmj_get_win_results",
     "rmj_drain_events", "rmj_format_events", "rmj_drain_format", "rmj_event_views", "rmj_round_track_device", "rmj_round_track_reset", "rmj_get_events_lost", "rmj_get_log_positions",
     "rmj_drain_text", "rmj_format_events_device",
+    "rmj_encode_batch_device", "rmj_encode_batch", "rmj_step_ids_encode_batch_device", "rmj_step_sample_encode_batch_device",
 ]
 
 
@@ -159,6 +160,10 @@ def load_lib():
     L.rmj_round_track_reset.argtypes = [vp]
     L.rmj_drain_text.argtypes = [vp, vp, C.c_int, C.c_uint32, C.POINTER(abi.TextView)]
     L.rmj_format_events_device.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, C.c_uint32, C.POINTER(abi.TextView)]
+    L.rmj_encode_batch_device.argtypes = [vp, C.POINTER(abi.ObsBatch)]
+    L.rmj_encode_batch.argtypes = [vp, C.POINTER(abi.ObsBatch)]
+    L.rmj_step_ids_encode_batch_device.argtypes = [vp, vp, C.c_int, C.POINTER(abi.ObsBatch)]
+    L.rmj_step_sample_encode_batch_device.argtypes = [vp, vp, C.c_uint32, C.c_uint64, C.c_int, vp, C.POINTER(abi.ObsBatch)]
     _LIB = L
     return L
 
@@ -333,6 +338,68 @@ class VecRiichiEnv:
         _chk(self.L.rmj_bench_encode_compact(self.h, C.c_void_p(d_out_ptr), C.c_void_p(d_index_ptr), capacity, C.c_void_p(d_count_ptr),
                                              reps, C.byref(ms)))
         return ms.value
+
+    # ---- observation batches (header: rmj_encode_batch_device): one feature set, dense or compact
+    def feature_shape(self, features):
+        """(C, W) of a feature set ("base" / "discard_shanten" / "extended" or abi.FEATURES_*) on this environment"""
+        f = abi.FEATURES.get(features, -1) if isinstance(features, str) else int(features)
+        if f not in abi.FEATURE_CHANNELS:
+            raise ValueError(f"unknown feature set {features!r}")
+        if f == abi.FEATURES_DISCARD_SHANTEN and self.game_mode >= 3:
+            raise ValueError("the discard_shanten feature set (riichienv-ml feat_v2) is 4-player only")
+        return abi.FEATURE_CHANNELS[f], 27 if self.game_mode >= 3 else 34
+
+    @staticmethod
+    def obs_batch(features, d_out_ptr, compact=False, d_index_ptr=None, capacity=0, d_count_ptr=None, row_stride=0):
+        """the RmjObsBatch descriptor the three batch entry points share (pointers as integers)"""
+        if isinstance(features, str) and features not in abi.FEATURES:
+            raise ValueError(f"unknown feature set {features!r}")
+        f = abi.FEATURES[features] if isinstance(features, str) else int(features)
+        return abi.ObsBatch(f, int(compact), int(row_stride), int(capacity), d_out_ptr, d_index_ptr, d_count_ptr)
+
+    def encode_batch_device(self, features, d_out_ptr, compact=False, d_index_ptr=None, capacity=0, d_count_ptr=None, row_stride=0):
+        """The acting seats' tensors of one feature set into device memory (rmj_encode_batch_device): dense out[n][4][row_stride] or,
+        compact, out[capacity][row_stride] + index [capacity] i32 (game * 4 + seat) + the device u32 count.  Asynchronous."""
+        b = self.obs_batch(features, d_out_ptr, compact, d_index_ptr, capacity, d_count_ptr, row_stride)
+        _chk(self.L.rmj_encode_batch_device(self.h, C.byref(b)))
+
+    def step_ids_encode_batch_device(self, d_ids_ptr, features, d_out_ptr, compact=False, d_index_ptr=None, capacity=0, d_count_ptr=None,
+                                     row_stride=0, auto_reset=True):
+        """rmj_step_ids_device + rmj_encode_batch_device (rmj_step_ids_encode_batch_device)"""
+        b = self.obs_batch(features, d_out_ptr, compact, d_index_ptr, capacity, d_count_ptr, row_stride)
+        _chk(self.L.rmj_step_ids_encode_batch_device(self.h, C.c_void_p(d_ids_ptr), int(auto_reset), C.byref(b)))
+
+    def step_sample_encode_batch_device(self, d_logits_ptr, stride, seed, d_ids_ptr, features, d_out_ptr, compact=False, d_index_ptr=None,
+                                        capacity=0, d_count_ptr=None, row_stride=0, auto_reset=True):
+        """rmj_sample_ids_device + rmj_step_ids_device + rmj_encode_batch_device (rmj_step_sample_encode_batch_device); d_logits_ptr None =
+        the uniform policy"""
+        b = self.obs_batch(features, d_out_ptr, compact, d_index_ptr, capacity, d_count_ptr, row_stride)
+        _chk(self.L.rmj_step_sample_encode_batch_device(self.h, None if d_logits_ptr is None else C.c_void_p(d_logits_ptr), int(stride),
+                                                        int(seed) & 0xFFFFFFFFFFFFFFFF, int(auto_reset), C.c_void_p(d_ids_ptr), C.byref(b)))
+
+    def encode_batch(self, features="base", compact=True):
+        """The acting seats' tensors of one feature set on the host (rmj_encode_batch): (obs float32 [k, C, W], index int32 [k] =
+        game * 4 + seat) in (game, seat) order.  compact=False goes through the dense layout instead: obs is then [n, 4, C, W] with
+        zeros in the rows of seats that do not act, index lists the acting rows."""
+        ch, w = self.feature_shape(features)
+        if compact:
+            cap = self.n * 4   # never fewer rows than acting seats
+            out = np.zeros((cap, ch, w), np.float32)
+            idx = np.zeros(cap, np.int32)
+            cnt = np.zeros(1, np.uint32)
+            b = self.obs_batch(features, out.ctypes.data, True, idx.ctypes.data, cap, cnt.ctypes.data)
+            _chk(self.L.rmj_encode_batch(self.h, C.byref(b)))
+            k = int(cnt[0])
+            return out[:k], idx[:k]
+        out = np.zeros((self.n, 4, ch, w), np.float32)
+        b = self.obs_batch(features, out.ctypes.data, False)
+        _chk(self.L.rmj_encode_batch(self.h, C.byref(b)))
+        act, _ph, dn = self.status()
+        seats = 3 if self.game_mode >= 3 else 4
+        a = (((act.astype(np.int64)[:, None] >> np.arange(4)) & 1) == 1) & (dn[:, None] == 0)
+        a[:, seats:] = False
+        g, s = np.nonzero(a)
+        return out, (g * 4 + s).astype(np.int32)
 
     def random_actions(self, policy_seed):
         a = np.zeros((self.n, 4), np.uint64)
