@@ -508,6 +508,99 @@ int rmj_step_sample_encode_device(rmj_handle h, const float* d_logits, uint32_t 
  * if every legal id is -inf or NaN, the lowest legal id is drawn; among several +inf logits the lowest of them wins.  The noise
  * u of every id lies strictly inside (0, 1), so every finite logit gets a finite key. */
 int rmj_sample_ids_device(rmj_handle h, const float* d_logits, uint32_t stride, uint64_t seed, int32_t* d_ids);
+/* Action ids of one step when ONE seat per game learns (riichienv-ml trainers/_ppo_worker.py:164-239: the hero samples from the model,
+ * the other seats take `opp_logits.masked_fill(~mask, -1e9).argmax`; :393-466 evaluate_episodes: every seat takes the arg-max).
+ * As rmj_sample_ids_device plus d_hero [n] u8: seat d_hero[g] of game g gets the keyed Gumbel draw of rmj_sample_ids_device, unchanged
+ * (the same (seed, state) gives the id that call gives that seat); every other seat that is to act gets the arg-max of its logits over
+ * its legal ids - ties to the lowest id; a NaN or -inf logit is never chosen while a finite or +inf one is legal; if none is, the
+ * lowest legal id (the sampler's rules above).  d_hero[g] = 255: every seat of that game takes the arg-max.  d_hero = NULL: every
+ * seat samples (identical to rmj_sample_ids_device).  d_logits = NULL: all logits equal.  Cells the sampler never reads are not read.
+ * Asynchronous on the handle's stream. */
+int rmj_select_ids_device(rmj_handle h, const float* d_logits, uint32_t stride, uint64_t seed, const uint8_t* d_hero, int32_t* d_ids);
+
+/* ------------------------------------------------------------------ PPO transition collector
+ * What riichienv-ml's PPO worker returns (trainers/_ppo_worker.py:129-391 collect_episodes): the transitions of one hero seat per
+ * game - features [N][C][W] f32, mask [N][A] u8, action [N] i64, log_prob, advantage, return [N] f32 - cut into one trajectory per
+ * kyoku, with the generalised advantage estimate run backwards over each kyoku and the kyoku's reward paid on its last decision.
+ * A collector is bound to a handle and owns a pool of `capacity` transitions (capacity x (C x W x 4 + A + 45) bytes of device memory:
+ * the caller's decision; what does not fit is counted, never silently lost).  All calls are asynchronous on the handle's stream
+ * and take device pointers; only rmj_ppo_counts waits.  One iteration of the worker's loop:
+ *     obs batch -> policy -> rmj_select_ids_device -> rmj_ppo_record_device -> step (+ next obs batch) -> rmj_round_track_device
+ *     -> the caller's reward -> rmj_ppo_close_device;   at the end rmj_ppo_emit_device. */
+typedef struct RmjPpoConfig {
+    int32_t features;     /* RMJ_FEATURES_*: the rows the pool stores (C x W of the handle's mode) */
+    uint32_t capacity;    /* transitions */
+    double gamma;         /* discount (_ppo_worker.py gamma) */
+    double gae_lambda;
+} RmjPpoConfig;
+typedef struct rmj_ppo* rmj_ppo_handle;
+/* RMJ_ERR_ARG for a feature set the handle cannot serve (DISCARD_SHANTEN in 3P), a zero capacity or a missing pointer.  The
+ * collector lives until rmj_ppo_destroy or the handle's rmj_destroy, whichever comes first. */
+int rmj_ppo_create(rmj_handle h, const RmjPpoConfig* cfg, rmj_ppo_handle* out);
+int rmj_ppo_destroy(rmj_ppo_handle p);
+/* Between the policy's forward pass and the step (_ppo_worker.py:164-199): for every game whose hero is to act
+ * (d_ids[g][d_hero[g]] >= 0; a hero of 255 never records) one transition is appended - the feature row of (game, hero) from the
+ * observation batch `b` the policy just read (either layout of RmjObsBatch, the collector's feature set), the seat's mask bytes, the
+ * action id, the policy's value, and log_prob = log_softmax(masked_fill(logits, ~mask, -1e9))[action] (:175-182) computed in f32 from
+ * the row's logits.  d_logits / d_values are laid out like the observation rows: dense [n][4][logits_stride] / [n][4], compact
+ * [rows][logits_stride] / [rows] by compact slot.  Slots are handed out in (call, game) order.  When the pool is full nothing is
+ * written: the transition is counted as overflowed and the game's open trajectory is marked broken, so that a trajectory with a hole
+ * is never emitted.  The same holds for a hero whose row is missing from a compact batch that was too small. */
+int rmj_ppo_record_device(rmj_ppo_handle p, const RmjObsBatch* b, const uint8_t* d_hero, const int32_t* d_ids, const float* d_logits,
+                          uint32_t logits_stride, const float* d_values);
+/* After the step and the caller's reward computation (_ppo_worker.py:240-281): d_ended [n] u8, non-zero = the hero's open trajectory
+ * of this game ends here (rmj_round_track_device's `ended`: a renchan is a boundary; or a change of kyoku_idx / the game's end, the
+ * worker's own rule), d_reward [n] f32 = the hero's reward for that kyoku.  The trajectory's advantages and returns are computed as
+ * :314-326 does - float64 over the f32 values and reward, the worker's order of operations, no fused multiply-add, rounded to f32
+ * once (:350-351): the worker's bits - and its transitions become valid.  Empty trajectories are skipped (:307-308), broken ones
+ * dropped. */
+int rmj_ppo_close_device(rmj_ppo_handle p, const uint8_t* d_ended, const float* d_reward);
+/* The worker's flattening (:328-353): the valid transitions, in pool order, into the caller's arrays (`rows` rows each; action as
+ * int64 like the worker's).  d_count [2] u32: [0] the number of valid transitions (when it exceeds `rows` only the first `rows` were
+ * written), [1] the slots left out because their trajectory was still open or broken. */
+typedef struct RmjPpoBatch {
+    float* d_features;    /* [rows][C][W] */
+    uint8_t* d_mask;      /* [rows][A], A = 82 (60 in 3P) */
+    int64_t* d_action;
+    float* d_log_prob;
+    float* d_advantage;
+    float* d_return;
+    uint32_t* d_count;    /* [2] */
+    uint32_t rows, reserved;
+} RmjPpoBatch;
+int rmj_ppo_emit_device(rmj_ppo_handle p, const RmjPpoBatch* out);
+/* The pool itself, without a copy: slot s < fill is a transition, `valid[s]` says whether its trajectory was closed complete.
+ * row_stride: floats from one feature row to the next (C x W rounded up to 4).  game / serial / t / prev: the slot's game, the
+ * game's trajectory serial, the position in the trajectory, the slot of the trajectory's previous transition (-1: first).  seg_len /
+ * seg_reward: at the LAST slot of a closed trajectory its length and reward, 0 elsewhere (the worker's kyoku statistics).  counters:
+ * device u32 [5] = the fields of RmjPpoCounts except `open`.  Valid until the collector is destroyed. */
+typedef struct RmjPpoViews {
+    uint32_t capacity, row_stride, action_space, reserved;
+    const float* features;
+    const uint8_t* mask;
+    const int32_t* action;
+    const float *value, *log_prob, *advantage, *ret;
+    const uint8_t* valid;
+    const int32_t *game, *t, *prev, *seg_len;
+    const uint32_t* serial;
+    const float* seg_reward;
+    const uint32_t* counters;
+    const uint32_t* open_len;   /* [n_games] transitions of every game's open trajectory */
+} RmjPpoViews;
+int rmj_ppo_views(rmj_ppo_handle p, RmjPpoViews* out);
+/* Waits for the handle's stream.  fill = valid + open + dropped. */
+typedef struct RmjPpoCounts {
+    uint32_t fill;        /* slots in use */
+    uint32_t valid;       /* transitions of trajectories closed complete */
+    uint32_t dropped;     /* transitions of broken trajectories that were closed: never emitted */
+    uint32_t overflowed;  /* transitions that found no slot (or no observation row) */
+    uint32_t segments;    /* trajectories closed complete */
+    uint32_t open;        /* transitions of trajectories still open */
+} RmjPpoCounts;
+int rmj_ppo_counts(rmj_ppo_handle p, RmjPpoCounts* out);
+/* Empties the pool and forgets the open trajectories (a new collect_episodes call). */
+int rmj_ppo_clear(rmj_ppo_handle p);
+
 /* Round boundaries and per-round score deltas for a trainer on the same GPU (what riichienv-ml's PPO worker computes on the host
  * between steps: trainers/_ppo_worker.py:100-116 GRP features, :240-266 the reward at a kyoku boundary, :283-291 rank rewards).
  * Call after every step (asynchronous on the handle's stream): d_ended [n] u8 = 0 the round goes on, 1 a round ended in this step and

@@ -16,6 +16,7 @@ _LAZY = {
              "calculate_shanten_3p", "check_riichi_candidates", "parse_hand", "parse_tile"),
     "replay": ("MjaiReplay", "MjSoulReplay", "Kyoku", "WinResultContext"),
     "yaku_table": ("Yaku", "get_yaku_by_id", "get_all_yaku"),
+    "ppo": ("PPOCollector",),
 }
 __all__ = ["VecRiichiEnv", "RmjError", "load_lib", "convert", "consts"] + [n for names in _LAZY.values() for n in names]
 

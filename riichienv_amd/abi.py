@@ -238,6 +238,25 @@ class ObsBatch(C.Structure):   # RmjObsBatch
                 ("out", C.c_void_p), ("index", C.c_void_p), ("count", C.c_void_p)]
 
 
+class PpoConfig(C.Structure):   # RmjPpoConfig
+    _fields_ = [("features", C.c_int32), ("capacity", C.c_uint32), ("gamma", C.c_double), ("gae_lambda", C.c_double)]
+
+
+class PpoBatch(C.Structure):    # RmjPpoBatch (rmj_ppo_emit_device)
+    _fields_ = [("features", C.c_void_p), ("mask", C.c_void_p), ("action", C.c_void_p), ("log_prob", C.c_void_p), ("advantage", C.c_void_p),
+                ("ret", C.c_void_p), ("count", C.c_void_p), ("rows", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class PpoViews(C.Structure):    # RmjPpoViews
+    _fields_ = [("capacity", C.c_uint32), ("row_stride", C.c_uint32), ("action_space", C.c_uint32), ("reserved", C.c_uint32)] + [
+        (k, C.c_void_p) for k in ("features", "mask", "action", "value", "log_prob", "advantage", "ret", "valid", "game", "t", "prev", "seg_len",
+                                  "serial", "seg_reward", "counters", "open_len")]
+
+
+class PpoCounts(C.Structure):   # RmjPpoCounts
+    _fields_ = [(k, C.c_uint32) for k in ("fill", "valid", "dropped", "overflowed", "segments", "open")]
+
+
 class BenchResult(C.Structure):
     _fields_ = [("total_ms", C.c_double), ("step_kernel_ms", C.c_double), ("env_steps", C.c_uint64),
                 ("launches", C.c_uint32), ("launches_in_flight", C.c_uint32), ("full_path_steps", C.c_uint64),

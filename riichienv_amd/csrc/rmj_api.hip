@@ -100,11 +100,12 @@ __global__ void k_random_actions(Env E, uint64_t policy_seed, uint64_t* out) {
 // Non-finite logits: a -inf or NaN logit is never drawn while a finite one is legal; if every legal id is -inf or NaN the lowest legal
 // id is drawn; among several +inf logits the lowest id wins.  tests/sampler_ref.py restates the draw in float64.
 __device__ __forceinline__ int32_t sample_ids_row(const uint32_t* status, const GState* core, const uint8_t* nlegal, const uint8_t* mask, uint64_t game_offset,
-                                                  int game_mode, uint32_t g, bool in, const float* __restrict__ logits, uint32_t stride, uint64_t seed, int lane) {
+                                                  int game_mode, uint32_t g, bool in, const float* __restrict__ logits, uint32_t stride, uint64_t seed, int lane,
+                                                  uint32_t seats = 0xFu) {   // seats: the seats that draw (k_select_ids draws for one)
     const int r = lane & 15;
     const uint32_t gi = in ? g : 0u;
     const uint32_t st = in ? status[gi] : 0x10000u;
-    const uint32_t am = (st >> 16) & 0xFFu ? 0u : (st & 0xFu);   // done games have nobody to act
+    const uint32_t am = ((st >> 16) & 0xFFu ? 0u : (st & 0xFu)) & seats;   // done games have nobody to act
     const int A = game_mode >= 3 ? RMJ_ACTION_SPACE_3P : RMJ_ACTION_SPACE_4P;
     const uint64_t base = sm64(seed ^ sm64(game_offset + gi)) + ((uint64_t)core[gi].step_count << 10);
     const uint32_t nl4 = in ? *reinterpret_cast<const uint32_t*>(nlegal + (size_t)gi * 4) : 0u;   // the four list lengths of the game
@@ -629,6 +630,7 @@ __device__ __forceinline__ uint32_t obs_block_prefix(const uint32_t* __restrict_
     for (int d = 32; d >= 1; d >>= 1) s += (uint32_t)__shfl_xor((int)s, d, 64);
     return s;
 }
+#include "rmj_ppo.hip.h"
 // Observation.encode() of the games [g0, g0 + gridDim.x): ONE block (= one wave) per game, which walks the seats it has to
 // encode - with only_active that is the acting seat (one, rarely two or three), so the launch has a quarter of the blocks of
 // a (game, seat) grid and no early-exit blocks.  The tensor of a seat is staged as one byte per cell (EncByteSink: 2.5 KB,
@@ -1101,6 +1103,7 @@ struct rmj_env {
     int queue_min_chunk = 5;        // shortest ticket (steps): a rollout of >= 2 tickets per quad runs as tickets; RMJ_QUEUE_MIN_CHUNK at create
     uint32_t max_xcc_id = 0;        // largest HW_REG_XCC_ID seen by a probe launch at create: the ticket rollout assumes ids 0..7 (one L2 per queue)
     uint32_t* d_ev_lost = nullptr;  // [n_games] records a game's ring lost to a late drain (rmj_drain_events), cumulative
+    std::vector<struct rmj_ppo*> ppo;   // transition collectors bound to this handle (rmj_ppo_create): destroyed with it
     void* d_track = nullptr;        // round tracker (rmj_round_track_device): hand index / scores / meta where every game's round began
     // staging of rmj_drain_format's size call (the records sit in h_pin): reused by the call that brings the text buffer
     bool stage_valid = false;
@@ -1180,6 +1183,14 @@ struct DevTmp {
     }
 };
 
+// a PPO transition collector bound to a handle (rmj_ppo_create): its pool is one device allocation
+struct rmj_ppo {
+    rmj_env* env = nullptr;
+    RmjPpoConfig cfg{};
+    double gamma_lambda = 0.0;   // gamma * lambda as the worker forms it (_ppo_worker.py:322), in double
+    void* mem = nullptr;
+    PpoPool P{};
+};
 static int shanten_tables_for(int device, ShantenTables* out);
 static void launch_encode_base_range(rmj_env* h, hipStream_t st, int only_active, float* d_out, uint32_t g0, uint32_t g1);
 
@@ -1316,6 +1327,7 @@ int rmj_destroy(rmj_handle h) {
     hipFree(h->d.core); hipFree(h->d.wall); hipFree(h->d.wall_dg); hipFree(h->d.legal); hipFree(h->d.nlegal); hipFree(h->d_decay); if (h->d_scratch) hipFree(h->d_scratch); hipFree(h->d.mask);
     hipFree(h->d.waits); hipFree(h->d.status); hipFree(h->d.events); hipFree(h->d.win); hipFree(h->d_actions); hipFree(h->d_counter); hipFree(h->d_obs_offs); hipFree(h->d_env); hipFree(h->d_qheads);   // (d_qdone lives in the same allocation)
     hipFree(h->d_ev_lost); hipFree(h->d_track); hipFree(h->d_heavy);
+    while (!h->ppo.empty()) rmj_ppo_destroy(h->ppo.back());
     hipFree(h->d_txt); hipFree(h->d_txt_offs); hipFree(h->d_txt_work);
     if (h->h_txt) hipHostFree(h->h_txt);
     if (h->h_txt_offs) hipHostFree(h->h_txt_offs);
@@ -1536,6 +1548,16 @@ int rmj_sample_ids_device(rmj_handle h, const float* d_logits, uint32_t stride, 
     HIPCHK(hipSetDevice(h->cfg.device));
     const uint32_t n = h->cfg.n_games;
     hipLaunchKernelGGL(k_sample_ids, dim3((n + 15) / 16), dim3(256), 0, h->stream, h->d, d_logits, stride, seed, d_ids);
+    HIPCHK(hipGetLastError());
+    return RMJ_OK;
+}
+int rmj_select_ids_device(rmj_handle h, const float* d_logits, uint32_t stride, uint64_t seed, const uint8_t* d_hero, int32_t* d_ids) {
+    if (!h || !d_ids) return fail(RMJ_ERR_ARG, "null argument");
+    const uint32_t A = h->cfg.game_mode >= 3 ? RMJ_ACTION_SPACE_3P : RMJ_ACTION_SPACE_4P;
+    if (d_logits && stride < A) return fail(RMJ_ERR_ARG, "logits row shorter than the action space");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const uint32_t n = h->cfg.n_games;
+    hipLaunchKernelGGL(k_select_ids, dim3((n + 15) / 16), dim3(256), 0, h->stream, h->d, d_logits, stride, seed, d_hero, d_ids);
     HIPCHK(hipGetLastError());
     return RMJ_OK;
 }
@@ -3134,6 +3156,141 @@ int rmj_step_sample_encode_batch_device(rmj_handle h, const float* d_logits, uin
     if ((rc = rmj_step_ids_device(h, d_ids, auto_reset))) return rc;
     launch_encode_batch(h, b, rs);
     HIPCHK(hipGetLastError());
+    return RMJ_OK;
+}
+// ---- PPO transition collector (rmj_ppo.hip.h) ------------------------------------------------------------------
+static int ppo_clear_impl(rmj_ppo* p) {
+    rmj_env* h = p->env;
+    const uint32_t n = h->cfg.n_games;
+    HIPCHK(hipMemsetAsync(p->P.ctr, 0, PPO_C_WORDS * 4, h->stream));
+    HIPCHK(hipMemsetAsync(p->P.tail, 0xFF, (size_t)n * 4, h->stream));
+    HIPCHK(hipMemsetAsync(p->P.open_len, 0, (size_t)n * 4, h->stream));
+    HIPCHK(hipMemsetAsync(p->P.g_serial, 0, (size_t)n * 4, h->stream));
+    HIPCHK(hipMemsetAsync(p->P.broken, 0, (size_t)n, h->stream));
+    return RMJ_OK;
+}
+int rmj_ppo_create(rmj_handle h, const RmjPpoConfig* cfg, rmj_ppo_handle* out) {
+    if (!h || !cfg || !out) return fail(RMJ_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (!cfg->capacity) return fail(RMJ_ERR_ARG, "rmj_ppo_create: the pool needs a capacity (transitions)");
+    uint32_t ch, w, rs;
+    float dummy;
+    RmjObsBatch b{};
+    b.features = cfg->features;
+    b.d_out = &dummy;   // (shape check only)
+    int rc = batch_shape(h, &b, &ch, &w, &rs);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    rmj_ppo* p = new rmj_ppo();
+    p->env = h;
+    p->cfg = *cfg;
+    p->gamma_lambda = cfg->gamma * cfg->gae_lambda;
+    const uint32_t n = h->cfg.n_games, cap = cfg->capacity, A = h->cfg.game_mode >= 3 ? RMJ_ACTION_SPACE_3P : RMJ_ACTION_SPACE_4P;
+    PpoPool& P = p->P;
+    P.capacity = cap; P.feat_floats = ch * w; P.row_floats = (ch * w + 3u) & ~3u; P.A = A;
+    const size_t big = n > cap ? n : cap;
+    // one allocation: the feature rows first (16-byte rows), then the 4-byte arrays, then the bytes
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t o_feat = take((size_t)cap * P.row_floats * 4), o_action = take((size_t)cap * 4), o_value = take((size_t)cap * 4), o_logp = take((size_t)cap * 4),
+                 o_adv = take((size_t)cap * 4), o_ret = take((size_t)cap * 4), o_game = take((size_t)cap * 4), o_serial = take((size_t)cap * 4), o_t = take((size_t)cap * 4),
+                 o_prev = take((size_t)cap * 4), o_slen = take((size_t)cap * 4), o_srew = take((size_t)cap * 4), o_tail = take((size_t)n * 4), o_olen = take((size_t)n * 4),
+                 o_gser = take((size_t)n * 4), o_rowof = take((size_t)n * 4), o_offs = take(big * 4), o_totals = take(((big + PPO_SCAN_BLOCK - 1) / PPO_SCAN_BLOCK) * 4),
+                 o_ctr = take(PPO_C_WORDS * 4), o_mask = take((size_t)cap * A), o_valid = take(cap), o_broken = take(n);
+    if (hipMalloc(&p->mem, off) != hipSuccess) {
+        (void)hipGetLastError();
+        delete p;
+        return fail(RMJ_ERR_HIP, "rmj_ppo_create: no device memory for a pool of " + std::to_string(off >> 20) + " MiB (capacity x row bytes: choose a smaller capacity)");
+    }
+    uint8_t* m = (uint8_t*)p->mem;
+    P.feat = (float*)(m + o_feat); P.action = (int32_t*)(m + o_action); P.value = (float*)(m + o_value); P.logp = (float*)(m + o_logp); P.adv = (float*)(m + o_adv);
+    P.ret = (float*)(m + o_ret); P.game = (int32_t*)(m + o_game); P.serial = (uint32_t*)(m + o_serial); P.t = (int32_t*)(m + o_t); P.prev = (int32_t*)(m + o_prev);
+    P.seg_len = (int32_t*)(m + o_slen); P.seg_reward = (float*)(m + o_srew); P.tail = (int32_t*)(m + o_tail); P.open_len = (uint32_t*)(m + o_olen);
+    P.g_serial = (uint32_t*)(m + o_gser); P.rowof = (int32_t*)(m + o_rowof); P.offs = (uint32_t*)(m + o_offs); P.totals = (uint32_t*)(m + o_totals);
+    P.ctr = (uint32_t*)(m + o_ctr); P.mask = m + o_mask; P.valid = m + o_valid; P.broken = m + o_broken;
+    h->ppo.push_back(p);
+    // everything behind the feature rows starts as zeros (the views show defined values in slots that were never filled)
+    if (hipMemsetAsync(m + o_action, 0, off - o_action, h->stream) != hipSuccess || (rc = ppo_clear_impl(p))) {
+        rmj_ppo_destroy(p);
+        return rc ? rc : fail(RMJ_ERR_HIP, "rmj_ppo_create: hipMemsetAsync failed");
+    }
+    *out = p;
+    return RMJ_OK;
+}
+int rmj_ppo_destroy(rmj_ppo_handle p) {
+    if (!p) return RMJ_OK;
+    rmj_env* h = p->env;
+    hipSetDevice(h->cfg.device);
+    if (h->stream) hipStreamSynchronize(h->stream);
+    for (size_t i = 0; i < h->ppo.size(); i++)
+        if (h->ppo[i] == p) { h->ppo.erase(h->ppo.begin() + i); break; }
+    hipFree(p->mem);
+    delete p;
+    return RMJ_OK;
+}
+int rmj_ppo_clear(rmj_ppo_handle p) {
+    if (!p) return fail(RMJ_ERR_ARG, "null argument");
+    HIPCHK(hipSetDevice(p->env->cfg.device));
+    return ppo_clear_impl(p);
+}
+// waves of a grid-stride launch with one wave per item: enough to fill the chip a few times over, never more than the items
+static inline dim3 ppo_wave_grid(uint32_t items) { const uint32_t b = (items + 3u) / 4u; return dim3(b < 1u ? 1u : (b > 4096u ? 4096u : b)); }
+int rmj_ppo_record_device(rmj_ppo_handle p, const RmjObsBatch* b, const uint8_t* d_hero, const int32_t* d_ids, const float* d_logits, uint32_t logits_stride,
+                          const float* d_values) {
+    if (!p || !b || !d_hero || !d_ids || !d_logits || !d_values) return fail(RMJ_ERR_ARG, "null argument");
+    rmj_env* h = p->env;
+    uint32_t ch, w, rs;
+    int rc = batch_shape(h, b, &ch, &w, &rs);
+    if (rc) return rc;
+    if (b->features != p->cfg.features) return fail(RMJ_ERR_ARG, "rmj_ppo_record_device: the observation batch is not of the collector's feature set");
+    if (logits_stride < p->P.A) return fail(RMJ_ERR_ARG, "logits row shorter than the action space");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const uint32_t n = h->cfg.n_games, nb = (n + PPO_SCAN_BLOCK - 1) / PPO_SCAN_BLOCK;
+    hipLaunchKernelGGL(k_ppo_scan, dim3(nb), dim3(PPO_SCAN_BLOCK), 0, h->stream, p->P, n, d_hero, d_ids, b->compact ? (const int32_t*)b->d_index : (const int32_t*)nullptr,
+                       b->capacity, (const uint32_t*)b->d_count);
+    hipLaunchKernelGGL(k_ppo_record, ppo_wave_grid(n), dim3(256), 0, h->stream, p->P, n, (const uint8_t*)h->d.mask, d_hero, d_ids, (const float*)b->d_out, rs, d_logits,
+                       logits_stride, d_values);
+    hipLaunchKernelGGL(k_ppo_advance, dim3(1), dim3(64), 0, h->stream, p->P, nb);
+    HIPCHK(hipGetLastError());
+    return RMJ_OK;
+}
+int rmj_ppo_close_device(rmj_ppo_handle p, const uint8_t* d_ended, const float* d_reward) {
+    if (!p || !d_ended || !d_reward) return fail(RMJ_ERR_ARG, "null argument");
+    rmj_env* h = p->env;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const uint32_t n = h->cfg.n_games;
+    hipLaunchKernelGGL(k_ppo_close, dim3((n + 255u) / 256u), dim3(256), 0, h->stream, p->P, n, d_ended, d_reward, p->cfg.gamma, p->gamma_lambda);
+    HIPCHK(hipGetLastError());
+    return RMJ_OK;
+}
+int rmj_ppo_emit_device(rmj_ppo_handle p, const RmjPpoBatch* out) {
+    if (!p || !out || !out->d_count) return fail(RMJ_ERR_ARG, "null argument");
+    if (out->rows && (!out->d_features || !out->d_mask || !out->d_action || !out->d_log_prob || !out->d_advantage || !out->d_return))
+        return fail(RMJ_ERR_ARG, "null argument");
+    rmj_env* h = p->env;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const uint32_t cap = p->P.capacity;
+    PpoOut O{out->d_features, out->d_mask, out->d_action, out->d_log_prob, out->d_advantage, out->d_return, out->d_count, out->rows};
+    hipLaunchKernelGGL(k_ppo_emit_scan, dim3((cap + PPO_SCAN_BLOCK - 1) / PPO_SCAN_BLOCK), dim3(PPO_SCAN_BLOCK), 0, h->stream, p->P);
+    hipLaunchKernelGGL(k_ppo_emit, ppo_wave_grid(cap), dim3(256), 0, h->stream, p->P, O);
+    HIPCHK(hipGetLastError());
+    return RMJ_OK;
+}
+int rmj_ppo_views(rmj_ppo_handle p, RmjPpoViews* out) {
+    if (!p || !out) return fail(RMJ_ERR_ARG, "null argument");
+    const PpoPool& P = p->P;
+    *out = RmjPpoViews{P.capacity, P.row_floats, P.A, 0u, P.feat, P.mask, P.action, P.value, P.logp, P.adv, P.ret, P.valid, P.game, P.t, P.prev, P.seg_len, P.serial,
+                       P.seg_reward, P.ctr, P.open_len};
+    return RMJ_OK;
+}
+int rmj_ppo_counts(rmj_ppo_handle p, RmjPpoCounts* out) {
+    if (!p || !out) return fail(RMJ_ERR_ARG, "null argument");
+    rmj_env* h = p->env;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    uint32_t c[PPO_C_WORDS];
+    HIPCHK(hipMemcpyAsync(c, p->P.ctr, sizeof(c), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    *out = RmjPpoCounts{c[PPO_C_FILL], c[PPO_C_VALID], c[PPO_C_DROPPED], c[PPO_C_OVERFLOWED], c[PPO_C_SEGMENTS], c[PPO_C_FILL] - c[PPO_C_VALID] - c[PPO_C_DROPPED]};
     return RMJ_OK;
 }
 

@@ -238,7 +238,8 @@ class TorchVecEnv:
         model's inputs are in info), plus the rank reward of _ppo_worker.py:283-291 in the step that ends the game (rank_rewards:
         a per-rank tuple, default 10 / 4 / -4 / -10; () for none).  terminated [n] bool: the game ended in this step (with auto_reset
         it restarts at the next one).  info: ended, delta, meta, kyoku_idx (round_track), scores, ranks of the games that ended.
-        obs: the resident feature tensor of the feature set (step_obs) - rows of the seats that act next; None with with_obs=False."""
+        obs: the resident feature tensor of the feature set (step_obs) - rows of the seats that act next; None with with_obs=False.
+        The worker's full output - one hero's transitions cut per kyoku, with GAE - is riichienv_amd.ppo.PPOCollector."""
         t = self.torch
         if not hasattr(self, "_rt"):
             self.round_track()                       # baseline before the first transition

@@ -36,6 +36,8 @@ EXPORTS = [
     "rmj_drain_events", "rmj_format_events", "rmj_drain_format", "rmj_event_views", "rmj_round_track_device", "rmj_round_track_reset", "rmj_get_events_lost", "rmj_get_log_positions",
     "rmj_drain_text", "rmj_format_events_device",
     "rmj_encode_batch_device", "rmj_encode_batch", "rmj_step_ids_encode_batch_device", "rmj_step_sample_encode_batch_device",
+    "rmj_select_ids_device", "rmj_ppo_create", "rmj_ppo_destroy", "rmj_ppo_record_device", "rmj_ppo_close_device", "rmj_ppo_emit_device",
+    "rmj_ppo_views", "rmj_ppo_counts", "rmj_ppo_clear",
 ]
 
 
@@ -164,6 +166,15 @@ def load_lib():
     L.rmj_encode_batch.argtypes = [vp, C.POINTER(abi.ObsBatch)]
     L.rmj_step_ids_encode_batch_device.argtypes = [vp, vp, C.c_int, C.POINTER(abi.ObsBatch)]
     L.rmj_step_sample_encode_batch_device.argtypes = [vp, vp, C.c_uint32, C.c_uint64, C.c_int, vp, C.POINTER(abi.ObsBatch)]
+    L.rmj_select_ids_device.argtypes = [vp, vp, C.c_uint32, C.c_uint64, vp, vp]
+    L.rmj_ppo_create.argtypes = [vp, C.POINTER(abi.PpoConfig), C.POINTER(vp)]
+    L.rmj_ppo_destroy.argtypes = [vp]
+    L.rmj_ppo_record_device.argtypes = [vp, C.POINTER(abi.ObsBatch), vp, vp, vp, C.c_uint32, vp]
+    L.rmj_ppo_close_device.argtypes = [vp, vp, vp]
+    L.rmj_ppo_emit_device.argtypes = [vp, C.POINTER(abi.PpoBatch)]
+    L.rmj_ppo_views.argtypes = [vp, C.POINTER(abi.PpoViews)]
+    L.rmj_ppo_counts.argtypes = [vp, C.POINTER(abi.PpoCounts)]
+    L.rmj_ppo_clear.argtypes = [vp]
     _LIB = L
     return L
 
