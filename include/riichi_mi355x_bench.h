@@ -12,8 +12,7 @@
  *                              for any batch of >= 64 quads: tests)
  *   RMJ_QUEUE_TEST_SKIP_XCDS=mask   TEST HOOK: waves on these XCDs leave the ticket kernel at once, as if the dispatcher had given
  *                              that XCD no block - exercises the fix-up launch (tests/test_gpu_fullsize.py)
- *   RMJ_ENC_STREAMS, RMJ_ENC_PARTS_QUAD, RMJ_ENC_FUSED   schedules of the step + encode rollout
- *   RMJ_EXTRA_LDS=bytes        occupancy experiments of the per-step kernel
+ *   RMJ_ENC_FUSED=0|1          the step + encode rollout as one launch (1, default) or as parts of the batch on the rollout streams
  */
 #ifndef RIICHI_MI355X_BENCH_H
 #define RIICHI_MI355X_BENCH_H

@@ -42,9 +42,7 @@ struct BlockSharedT {
     WaveScratch x[N];
 };
 typedef BlockSharedT<WPB> BlockShared;
-#ifndef RMJ_STEP_WPB
 #define RMJ_STEP_WPB 1 /* games (= waves) per block of the step kernel: single-wave blocks release their LDS as soon as the game is done (a block of four waited for its slowest game) */
-#endif
 static inline dim3 step_grid(uint32_t n) { return dim3((n + RMJ_STEP_WPB - 1) / RMJ_STEP_WPB); }
 // smallest batch that a multi-step device rollout splits over several streams of a handle (rmj_step_random)
 #define RMJ_SPLIT_MIN_GAMES 16384u
@@ -378,15 +376,8 @@ struct EvalShared {
     alignas(16) uint32_t out[4][16];
 };
 static_assert(sizeof(RmjHandCase) == 88 && sizeof(RmjHandResult) == 64, "k_eval_hands stages cases / results by these sizes");
-#ifndef RMJ_EVAL_WAVES
 #define RMJ_EVAL_WAVES 6   /* 129 VGPR left alone = three waves per SIMD: 0.72 G hands/s; four 0.84, five 0.906, six 0.91-0.92, seven 0.905, eight 0.84 */
-#endif
-#if RMJ_EVAL_WAVES > 0
-#define RMJ_EVAL_OCC __attribute__((amdgpu_waves_per_eu(RMJ_EVAL_WAVES, RMJ_EVAL_WAVES)))
-#else
-#define RMJ_EVAL_OCC
-#endif
-__global__ __launch_bounds__(256) RMJ_EVAL_OCC void k_eval_hands(const RmjHandCase* cases, uint32_t n, RmjHandResult* out) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RMJ_EVAL_WAVES, RMJ_EVAL_WAVES))) void k_eval_hands(const RmjHandCase* cases, uint32_t n, RmjHandResult* out) {
     __shared__ EvalShared shw[WPB];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, rb = lane & 48, row = lane >> 4;
     const uint32_t k0 = (blockIdx.x * WPB + wave) * 4u;   // first hand of the wave
@@ -639,18 +630,11 @@ __device__ __forceinline__ uint32_t obs_block_prefix(const uint32_t* __restrict_
 // it runs the same either way (3P 0.1347 -> 0.1378 ms, occupancy 5 -> 8 changed nothing in round 5), but next to step and sampler kernels of other
 // shards on other streams the seven-wave form crowds them out: the trainer loop as 4 shards on 4 streams 304 -> 345 M env.step/s, 2 shards 290 -> 315 M,
 // compact batch 305 -> 334 M with the cap (five waves: 336 / 292 / 320; round-5 binary: 340-350 / 312-320 / 311-316).
-#ifndef RMJ_ENC_WAVES
 #define RMJ_ENC_WAVES 4
-#endif
-#if RMJ_ENC_WAVES > 0
-#define RMJ_ENC_OCC __attribute__((amdgpu_waves_per_eu(RMJ_ENC_WAVES, RMJ_ENC_WAVES)))
-#else
-#define RMJ_ENC_OCC
-#endif
 // `offs` != nullptr: compact output (rmj_encode_compact_device) - the observations of the acting seats, one after the other in
 // (game, seat) order: observation offs[g] + j is the j-th acting seat of game g, `index` receives game * 4 + seat.
 template <bool SANMA, bool COMPACT>
-__global__ __launch_bounds__(64) RMJ_ENC_OCC void k_encode_base(Env E, int only_active, float* __restrict__ out, uint32_t g0,
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RMJ_ENC_WAVES, RMJ_ENC_WAVES))) void k_encode_base(Env E, int only_active, float* __restrict__ out, uint32_t g0,
                                                                const uint32_t* __restrict__ offs, int32_t* __restrict__ index, uint32_t capacity,
                                                                const uint32_t* __restrict__ totals, uint32_t* __restrict__ count) {
     constexpr int W = SANMA ? ENC_W3 : ENC_W4, NPP = SANMA ? 3 : 4;
@@ -699,12 +683,7 @@ __global__ __launch_bounds__(64) RMJ_ENC_OCC void k_encode_base(Env E, int only_
         }
         const int head = (int)(((16u - (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u) >> 2);  // 0 or 2 floats
         EncByteSink<W> o{raw + ((4 - head) & 3), lut, lane, -1.0f};
-#ifdef RMJ_ENC_NOCOMPUTE   /* experiment: the memory side alone (record in, 74 x W floats out) */
-        o.zero();
-        wave_sync();
-#else
         encode_seat_to<SANMA>(S, seat, lane, hist, o, true);
-#endif
         enc_emit_bytes<W>(dst, o.cells, lut, lane, head, o.big);
         wave_sync();
     }
@@ -728,16 +707,9 @@ __device__ __forceinline__ void enc_emit_fn(float* dst, int n_floats, int lane, 
 // table of the 53 channels that are one value per row) and the 84 meld-overview channels (a 0/1 pattern).  6 KB of LDS per
 // block instead of 12 KB: the kernel waits on table lookups (the ukeire walk), and its duration is inversely proportional to
 // the resident waves (measured by capping them: 13 / 8 / 5 / 3 blocks per CU -> 1.05 / 1.63 / 2.24 / 3.67 ms).
-#ifndef RMJ_ENCX_WAVES
 #define RMJ_ENCX_WAVES 6   /* 3P (85 VGPR left alone = five waves): six waves 691 -> 661 us, seven 667, eight 755; 4P (63 VGPR) the same at any */
-#endif
-#if RMJ_ENCX_WAVES > 0
-#define RMJ_ENCX_OCC __attribute__((amdgpu_waves_per_eu(RMJ_ENCX_WAVES, RMJ_ENCX_WAVES)))
-#else
-#define RMJ_ENCX_OCC
-#endif
 template <bool SANMA>
-__global__ __launch_bounds__(64) RMJ_ENCX_OCC void k_encode_ext(Env E, int only_active, const float* __restrict__ decay, float* __restrict__ out) {
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RMJ_ENCX_WAVES, RMJ_ENCX_WAVES))) void k_encode_ext(Env E, int only_active, const float* __restrict__ decay, float* __restrict__ out) {
     constexpr int W = SANMA ? ENC_W3 : ENC_W4;
     constexpr int CH = ENC_EXT_CH;
     __shared__ GState st;
@@ -802,7 +774,7 @@ __global__ __launch_bounds__(64) RMJ_ENCX_OCC void k_encode_ext(Env E, int only_
 // in parallel.  A seat that does not act leaves on the 4-byte status word.  The compact slot is k_obs_offsets' offset of the game,
 // plus the totals of the scan blocks before it, plus the acting seats of the game below this one.
 template <bool SANMA, int FEAT, bool COMPACT>
-__global__ __launch_bounds__(64) RMJ_ENCX_OCC void k_encode_batch(Env E, const float* __restrict__ decay, float* __restrict__ out, uint32_t RS,
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RMJ_ENCX_WAVES, RMJ_ENCX_WAVES))) void k_encode_batch(Env E, const float* __restrict__ decay, float* __restrict__ out, uint32_t RS,
                                                                   const uint32_t* __restrict__ offs, const uint32_t* __restrict__ totals,
                                                                   int32_t* __restrict__ index, uint32_t capacity, uint32_t* __restrict__ count) {
     constexpr int W = SANMA ? ENC_W3 : ENC_W4, NPP = SANMA ? 3 : 4;
@@ -1015,11 +987,8 @@ __global__ __launch_bounds__(256) void k_shanten(ShantenTables T, const uint8_t*
 }
 // (round 4's walk: 82 VGPRs = five waves per SIMD left alone; compiled for six: +5 %, eight: the same.  Round 5's pair-dense walk, 74 VGPRs left alone:
 //  five waves 0.388, six 0.412, seven 0.425, eight 0.430 G hands/s of best ukeire on random hands)
-#ifndef RMJ_UKE_WAVES
 #define RMJ_UKE_WAVES 8
-#endif
-#define RMJ_UKE_OCC __attribute__((amdgpu_waves_per_eu(RMJ_UKE_WAVES, RMJ_UKE_WAVES)))
-__global__ __launch_bounds__(256) RMJ_UKE_OCC void k_ukeire(ShantenTables T, const uint8_t* counts, const uint8_t* visible, uint32_t n, int sanma,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RMJ_UKE_WAVES, RMJ_UKE_WAVES))) void k_ukeire(ShantenTables T, const uint8_t* counts, const uint8_t* visible, uint32_t n, int sanma,
                                                 int mode, uint32_t* out) {
     const int lane = threadIdx.x & 63;
     const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -1124,8 +1093,6 @@ struct rmj_env {
     uint64_t txt_pin_bytes = 0;
     void* h_txt_offs = nullptr;     // pinned text offsets [games + 1], then the new cursors
     size_t txt_pin_offs_bytes = 0;
-    int enc_streams = 0;            // RMJ_ENC_STREAMS at create (0: want_streams): parts of the step + encode rollout
-    int enc_parts_quad = -1;        // RMJ_ENC_PARTS_QUAD at create (-1: follow `quad`)
     int enc_fused = 1;              // RMJ_ENC_FUSED at create: the step + encode rollout as ONE launch (k_step4_enc / k_step4_queue_enc); 0 = parts on streams
     uint32_t q_slots_enc = 0;       // waves of k_step4_queue_enc the device holds at once
 };
@@ -1220,8 +1187,6 @@ static int create_impl(rmj_env* h, const RmjConfig* cfg, uint64_t** d_seeds_out)
     if (const char* e = getenv("RMJ_HEAVY_FIRST")) h->heavy_first = atoi(e);
     h->rows_pw = cfg->n_games <= RMJ_ROWS1_MAX_GAMES ? 1u : (cfg->n_games <= RMJ_ROWS2_MAX_GAMES ? 2u : 4u);
     if (const char* e = getenv("RMJ_ROWS")) { const int r = atoi(e); if (r == 1 || r == 2 || r == 4) h->rows_pw = (uint32_t)r; }
-    if (const char* e = getenv("RMJ_ENC_STREAMS")) h->enc_streams = atoi(e);
-    if (const char* e = getenv("RMJ_ENC_PARTS_QUAD")) h->enc_parts_quad = atoi(e) != 0;
     if (const char* e = getenv("RMJ_ENC_FUSED")) h->enc_fused = atoi(e);
     const size_t B = cfg->n_games;
     Env& d = h->d;
@@ -1360,8 +1325,6 @@ int rmj_clone(rmj_handle h, rmj_handle* out) {
     c->queue_tail = h->queue_tail;
     c->rows_pw = h->rows_pw;
     c->heavy_first = h->heavy_first;
-    c->enc_streams = h->enc_streams;
-    c->enc_parts_quad = h->enc_parts_quad;
     c->enc_fused = h->enc_fused;
     if (h->d.enc_stride != c->d.enc_stride) { int rc2 = rmj_set_encode_row_stride(c, h->d.enc_stride); if (rc2) { rmj_destroy(c); return rc2; } }
     const size_t B = h->cfg.n_games, ring = (size_t)h->d.ring_mask + 1u;
@@ -1449,14 +1412,9 @@ int rmj_reset(rmj_handle h, const uint8_t* select, const uint8_t* walls, const u
 
 // one k_step launch over games [g0, g1) of the handle
 static inline void launch_step_range(rmj_env* h, hipStream_t st, const uint64_t* d_actions, uint64_t policy_seed, uint32_t flags,
-                                     uint32_t g0, uint32_t g1, bool allow_quad = true) {
+                                     uint32_t g0, uint32_t g1) {
     const bool greedy = (flags & STEP_F_GREEDY) != 0u;   // (four-games-per-wave kernels only: the callers check h->quad)
-#ifdef RMJ_TUNE_LDS
-    static const unsigned extra_lds = getenv("RMJ_EXTRA_LDS") ? (unsigned)atoi(getenv("RMJ_EXTRA_LDS")) : 0u;  // occupancy experiments
-#else
-    const unsigned extra_lds = 0u;
-#endif
-    if (h->quad && allow_quad) {   // four games per wave (device policy, packed actions or action ids); small batches: two or one (rows_pw)
+    if (h->quad) {   // four games per wave (device policy, packed actions or action ids); small batches: two or one (rows_pw)
         const uint32_t rows = h->rows_pw;
         flags |= (rows == 4u ? 0u : rows) << STEP_F_ROWS_SHIFT;
         const uint32_t units = (g1 - g0 + rows - 1u) / rows;
@@ -1490,8 +1448,8 @@ static inline void launch_step_range(rmj_env* h, hipStream_t st, const uint64_t*
         }
         return;
     }
-    if (h->cfg.game_mode >= 3) hipLaunchKernelGGL(rmj3::k_step, step_grid(g1 - g0), dim3(64 * RMJ_STEP_WPB), extra_lds, st, (const Env*)h->d_env, d_actions, policy_seed, flags, g0, g1);
-    else hipLaunchKernelGGL(rmj4::k_step, step_grid(g1 - g0), dim3(64 * RMJ_STEP_WPB), extra_lds, st, (const Env*)h->d_env, d_actions, policy_seed, flags, g0, g1);
+    if (h->cfg.game_mode >= 3) hipLaunchKernelGGL(rmj3::k_step, step_grid(g1 - g0), dim3(64 * RMJ_STEP_WPB), 0, st, (const Env*)h->d_env, d_actions, policy_seed, flags, g0, g1);
+    else hipLaunchKernelGGL(rmj4::k_step, step_grid(g1 - g0), dim3(64 * RMJ_STEP_WPB), 0, st, (const Env*)h->d_env, d_actions, policy_seed, flags, g0, g1);
 }
 int rmj_step_device(rmj_handle h, const rmj_action_t* d_actions) {
     if (!h || !d_actions) return fail(RMJ_ERR_ARG, "null argument");
@@ -1832,9 +1790,8 @@ int rmj_step_random_encode(rmj_handle h, uint64_t policy_seed, uint32_t n_steps,
     }
     // The encoder is bound by its stores, the step by instruction issue: parts of the batch on k streams put the step of one
     // part under the encoder of another (measured, 65 536 3P games: one stream 283 M env.step/s, four parts 383 M with the
-    // four-game kernel and 323 M with the one-game kernel).  RMJ_ENC_STREAMS / RMJ_ENC_PARTS_QUAD: experiment knobs.
-    int k = h->enc_streams > 0 ? h->enc_streams : h->want_streams;
-    const bool parts_quad = h->enc_parts_quad >= 0 ? h->enc_parts_quad != 0 : h->quad != 0;
+    // four-game kernel and 323 M with the one-game kernel).
+    int k = h->want_streams;
     if (k > RMJ_MAX_ROLLOUT_STREAMS) k = RMJ_MAX_ROLLOUT_STREAMS;
     if ((int)(n / RMJ_SPLIT_MIN_PART) < k) k = (int)(n / RMJ_SPLIT_MIN_PART);
     if (n_steps < 2 || n < RMJ_SPLIT_MIN_GAMES || k < 2) k = 1;
@@ -1846,7 +1803,7 @@ int rmj_step_random_encode(rmj_handle h, uint64_t policy_seed, uint32_t n_steps,
             for (int i = 0; i < k; i++) {
                 hipStream_t st = i ? h->xstream[i - 1] : h->stream;
                 const uint32_t g0 = (uint32_t)((uint64_t)n * i / k), g1 = (uint32_t)((uint64_t)n * (i + 1) / k);
-                launch_step_range(h, st, nullptr, policy_seed, flags, g0, g1, parts_quad);
+                launch_step_range(h, st, nullptr, policy_seed, flags, g0, g1);
                 launch_encode_base_range(h, st, only_active, d_out, g0, g1);
             }
         for (int i = 1; i < k; i++) {
@@ -3665,14 +3622,6 @@ extern "C" int rmj_debug_re_prof(unsigned long long* out8, int reset) {
     unsigned long long z[24] = {0};
     if (out8) HIPCHK(hipMemcpyFromSymbol(out8, HIP_SYMBOL(rmj::g_re_prof), sizeof(z)));
     if (reset) HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(rmj::g_re_prof), z, sizeof(z)));
-    return RMJ_OK;
-}
-#endif
-#ifdef RMJ_DEBUG_HWID
-// debugging build only: HW ids / times of the waves of the last k_step4_act_enc launch (4 u64 per block)
-extern "C" int rmj_debug_hwid_fetch(uint64_t* out, uint32_t n_blocks) {
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpyFromSymbol(out, HIP_SYMBOL(rmj::g_dbg_hwid), (size_t)(n_blocks < RMJ_DEBUG_HWID ? n_blocks : RMJ_DEBUG_HWID) * 32));
     return RMJ_OK;
 }
 #endif

@@ -127,9 +127,6 @@ __device__ unsigned long long* g_tl4;
                         [0] r4_round_end, [1] its calls, [2] step4_pass2, [3] its calls, [4] r4_round_end up to the wall loop, [5] the wall / deal / hand-sort / event loop, [6] games dealt */
 __device__ unsigned long long g_re_prof[24];   // [8 + mode]: rows by R4_RE_* mode at the calls of step4_finish_rounds
 #endif
-#ifdef RMJ_DEBUG_HWID   /* value = blocks recorded; see k_step4_act_enc */
-__device__ unsigned long long g_dbg_hwid[4 * RMJ_DEBUG_HWID];
-#endif
 #ifdef RMJ_QTL   /* ticket timeline build of k_step4_queue (-DRMJ_QTL, scripts/timeline_queue.py, never the shipped library) */
 __device__ unsigned long long* g_qtl;
 #define RMJ_QTL_ROW 256   /* u64 per wave: [0] kernel entry, [1] exit, [2] tickets, then 4 per ticket */

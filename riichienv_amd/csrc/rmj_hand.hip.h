@@ -45,18 +45,10 @@ __device__ __forceinline__ uint32_t row_sum16(uint32_t v) {
 // published legal lists with entries missing (docs/journal_r06.md section 1; scripts/lint_isa_last_vgpr.py guards every build).
 // The permute has no 64-bit operand, needs one lane-constant register (the selector) instead of two (rb & 32, rb & 16), and is two
 // full-rate instructions.
-#ifndef RMJ_ROW_BALLOT_SHIFT64
-#define RMJ_ROW_BALLOT_SHIFT64 0   /* 1: the form of rounds 2-5 (A/B and the reproduction of the hazard only; scripts/lint_isa_last_vgpr.py then decides whether a build is safe) */
-#endif
 __device__ __forceinline__ uint32_t row_ballot16(bool p, int rb) {
     const uint64_t b = __ballot(p);
-#if RMJ_ROW_BALLOT_SHIFT64
-    const uint32_t w = (rb & 32) ? (uint32_t)(b >> 32) : (uint32_t)b;
-    return __builtin_amdgcn_ubfe(w, (uint32_t)(rb & 16), 16u);
-#else
     const uint32_t sel = 0x0C0C0100u + ((uint32_t)rb >> 4) * 0x0202u;
     return __builtin_amdgcn_perm((uint32_t)(b >> 32), (uint32_t)b, sel);
-#endif
 }
 __device__ __forceinline__ int t_suit(int t) { return t >= 27 ? 3 : (t >= 18 ? 2 : (t >= 9 ? 1 : 0)); }
 __device__ __forceinline__ uint32_t ph_get(const PH& h, int s) { return s == 0 ? h.a : (s == 1 ? h.b : (s == 2 ? h.c : h.d)); }

@@ -51,9 +51,7 @@ __device__ __noinline__ void ol_step_full(CtxV v, uint64_t mine, uint32_t flags)
     TLF(c, 13);
 }
 
-#ifndef RMJ_STEP_WAVES
 #define RMJ_STEP_WAVES 8
-#endif
 __global__ __launch_bounds__(64 * RMJ_STEP_WPB, RMJ_STEP_WAVES) void k_step(const Env* __restrict__ Ep, const uint64_t* __restrict__ actions, uint64_t policy_seed, uint32_t flags,
                                                                                 uint32_t g_base, uint32_t g_end) {
     CEnv& E = *(CEnv*)Ep;  // device-resident record, read through the constant address space (see CEnv)

@@ -444,9 +444,6 @@ __device__ __forceinline__ int sh_entry_pm(uint64_t a, uint64_t b, int m) {
 // Both quantities judge the same (discard d, draw t) pairs - "does t lower the shanten of the hand without d" - so one
 // pass serves both, and the shanten after each discard is evaluated for all d at once (lane = d): 2 + #held-types
 // per-lane table evaluations instead of 2 + 4 x #held-types for the two separate walks.
-#ifndef RMJ_UKEIRE_DENSE
-#define RMJ_UKEIRE_DENSE 1   // 1: the fast case runs the pair-dense walk of rmj_ukeire.hip.h (round 5); 0: the round-4 walk below (A/B)
-#endif
 __device__ inline void sh_ukeire_dense(const ShantenTables& T, const PH& h, uint32_t my_vis, bool sm, int lane, bool want_eff, bool want_uke,
                                        uint32_t& eff, uint32_t& uke, int cur_in, int* nsh_out, int* cur_out);
 __device__ inline void sh_ukeire_both(const ShantenTables& T, const PH& h, uint32_t my_cnt, uint32_t my_vis, bool sm, int lane,
@@ -460,7 +457,7 @@ __device__ inline void sh_ukeire_both(const ShantenTables& T, const PH& h, uint3
     // (h - d + t then has two) and holds no 2m..8m; 1m / 9m then belong to the honor "suit" and a hand's honor word is that of its own
     // relocation.  Anything else takes the general walk below.
     const bool fast = !sm || (__popc(~(h.d | (h.d >> 1) | (h.d >> 2)) & O7_1) >= 3 && (h.a & ~(7u | (7u << 24))) == 0u);
-    if (RMJ_UKEIRE_DENSE && fast && total <= 14) {
+    if (fast && total <= 14) {   // the pair-dense walk of rmj_ukeire.hip.h (round 5); the round-4 walk below serves what is left
         sh_ukeire_dense(T, h, my_vis, sm, lane, want_eff, want_uke, eff, uke, cur_in, nsh_out, cur_out);
         return;
     }

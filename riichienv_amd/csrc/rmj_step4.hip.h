@@ -40,36 +40,6 @@ __device__ __forceinline__ uint32_t r4_rows(uint32_t flags) {
     const uint32_t c = (flags >> STEP_F_ROWS_SHIFT) & 3u;
     return c == 0u ? 4u : c;
 }
-#ifndef RMJ_INLINE_STEP
-#define RMJ_INLINE_STEP 1     /* the step of the fused rollouts inlined into the rollout loop (see step4_call_inl); 0: out of line, as in rounds 2-4 */
-#endif
-#ifndef RMJ_ROW_SETTLE
-#define RMJ_ROW_SETTLE 1      /* Tsumo / Ron settlements of the rich tier stay in tier 0 too (r4_round_end); 0: they bail to the full path */
-#endif
-#ifndef RMJ_ROW_ROUND_END
-#define RMJ_ROW_ROUND_END 1   /* exhaustive draws, next rounds and restarts stay in tier 0 (r4_round_end); 0: they enter the full path at the exit */
-#endif
-#ifndef RMJ_FULL_PRIO
-#define RMJ_FULL_PRIO 0
-#endif
-#ifndef RMJ_RON_SKIP
-#define RMJ_RON_SKIP 1   /* Ron eligibility: skipped when no seat of any game of the wave waits on its game's discard (0: A/B) */
-#endif
-#ifndef RMJ_CHI_SKIP
-#define RMJ_CHI_SKIP 1   /* chi lists: a pattern no row of the wave can form is skipped as a whole (0: A/B) */
-#endif
-#ifndef RMJ_GROUP_FILTER_ALL
-#define RMJ_GROUP_FILTER_ALL 0   /* 1: the group-residue tests also in the kernels of one step per launch (A/B; see step4_body) */
-#endif
-#ifndef RMJ_GROUP_FILTER13
-#define RMJ_GROUP_FILTER13 1   /* wait-cache refill: the group-residue test in front of the table shanten (r4_group_residues; 0: A/B) */
-#endif
-#ifndef RMJ_GROUP_FILTER14
-#define RMJ_GROUP_FILTER14 1   /* riichi bound of the drawer's list: the same on 14 tiles (0: A/B) */
-#endif
-#ifndef RMJ_HEAVY_TENPAI
-#define RMJ_HEAVY_TENPAI 1   /* heavy-first order of the per-step kernel: games with a seat that waits without a riichi count as heavy (0: A/B) */
-#endif
 #ifdef RMJ_CUTS   /* instruction accounting build (scripts/valu_sections4.py, scripts/bail_census.py) */
 /* (an asm s_endpgm, not __builtin_amdgcn_endpgm: the builtin is noreturn, and a noreturn call inside divergent control flow lets the
    compiler drop the EXEC restore behind the region - rows that were masked off there stayed off for the rest of the step in the greedy
@@ -102,9 +72,7 @@ struct Quad4Enc {          // byte staging of Observation.encode() inside the fu
     alignas(16) uint8_t raw[(ENC_CH * (KSANMA ? ENC_W3 : ENC_W4) + 4 + 15) / 16 * 16];
     uint32_t hist[ENC_HIST_WORDS];
 };
-#ifndef R4_RS_WORDS
 #define R4_RS_WORDS 100   /* round-end scratch (r4_round_end): 32 words of packed bucket counters + 136 16-bit sort words.  Measured (profiles/r04_lds_sweep.txt): up to 6 336 B of LDS per wave the fused rollout runs at 1.81-1.82 G env.step/s, at 6 512 B at 1.70 G */
-#endif
 struct Quad4Shared {
     GState st[4];
     union {
@@ -438,7 +406,7 @@ __device__ __forceinline__ void r4_fill_waits13(R4& q, PState* P, int n) {
         // Of the rest, a standard-form tenpai needs its groups' sizes mod 3 to be {1} or {2, 2} (r4_group_residues); seven pairs
         // and kokushi keep their own gates.
         bool far = iso >= 2 && yaochu < 12;
-        if (RMJ_GROUP_FILTER13 && q.gf && !far && !(len3 == 4 && (sp.pairs >= 6 || yaochu >= 12))) {
+        if (q.gf && !far && !(len3 == 4 && (sp.pairs >= 6 || yaochu >= 12))) {
             const uint32_t gr = r4_group_residues(sp.start, sp.S, n, q.r, q.rb);
             far = gr != 0x01u && gr != 0x20u;
         }
@@ -560,7 +528,7 @@ __device__ __forceinline__ void r4_deal_next(R4& q, int pf) {
     GState* G = q.G;
     const int drawable = G->drawable_count;
     if (drawable == 0) {   // exhaustive draw
-        if (RMJ_ROW_ROUND_END && q.pause_ok) q.rend = 1u /* R4_RE_DRAW */;   // the round ends in row form, behind the transitions of this call (r4_round_end)
+        if (q.pause_ok) q.rend = 1u /* R4_RE_DRAW */;   // the round ends in row form, behind the transitions of this call (r4_round_end)
         else { R4BAIL(q, 7); q.cont = 1; }                                    // the full path takes over right here (trigger_ryukyoku)
         return;
     }
@@ -867,7 +835,7 @@ __device__ __forceinline__ void r4_resolve_discard(R4& q, int pid, int tile, boo
     // the cached wait: calc.is_win of legal_actions.rs:254-310 is true): RICH offers that Ron here; any other seat that could
     // win needs the evaluator - full path.
     uint32_t ron_m = 0u;
-    if (!RMJ_RON_SKIP || __ballot(((W >> tt) & 1ull) != 0ull)) {   // (wave-uniform) nobody in the wave's games waits on its game's tile (nearly every discard): no furiten arithmetic
+    if (__ballot(((W >> tt) & 1ull) != 0ull)) {   // (wave-uniform) nobody in the wave's games waits on its game's tile (nearly every discard): no furiten arithmetic
         const uint64_t dtm = S4.discard_type_mask;
         const bool in_discards = (dtm >> tt) & 1ull;
         const bool in_missed = (qfl & PF_MISSED_DOUJUN) || ((qfl & PF_RIICHI_DECLARED) && (qfl & PF_MISSED_RIICHI));
@@ -953,9 +921,7 @@ __device__ __forceinline__ void r4_resolve_discard(R4& q, int pid, int tile, boo
                     const bool pat_ok = k == 0 ? (r9 >= 2) : (k == 1 ? (r9 >= 1 && r9 <= 7) : (r9 <= 6));
                     const uint32_t ma = k == 0 ? m_m2 : (k == 1 ? m_m1 : m_p1);
                     const uint32_t mbb = k == 0 ? m_m1 : (k == 1 ? m_p1 : m_p2);
-#if RMJ_CHI_SKIP
                     if (!__ballot(pat_ok && ma != 0u && mbb != 0u)) continue;   // (wave-uniform) no row of the wave holds this pattern's two tiles: nothing to list
-#endif
                     int forb = __popc(m_0);
                     if (k == 2 && r9 <= 5) forb += __popc(m_p3);
                     if (k == 0 && r9 >= 3) forb += __popc(m_m3);
@@ -1097,7 +1063,7 @@ __device__ __forceinline__ void r4_gen_act_legal(R4& q, int& nl_mine) {
                 // tile is merged into the sorted run by its rank; a hand that is not "sorted run + drawn tile" keeps the histogram bound.
                 bool may;
                 const int nx14 = __builtin_amdgcn_update_dpp(0xFFFF, ht, 0x101 /* row_shl:1 */, 0xf, 0xf, false);
-                if (RMJ_GROUP_FILTER14 && q.gf && d_idx == hl - 1 && rballot(r < hl - 2 && ht > nx14, rb) == 0u) {
+                if (q.gf && d_idx == hl - 1 && rballot(r < hl - 2 && ht > nx14, rb) == 0u) {
                     const bool in = r < hl;
                     const int k = in ? r4_key(hty) : 1000;
                     const int kd = rbc(k, rb + hl - 1);
@@ -1234,8 +1200,17 @@ __device__ __forceinline__ void r4_emit_now(R4& q, bool on, uint32_t w) {
 // RICH: with the settlements of the rich tier (the lean tier's Tsumo / Ron actions bail to the full path: its copy has no evaluator)
 #ifdef RMJ_RE_PROF
 #define RE_MARK(k) do { const unsigned long long t__ = __builtin_amdgcn_s_memrealtime(); if (lane == 0) atomicAdd(&rmj::g_re_prof[k], t__ - re_t); re_t = t__; } while (0)
+/* the marks of step4_finish_rounds: rows by R4_RE_* mode; a time stamp; [0] / [2] ticks and [1] / [3] calls of r4_round_end / step4_pass2 ([17], [19]: sums of the call and return times) */
+#define RE_ROWS(md) do { if ((threadIdx.x & 15u) == 0u) atomicAdd(&rmj::g_re_prof[8 + ((md) & 15u)], 1ull); } while (0)
+#define RE_STAMP(t) const unsigned long long t = __builtin_amdgcn_s_memrealtime()
+#define RE_ROUND_END_DONE(t) do { if ((threadIdx.x & 63u) == 0u) { const unsigned long long tr = __builtin_amdgcn_s_memrealtime(); atomicAdd(&rmj::g_re_prof[0], tr - t); atomicAdd(&rmj::g_re_prof[1], 1ull); atomicAdd(&rmj::g_re_prof[17], t); atomicAdd(&rmj::g_re_prof[19], tr); } } while (0)
+#define RE_PASS2_DONE(t) do { if ((threadIdx.x & 63u) == 0u) { atomicAdd(&rmj::g_re_prof[2], __builtin_amdgcn_s_memrealtime() - t); atomicAdd(&rmj::g_re_prof[3], 1ull); } } while (0)
 #else
 #define RE_MARK(k) do {} while (0)
+#define RE_ROWS(md) do {} while (0)
+#define RE_STAMP(t) do {} while (0)
+#define RE_ROUND_END_DONE(t) do {} while (0)
+#define RE_PASS2_DONE(t) do {} while (0)
 #endif
 template <bool RICH>
 __device__ __noinline__ void r4_round_end(const Env* Ep, uint32_t g0) {
@@ -1260,7 +1235,7 @@ __device__ __noinline__ void r4_round_end(const Env* Ep, uint32_t g0) {
     const bool seat = r < KNP;
     const int oya = G->oya;
     bool oya_won = false;               // _initialize_next_round's first argument: the dealer won / is tenpai at the draw
-    if (RICH && RMJ_ROW_SETTLE && __ballot(win)) {
+    if (RICH && __ballot(win)) {
         // ---- settlement of a Tsumo (state/mod.rs:690-880) or of the Ron answers (state/mod.rs:945-1142), rows side by side: one winner
         // per row and pass (the Tsumo, then the Ron winners by distance from the discarder), the evaluation in row form with the settlement's
         // conditions (r4_seat_eval<true>), the payments by lane = seat.
@@ -2028,12 +2003,7 @@ __device__ __forceinline__ uint32_t step4_body(const Env* Ep, Quad4Shared& sh, u
     uint64_t tl_prev = __builtin_readcyclecounter();
 #endif
     int lane_ = threadIdx.x & 63;
-#if RMJ_INLINE_STEP
     if constexpr (INLR) asm volatile("" : "+v"(lane_));   // nothing derived from the lane id is hoisted out of the rollout loop and kept live across the step (step4_call_inl)
-#endif
-#if RMJ_INLINE_ENC
-    if constexpr (LOOP && !INLR && !PASS2) asm volatile("" : "+v"(lane_));
-#endif
     const int lane = lane_;
     const int row = lane >> 4, r = lane & 15, rb = lane & 48;
     const uint32_t rows_pw = r4_rows(flags);
@@ -2071,8 +2041,8 @@ __device__ __forceinline__ uint32_t step4_body(const Env* Ep, Quad4Shared& sh, u
     q.G = &sh.st[row]; q.T = &sh.u.t; q.E = &E; q.lane = lane; q.r = r; q.rb = rb; q.row = row; q.g = g;
     // (round 6, one box, 65 536 games: with the tests the fused rollouts gain 1.5 % (2.11 -> 2.14 G); the kernels of one step per launch lose - the step at
     //  80 registers has no room for them: 0.97 -> 0.88 G - and keep the isolated-tile bounds alone)
-    q.gf = LOOP || RMJ_GROUP_FILTER_ALL;
-    // pass 2 (RMJ_ROW_ROUND_END): the rows whose round ended in pass 1 and has been dealt since (r4_round_end, run by the caller between the
+    q.gf = LOOP;
+    // pass 2: the rows whose round ended in pass 1 and has been dealt since (r4_round_end, run by the caller between the
     // passes - a call in here would cost every step ten more callee-saved registers): they skip policy and transitions, get their
     // first list and are published like any other row
     q.live = pass2 ? ((uint32_t)row < n_here && sh.rmode[row] != 0u) : ((uint32_t)row < n_here && (!INLR || left != 0u));
@@ -2097,7 +2067,7 @@ __device__ __forceinline__ uint32_t step4_body(const Env* Ep, Quad4Shared& sh, u
     }
     // ---- policy (lane = seat): RandomAgent keyed per (game, step, seat), see k_step; POL = 1: the greedy policy (r4_policy_greedy)
     uint64_t mine = RMJ_NO_ACTION;
-    q.pause_ok = RMJ_ROW_ROUND_END && !pass2;
+    q.pause_ok = !pass2;
     q.yk = 0u; q.yk_mode = 0u;
     if (pass2) {
         if (q.live) {
@@ -2106,7 +2076,7 @@ __device__ __forceinline__ uint32_t step4_body(const Env* Ep, Quad4Shared& sh, u
             if (md == R4_RE_YAKU_CLAIMS || md == R4_RE_YAKU_TSUMO) { q.yk_mode = md; q.yk = sh.yk[row]; }
         }
     } else if (q.live && G->is_done) {   // finished game: restart (auto-reset: in row form) or nothing to do (full path)
-        if (RMJ_ROW_ROUND_END && (flags & STEP_F_AUTORESET)) q.rend = R4_RE_RESTART; else R4BAIL(q, 18);
+        if (flags & STEP_F_AUTORESET) q.rend = R4_RE_RESTART; else R4BAIL(q, 18);
     }
     int pol_seat = -1, pol_sh = 99;   // greedy policy: shanten of the hand the chosen discard of seat pol_seat leaves
     if (POL == 1) {
@@ -2200,7 +2170,7 @@ __device__ __forceinline__ uint32_t step4_body(const Env* Ep, Quad4Shared& sh, u
                 // no action for the current player (a policy that skipped it; 3P: a seat the reference leaves without any legal action
                 // after a Kita in its riichi stage, quirk Q15 - such a game stays like this for good, one bail per step before round 4)
                 noop = true;
-            } else if (RICH && RMJ_ROW_SETTLE && ty == RMJ_TSUMO && q.pause_ok) {
+            } else if (RICH && ty == RMJ_TSUMO && q.pause_ok) {
                 // (with or without the tile: a caller's Tsumo matched the list's entry by type)
                 q.rend = R4_RE_WIN_TSUMO;   // the settlement, the next round or the end of the game between the passes (r4_round_end)
             } else if (((act >> 8) & 0xFFu) == RMJ_TILE_NONE) {
@@ -2467,7 +2437,7 @@ __device__ __forceinline__ uint32_t step4_body(const Env* Ep, Quad4Shared& sh, u
             const uint32_t roned = rballot(has && my_ty == RMJ_RON, rb) & 0xFu;
             const uint32_t offer = G->ron_offer_mask;
             if (roned & act_m) {                                  // Ron settlement
-                if (RICH && RMJ_ROW_SETTLE && q.pause_ok && !(!KSANMA && __popc(roned & act_m) >= 3 && (E.rule_bits & RMJ_RULE_SANCHAHO_DRAW))) {
+                if (RICH && q.pause_ok && !(!KSANMA && __popc(roned & act_m) >= 3 && (E.rule_bits & RMJ_RULE_SANCHAHO_DRAW))) {
                     if (r < 4 && ((offer & ~roned) >> r) & 1u) {  // a Ron offer that was not taken (state/mod.rs:905-915 runs before the settlement)
                         uint32_t fl = G->p[r].flags | PF_MISSED_DOUJUN;
                         if (fl & PF_RIICHI_DECLARED) fl |= PF_MISSED_RIICHI;
@@ -2629,7 +2599,7 @@ __device__ __forceinline__ uint32_t step4_body(const Env* Ep, Quad4Shared& sh, u
     R4T(2);
     // rows whose round ended (an exhaustive draw above, a finished game under auto-reset) stop here in pass 1: ryukyoku, next round or end
     // of game and the deal happen between the passes (r4_round_end), their observation is pass 2's
-    bool wait_deal = RMJ_ROW_ROUND_END && !pass2 && t0 && !q.bail && q.rend != 0u;
+    bool wait_deal = !pass2 && t0 && !q.bail && q.rend != 0u;
     if (q.rend) q.dirty = 0xFu;
     if (pass2 && RICH && __ballot(t0 && q.yk_mode == R4_RE_YAKU_CLAIMS)) {
         // pass 2 of a row that paused at its discard's Ron check: the rest of _resolve_discard with the evaluator's answers.  Whatever makes
@@ -2650,7 +2620,7 @@ __device__ __forceinline__ uint32_t step4_body(const Env* Ep, Quad4Shared& sh, u
             if (!(noop && G->nlegal[G->current_player & 3] == 0 && Pc.hand_len + 3 * Pc.n_melds == 14)) r4_gen_act_legal<RICH>(q, nl_mine);
             if (q.rend && q.bail) q.cont = 2;   // (a dealt hand tier 0 has no list for: the full path publishes the state as it stands)
         }
-        if (RMJ_ROW_ROUND_END && !pass2 && !q.bail && q.rend != 0u) wait_deal = true;   // (paused at the list's Tsumo check)
+        if (!pass2 && !q.bail && q.rend != 0u) wait_deal = true;   // (paused at the list's Tsumo check)
     }
     R4M(45);
     R4T(3);
@@ -2660,7 +2630,7 @@ __device__ __forceinline__ uint32_t step4_body(const Env* Ep, Quad4Shared& sh, u
     // tier 0 had got to), and the row's own publication flags: quiet unless this was the last step of the rollout
     const uint32_t used = (!q.live || pass2) ? 0u : ((INLR && second && (!q.bail || q.cont)) ? 2u : 1u);
     const uint32_t fl_pub = pass2 ? sh.rfl[row] : (INLR ? (flags | ((final_chunk && left == used) ? STEP_F_ALLROWS : STEP_F_QUIET)) : flags);
-    if (RMJ_ROW_ROUND_END && r == 0) {
+    if (r == 0) {
         sh.rmode[row] = wait_deal ? q.rend : 0u;
         sh.rfl[row] = fl_pub;
     }
@@ -2769,13 +2739,7 @@ __device__ __forceinline__ uint32_t step4_body(const Env* Ep, Quad4Shared& sh, u
         wave_sync();
 #endif
         if (LOOP) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // the full path reads wall, lists and record with plain loads: drop what the L1 may hold of an earlier visit of this game to this CU (see the record fetch above)
-#if RMJ_FULL_PRIO
-        if (!LOOP || RMJ_FULL_PRIO > 1) __builtin_amdgcn_s_setprio(3);   // experiment: the few long waves of a per-step launch issue ahead of the others of their SIMD
-#endif
         ol_step_full(ctx_pack(c), lane < 4 ? m_full : RMJ_NO_ACTION, (uint32_t)__builtin_amdgcn_readlane((int)fl_full, 16 * br));
-#if RMJ_FULL_PRIO
-        if (!LOOP || RMJ_FULL_PRIO > 1) __builtin_amdgcn_s_setprio(0);
-#endif
         wave_sync();
 #ifdef RMJ_TL4
         if (!LOOP && lane < 16) rmj::g_tl4[(size_t)blockIdx.x * RMJ_TL4_ROW + 16 + lane] += (unsigned long long)sh.u.x.tl_acc[lane];
@@ -2793,14 +2757,6 @@ __device__ __forceinline__ uint32_t step4_body(const Env* Ep, Quad4Shared& sh, u
     return used | (__ballot(wait_deal) ? R4_RET_ROUND : 0u);
     }
 }
-// The step as an out-of-line function with its own static LDS: the rollout loop calls it once per step, so nothing of a
-// step is hoisted out of the loop or kept live across it (the loop inlined: 48 VGPR + 37 SGPR spills).
-template <bool LOOP, int POL>
-__device__ __noinline__ uint32_t step4_call(const Env* Ep, uint64_t policy_seed, uint32_t flags, uint32_t g_base, uint32_t g_end, uint32_t load,
-                                            uint64_t gs_row, uint32_t quad = 0xFFFFFFFFu) {
-    Quad4Shared& sh = g_q4;
-    return step4_body<LOOP, POL>(uni_ptr(Ep), sh, uni(policy_seed), uni(flags), uni(g_base), uni(g_end), uni(load) != 0u, gs_row, nullptr, uni(quad));
-}
 // Pass 2 of a step whose wave ended rounds (R4_RET_ROUND): r4_round_end has dealt them, their rows get the dealer's first list and are
 // published (step4_body<.., PASS2>: no policy, no transitions - a small function, out of line, entered once in ~25 wave-steps)
 template <bool LOOP, int POL>
@@ -2812,99 +2768,64 @@ template <bool LOOP, int POL>
 __device__ __forceinline__ void step4_finish_rounds(const Env* Ep, uint32_t flags, uint32_t g_base, uint32_t g_end, uint32_t quad = 0xFFFFFFFFu) {
     constexpr bool RICH = (POL == 1) || !LOOP;   // (step4_body's tier)
     const uint32_t md = g_q4.rmode[(threadIdx.x & 63u) >> 4];
-#ifdef RMJ_RE_PROF
-    if ((threadIdx.x & 15u) == 0u) atomicAdd(&rmj::g_re_prof[8 + (md & 15u)], 1ull);
-#endif
+    RE_ROWS(md);
     if (__ballot(md == R4_RE_DRAW || md == R4_RE_RESTART || md == R4_RE_WIN_TSUMO || md == R4_RE_WIN_RON)) {
         if (LOOP && RICH) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // (the settlement reads the ura indicators off the wall slab with plain loads)
-#ifdef RMJ_RE_PROF
-        const unsigned long long pt0 = __builtin_amdgcn_s_memrealtime();
-#endif
+        RE_STAMP(pt0);
         r4_round_end<RICH>(Ep, g_base + (quad == 0xFFFFFFFFu ? blockIdx.x : quad) * r4_rows(flags));
-#ifdef RMJ_RE_PROF
-        if ((threadIdx.x & 63u) == 0u) { const unsigned long long tr = __builtin_amdgcn_s_memrealtime(); atomicAdd(&rmj::g_re_prof[0], tr - pt0); atomicAdd(&rmj::g_re_prof[1], 1ull); atomicAdd(&rmj::g_re_prof[17], pt0); atomicAdd(&rmj::g_re_prof[19], tr); }
-#endif
+        RE_ROUND_END_DONE(pt0);
     }
     if (RICH && __ballot(md == R4_RE_YAKU_CLAIMS || md == R4_RE_YAKU_TSUMO)) r4_yaku_answers();   // (the lean tier never pauses for a yaku check)
-#ifdef RMJ_RE_PROF
-    const unsigned long long pt1 = __builtin_amdgcn_s_memrealtime();
-#endif
+    RE_STAMP(pt1);
     step4_pass2<LOOP, POL>(Ep, flags, g_base, g_end, quad);
-#ifdef RMJ_RE_PROF
-    if ((threadIdx.x & 63u) == 0u) { atomicAdd(&rmj::g_re_prof[2], __builtin_amdgcn_s_memrealtime() - pt1); atomicAdd(&rmj::g_re_prof[3], 1ull); }
-#endif
+    RE_PASS2_DONE(pt1);
 }
 // ... with inline responses (step4_body<.., INLR>): `left` steps to go per row, returns the steps taken per row
-#ifndef RMJ_INLINE_RESP
-#define RMJ_INLINE_RESP 3   /* bit 0: the RandomAgent's rollouts, bit 1: the greedy policy's */
-#endif
 // Round 5: the step of the fused RandomAgent / greedy rollouts is INLINED into the rollout loop.  Out of line it paid, per call, 33
 // callee-saved SGPRs through v_writelane / v_readlane (64 vector instructions of ~1 445) and 13 callee-saved VGPRs through scratch; the
 // inlined loop of round 4 spilled far worse (45 VGPR + 66 SGPR) because everything derived from the LANE ID - row, rb, LDS addresses of the
 // row's record - is loop invariant too and was hoisted and kept live across the step.  With the lane id laundered per iteration as well
 // (step4_body) the loop spills 17 VGPR / 52 SGPR in the ticket kernel, mostly outside the hot sections: +5 % at every batch size
-// (profiles/r05_inline_step_ab.txt).  RMJ_INLINE_STEP=0 brings the out-of-line step back (A/B).
-#if RMJ_INLINE_STEP
-#define R4_CALL_ATTR __forceinline__
-#else
-#define R4_CALL_ATTR __noinline__
-#endif
+// (profiles/r05_inline_step_ab.txt).
 template <int POL>
-__device__ R4_CALL_ATTR uint32_t step4_call_inl(const Env* Ep, uint64_t policy_seed, uint32_t flags, uint32_t g_base, uint32_t g_end, uint32_t load,
-                                                uint64_t gs_row, uint32_t quad, uint32_t left, uint32_t final_chunk) {
+__device__ __forceinline__ uint32_t step4_call_inl(const Env* Ep, uint64_t policy_seed, uint32_t flags, uint32_t g_base, uint32_t g_end, uint32_t load,
+                                                   uint64_t gs_row, uint32_t quad, uint32_t left, uint32_t final_chunk) {
     Quad4Shared& sh = g_q4;
-#if RMJ_INLINE_STEP
     // laundered as SCALAR registers (a vector-register launder made the Env pointer live in - and spill from - VGPRs: a scratch reload at
     // every event emission); readfirstlane first, so that the operands are scalar wherever this body is compiled
     Ep = uni_ptr(Ep); policy_seed = uni(policy_seed); flags = uni(flags); g_base = uni(g_base); g_end = uni(g_end); quad = uni(quad); final_chunk = uni(final_chunk);
     asm volatile("" : "+s"(Ep), "+s"(policy_seed), "+s"(flags), "+s"(g_base), "+s"(g_end), "+s"(quad), "+s"(final_chunk));
-#endif
     return step4_body<true, POL, true>(uni_ptr(Ep), sh, uni(policy_seed), uni(flags), uni(g_base), uni(g_end), uni(load) != 0u, gs_row, nullptr, uni(quad),
                                        left, uni(final_chunk) != 0u);
 }
-// the steps [0, steps) of a quad's rollout / ticket: the RandomAgent answers claims inline (rows run ahead of each other by a step or
-// two and wait at the end), the greedy policy steps all rows in lock-step
+// the steps [0, steps) of a quad's rollout / ticket: both policies answer claims inline (rows run ahead of each other by a step or
+// two and wait at the end)
 // max_calls: the ticket ends after that many calls of the step function even if rows have steps left (k_step4_queue: a ticket is a
 // number of CALLS, the rows carry what is left of their rollout to the quad's next ticket - no row idles at the end of a ticket while
 // the others catch up); the result = the row's steps still to take.
 template <int POL>
 __device__ __forceinline__ uint32_t step4_run(const Env* Ep, uint64_t policy_seed, uint32_t flags, uint32_t g_base, uint32_t g_end, uint64_t gs_row,
                                               uint32_t quad, uint32_t steps, bool final_chunk, uint32_t g_row, uint32_t max_calls = 0xFFFFFFFFu) {
-    if (RMJ_INLINE_RESP & (POL == 0 ? 1 : 2)) {
-        uint32_t left = g_row < g_end ? steps : 0u, load = 1u;
+    uint32_t left = g_row < g_end ? steps : 0u, load = 1u;
 #ifdef RMJ_QTL
-        if ((threadIdx.x & 63u) == 0u) { g_qtl_cnt[0] = 0u; g_qtl_cnt[1] = 0u; }
+    if ((threadIdx.x & 63u) == 0u) { g_qtl_cnt[0] = 0u; g_qtl_cnt[1] = 0u; }
 #endif
 #pragma unroll 1
-        while (__ballot(left != 0u) && max_calls-- != 0u) {
+    while (__ballot(left != 0u) && max_calls-- != 0u) {
 #ifdef RMJ_QTL
-            { const uint64_t lv = __ballot(left != 0u && (threadIdx.x & 15u) == 0u); if ((threadIdx.x & 63u) == 0u) { g_qtl_cnt[0] += 1u; g_qtl_cnt[1] += (uint32_t)__popcll(lv); } }
+        { const uint64_t lv = __ballot(left != 0u && (threadIdx.x & 15u) == 0u); if ((threadIdx.x & 63u) == 0u) { g_qtl_cnt[0] += 1u; g_qtl_cnt[1] += (uint32_t)__popcll(lv); } }
 #endif
-            const uint32_t ret = step4_call_inl<POL>(Ep, policy_seed, flags, g_base, g_end, load, gs_row, quad, left, final_chunk ? 1u : 0u);
-            left -= ret & 0xFFu;
-            load = 0u;
-            if (RMJ_ROW_ROUND_END && __ballot((ret & R4_RET_ROUND) != 0u)) step4_finish_rounds<true, POL>(Ep, flags, g_base, g_end, quad);   // (wave-uniform bit)
-        }
-        return left;
-    } else {
-        const uint32_t n = steps < max_calls ? steps : max_calls;   // (lock-step: every call is one step of every row)
-#pragma unroll 1
-        for (uint32_t it = 0; it < n; it++) {
-            const uint32_t fl = flags | ((final_chunk && it + 1u == steps) ? STEP_F_ALLROWS : STEP_F_QUIET);
-            const uint32_t ret = step4_call<true, POL>(Ep, policy_seed, fl, g_base, g_end, it == 0 ? 1u : 0u, gs_row, quad);
-            if (RMJ_ROW_ROUND_END && __ballot((ret & R4_RET_ROUND) != 0u)) step4_finish_rounds<true, POL>(Ep, fl, g_base, g_end, quad);
-        }
-        return g_row < g_end ? steps - n : 0u;
+        const uint32_t ret = step4_call_inl<POL>(Ep, policy_seed, flags, g_base, g_end, load, gs_row, quad, left, final_chunk ? 1u : 0u);
+        left -= ret & 0xFFu;
+        load = 0u;
+        if (__ballot((ret & R4_RET_ROUND) != 0u)) step4_finish_rounds<true, POL>(Ep, flags, g_base, g_end, quad);   // (wave-uniform bit)
     }
+    return left;
 }
-#ifndef RMJ_STEP4_WAVES
 #define RMJ_STEP4_WAVES 6
-#endif
 // The greedy policy's fused rollouts at five waves per SIMD (96 VGPR): 49 instead of 59 vector registers spilled in the ticket kernel, +4.5 % (931-941 ->
 // 977-979 M env.step/s); the RandomAgent's rollouts lose 10 % at five (1 890 -> 1 700 M) and stay at six.
-#ifndef RMJ_STEP4_WAVES_GREEDY
 #define RMJ_STEP4_WAVES_GREEDY 5
-#endif
 #define RMJ_STEP4_WAVES_OF(POL) ((POL) == 1 ? RMJ_STEP4_WAVES_GREEDY : RMJ_STEP4_WAVES)
 // LOOP = false: one step per launch.  LOOP = true: games are independent, so a device-policy rollout needs no
 // synchronisation between the steps of DIFFERENT games: the wave keeps its four records in LDS and steps its own games
@@ -2919,11 +2840,8 @@ __device__ __forceinline__ uint32_t step4_run(const Env* Ep, uint64_t policy_see
 // listed units; the blocks behind them serve the others in place and leave at once where a front block has been.  Hints only: the two
 // arrays are written by one launch and read by the next, so every unit is served exactly once whatever happened in between.
 // (struct HeavyOrder: rmj_common.hip.h)
-#ifndef RMJ_DEBUG_STEP_WAVES
-#define RMJ_DEBUG_STEP_WAVES RMJ_STEP4_WAVES
-#endif
 template <bool LOOP, int POL>
-__global__ __launch_bounds__(64, (LOOP && POL == 1) ? RMJ_STEP4_WAVES_GREEDY : RMJ_DEBUG_STEP_WAVES) void k_step4(const Env* __restrict__ Ep, uint64_t policy_seed, uint32_t flags, uint32_t g_base,
+__global__ __launch_bounds__(64, (LOOP && POL == 1) ? RMJ_STEP4_WAVES_GREEDY : RMJ_STEP4_WAVES) void k_step4(const Env* __restrict__ Ep, uint64_t policy_seed, uint32_t flags, uint32_t g_base,
                                                                    uint32_t g_end, uint32_t n_steps, const uint64_t* __restrict__ actions, HeavyOrder ho) {
     if (LOOP) {
         const uint32_t row_ = (threadIdx.x & 63u) >> 4;
@@ -2952,7 +2870,7 @@ __global__ __launch_bounds__(64, (LOOP && POL == 1) ? RMJ_STEP4_WAVES_GREEDY : R
         if (__ballot((ret & R4_RET_ROUND) != 0u) && (threadIdx.x & 63) == 0)   // ... and why (bit R4_RE_* per row)
             rmj::g_tl4[(size_t)blockIdx.x * RMJ_TL4_ROW + 14] = (1ull << g_q4.rmode[0]) | (1ull << g_q4.rmode[1]) | (1ull << g_q4.rmode[2]) | (1ull << g_q4.rmode[3]);
 #endif
-        if (RMJ_ROW_ROUND_END && __ballot((ret & R4_RET_ROUND) != 0u)) step4_finish_rounds<false, POL>(Ep, flags, g_base, g_end, unit);
+        if (__ballot((ret & R4_RET_ROUND) != 0u)) step4_finish_rounds<false, POL>(Ep, flags, g_base, g_end, unit);
         if (ho.out_cnt) {   // the note for the next launch
             const int row = (threadIdx.x & 63) >> 4;
             const GState& S = sh.st[row];
@@ -2963,7 +2881,7 @@ __global__ __launch_bounds__(64, (LOOP && POL == 1) ? RMJ_STEP4_WAVES_GREEDY : R
             const PState& Pw = S.p[threadIdx.x & 3];
             // (a seat whose cache is stale - it has just discarded from its hand or called - stays unpredicted: 2-6 waves per launch.  Its old
             //  shanten bound is no predictor: "sh13 <= 1" holds for most hands - the list then takes an atomic from nearly every wave, 163 us per launch)
-            const bool waits_open = RMJ_HEAVY_TENPAI && (threadIdx.x & 15) < 4 && (Pw.flags & PF_WAITS_VALID) && Pw.waits13 != 0ull && !(Pw.flags & PF_RIICHI_DECLARED);
+            const bool waits_open = (threadIdx.x & 15) < 4 && (Pw.flags & PF_WAITS_VALID) && Pw.waits13 != 0ull && !(Pw.flags & PF_RIICHI_DECLARED);
             const bool hv = (uint32_t)row < r4_rows(flags) && gq < g_end &&
                             (S.is_done ? (flags & STEP_F_AUTORESET) != 0u : ((S.phase == RMJ_WAIT_ACT && S.drawable_count == 0) || S.ron_offer_mask != 0 || waits_open));
             const bool any = __ballot(hv) != 0ull;
@@ -3053,9 +2971,6 @@ __global__ __launch_bounds__(64, RMJ_STEP4_WAVES_OF(POL)) void k_step4_queue(con
 #endif
         const uint32_t c = t / mine, quad = (t - c * mine) * 8u + xcd;
         if (c > 0u && (q_wait_for(done + quad, c) & RMJ_Q_FIN)) continue;   // the quad's previous ticket (handed out `mine` tickets ago) must have ended; nothing left: an empty ticket
-#ifdef RMJ_Q_ACQ   /* (A/B only, profiles/r05_ticket_acquire_ab.txt: the agent-scope acquire = an L1 invalidate per pick-up, as in rounds 2-4) */
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#endif
 #ifdef RMJ_QTL
         const unsigned long long qt1 = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -3118,29 +3033,20 @@ __global__ __launch_bounds__(64, RMJ_STEP4_WAVES_OF(POL)) void k_step4_fixup(con
 // SIMD: the encoder wants 85-96 registers.
 // (six waves per SIMD since the value table shrank to 64 entries - 6 512 B of LDS per wave, 80 VGPR without a spill: trainer loop +1.5 %, the 3P
 //  step + encode rollout the same: profiles/r05_enc_waves_ab.txt.  The launch is bound by its LDS and vector instruction streams together, not by occupancy.)
-#ifndef RMJ_STEP4_ENC_WAVES
 #define RMJ_STEP4_ENC_WAVES 6
-#endif
-#ifndef RMJ_INLINE_ENC
-#define RMJ_INLINE_ENC 0     /* experiment: step + encode inlined into the rollout loops of k_step4_enc / k_step4_queue_enc (see step4_call_inl) */
-#endif
 template <bool LOOP, int POL>
 __device__ __forceinline__ void step4_enc_impl(const Env* Ep, uint64_t policy_seed, uint32_t flags, uint32_t g_base, uint32_t g_end, uint32_t load,
                                                uint64_t gs_row, uint32_t quad, float* out, const uint64_t* actions = nullptr) {
     Quad4Shared& sh = g_q4;
     __shared__ float lut[ENC_LUT];
     constexpr int W = KSANMA ? ENC_W3 : ENC_W4;
-    int lane_ = threadIdx.x & 63;
-#if RMJ_INLINE_ENC
-    if constexpr (LOOP) asm volatile("" : "+v"(lane_));
-#endif
-    const int lane = lane_;
+    const int lane = threadIdx.x & 63;
     g_base = uni(g_base); g_end = uni(g_end); quad = uni(quad);
     out = uni_ptr(out);
     if (uni(load) != 0u) enc_lut_init(lut, lane);
     {
         const uint32_t ret = step4_body<LOOP, POL>(uni_ptr(Ep), sh, uni(policy_seed), uni(flags), g_base, g_end, uni(load) != 0u, gs_row, LOOP ? nullptr : uni_ptr(actions), quad);
-        if (RMJ_ROW_ROUND_END && __ballot((ret & R4_RET_ROUND) != 0u)) step4_finish_rounds<LOOP, POL>(uni_ptr(Ep), uni(flags), g_base, g_end, quad);
+        if (__ballot((ret & R4_RET_ROUND) != 0u)) step4_finish_rounds<LOOP, POL>(uni_ptr(Ep), uni(flags), g_base, g_end, quad);
     }
     wave_sync();
     const uint32_t g0 = g_base + (quad == 0xFFFFFFFFu ? blockIdx.x : quad) * 4u;
@@ -3162,23 +3068,13 @@ __device__ __forceinline__ void step4_enc_impl(const Env* Ep, uint64_t policy_se
         }
     }
 }
+// The step + encode out of line: what every kernel below calls.  (Inlined into the rollout loops, with the loop-invariant inputs laundered per
+// iteration as in step4_call_inl, the launch is store bound all the same: +1 % for 77 SGPR / 24 VGPR spills, journal r05 - not adopted.)
+// A wrapper around step4_enc_impl rather than one function: the code object names this symbol and the body's static `lut`.
 template <bool LOOP, int POL>
 __device__ __noinline__ void step4_call_enc_ool(const Env* Ep, uint64_t policy_seed, uint32_t flags, uint32_t g_base, uint32_t g_end, uint32_t load,
                                                 uint64_t gs_row, uint32_t quad, float* out, const uint64_t* actions = nullptr) {
     step4_enc_impl<LOOP, POL>(Ep, policy_seed, flags, g_base, g_end, load, gs_row, quad, out, actions);
-}
-// what the rollout loops call: out of line (rounds 2-4), or - RMJ_INLINE_ENC - inlined with the loop-invariant inputs laundered per iteration
-template <bool LOOP, int POL>
-__device__ __forceinline__ void step4_call_enc(const Env* Ep, uint64_t policy_seed, uint32_t flags, uint32_t g_base, uint32_t g_end, uint32_t load,
-                                               uint64_t gs_row, uint32_t quad, float* out, const uint64_t* actions = nullptr) {
-#if RMJ_INLINE_ENC
-    if constexpr (LOOP) {
-        asm volatile("" : "+v"(Ep), "+v"(policy_seed), "+v"(g_base), "+v"(g_end), "+v"(quad), "+v"(out));
-        step4_enc_impl<LOOP, POL>(Ep, policy_seed, flags, g_base, g_end, load, gs_row, quad, out, actions);
-        return;
-    }
-#endif
-    step4_call_enc_ool<LOOP, POL>(Ep, policy_seed, flags, g_base, g_end, load, gs_row, quad, out, actions);
 }
 template <int POL>
 __global__ __launch_bounds__(64, RMJ_STEP4_ENC_WAVES) void k_step4_enc(const Env* __restrict__ Ep, uint64_t policy_seed, uint32_t flags, uint32_t g_base,
@@ -3187,43 +3083,14 @@ __global__ __launch_bounds__(64, RMJ_STEP4_ENC_WAVES) void k_step4_enc(const Env
     const uint64_t gs_row = sm64(policy_seed + ((CEnv*)Ep)->game_offset + (uint64_t)g);
 #pragma unroll 1
     for (uint32_t it = 0; it < n_steps; it++)
-        step4_call_enc<true, POL>(Ep, policy_seed, flags | (it + 1u < n_steps ? STEP_F_QUIET : STEP_F_ALLROWS), g_base, g_end, it == 0 ? 1u : 0u, gs_row, 0xFFFFFFFFu, out);
+        step4_call_enc_ool<true, POL>(Ep, policy_seed, flags | (it + 1u < n_steps ? STEP_F_QUIET : STEP_F_ALLROWS), g_base, g_end, it == 0 ? 1u : 0u, gs_row, 0xFFFFFFFFu, out);
 }
 // One step driven by the caller's action ids / packed actions + the rows of the seats that are to act next: what a trainer loop
 // issues per iteration (rmj_step_ids_encode_device) - one launch instead of a step launch and an encoder launch, the encoder's
 // stores under the tail of the step (the last third of a per-step launch belongs to the few waves that carry a full-path game).
 __global__ __launch_bounds__(64, RMJ_STEP4_ENC_WAVES) void k_step4_act_enc(const Env* __restrict__ Ep, uint32_t flags, uint32_t g_base, uint32_t g_end,
                                                                                const uint64_t* __restrict__ actions, float* __restrict__ out) {
-#ifdef RMJ_DEBUG_LDS_FILL   /* debugging aid: what does the kernel read of LDS it has not written? */
-    for (int i = threadIdx.x & 63; i < (int)(sizeof(Quad4Shared) / 4); i += 64) reinterpret_cast<uint32_t*>(&g_q4)[i] = RMJ_DEBUG_LDS_FILL;
-    wave_sync();
-#endif
-#ifdef RMJ_ACT_ENC_STAGGER   /* experiment: every other wave starts late - do the waves of a generation run their step and store phases in lock-step? */
-    if (blockIdx.x & 1u)
-        for (int k = 0; k < RMJ_ACT_ENC_STAGGER; k++) __builtin_amdgcn_s_sleep(127);
-#endif
-#ifdef RMJ_DEBUG_PAD_VGPR   /* debugging aid (round 6, journal r06 section 1): -DRMJ_DEBUG_PAD_VGPR=95 makes the kernel NAME v95, so its waves are allocated 96 vector registers while the out-of-line step compiles to the same instructions as without it */
-#define RMJ_STR2(x) #x
-#define RMJ_STR(x) RMJ_STR2(x)
-    asm volatile("v_mov_b32 v" RMJ_STR(RMJ_DEBUG_PAD_VGPR) ", 0" ::: "v" RMJ_STR(RMJ_DEBUG_PAD_VGPR));
-#endif
-#ifdef RMJ_DEBUG_HWID   /* debugging aid (round 6, scripts/debug_scratch_poison.py --hwid; value = blocks recorded): where and when every wave of the launch ran - taken around the call, the out-of-line function itself is untouched */
-    const unsigned long long hw_t0 = __builtin_amdgcn_s_memrealtime();
-#endif
-#ifdef RMJ_DEBUG_ACT_ENC_INLINE
-    step4_enc_impl<false, 0>(Ep, 0ull, flags, g_base, g_end, 1u, 0ull, 0xFFFFFFFFu, out, actions);
-#else
-    step4_call_enc<false, 0>(Ep, 0ull, flags, g_base, g_end, 1u, 0ull, 0xFFFFFFFFu, out, actions);
-#endif
-#ifdef RMJ_DEBUG_HWID
-    if ((threadIdx.x & 63) == 0 && blockIdx.x < RMJ_DEBUG_HWID) {
-        unsigned long long* o = rmj::g_dbg_hwid + (size_t)blockIdx.x * 4;
-        o[0] = hw_t0;
-        o[1] = __builtin_amdgcn_s_memrealtime();
-        o[2] = (unsigned long long)(uint32_t)__builtin_amdgcn_s_getreg((31 << 11) | 4) | ((unsigned long long)(uint32_t)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32);   // HW_ID | XCC_ID
-        o[3] = (unsigned long long)(uint32_t)__builtin_amdgcn_s_getreg((31 << 11) | 5) | ((unsigned long long)(uint32_t)__builtin_amdgcn_s_getreg((31 << 11) | 6) << 32);    // GPR_ALLOC | LDS_ALLOC
-    }
-#endif
+    step4_call_enc_ool<false, 0>(Ep, 0ull, flags, g_base, g_end, 1u, 0ull, 0xFFFFFFFFu, out, actions);
 }
 // ... with the policy's draw in front (rmj_step_sample_encode_device): the wave samples one id per acting seat of its own four games from the
 // caller's logits (sample_ids_row: the keyed Gumbel draw of k_sample_ids, the same ids), hands them to the caller (d_ids) and steps under
@@ -3239,7 +3106,7 @@ __global__ __launch_bounds__(64, RMJ_STEP4_ENC_WAVES) void k_step4_sample_enc(co
         const int32_t res = sample_ids_row(E.status, E.core, E.nlegal, E.mask, E.game_offset, (int)E.game_mode, g, in, logits, stride, seed, lane);
         if (in && (lane & 15) < 4) ids[(size_t)g * 4 + (lane & 15)] = res;
     }
-    step4_call_enc<false, 0>(Ep, 0ull, flags, g_base, g_end, 1u, 0ull, 0xFFFFFFFFu, out, reinterpret_cast<const uint64_t*>(ids));
+    step4_call_enc_ool<false, 0>(Ep, 0ull, flags, g_base, g_end, 1u, 0ull, 0xFFFFFFFFu, out, reinterpret_cast<const uint64_t*>(ids));
 }
 // the same as tickets (see k_step4_queue): a quad's chunks - its records, lists and tensor rows - stay on one XCD
 template <int POL>
@@ -3266,7 +3133,7 @@ __global__ __launch_bounds__(64, RMJ_STEP4_ENC_WAVES) void k_step4_queue_enc(con
         const bool last_chunk = c + 1u == n_chunks;
 #pragma unroll 1
         for (uint32_t it = 0; it < steps; it++)
-            step4_call_enc<true, POL>(Ep, policy_seed, flags | ((last_chunk && it + 1u == steps) ? STEP_F_ALLROWS : STEP_F_QUIET), 0u, n_games, it == 0 ? 1u : 0u, gs_row, quad, out);
+            step4_call_enc_ool<true, POL>(Ep, policy_seed, flags | ((last_chunk && it + 1u == steps) ? STEP_F_ALLROWS : STEP_F_QUIET), 0u, n_games, it == 0 ? 1u : 0u, gs_row, quad, out);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         wave_sync();
         if (lane == 0u) __hip_atomic_store(done + quad, c + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -3280,7 +3147,7 @@ __global__ __launch_bounds__(64, RMJ_STEP4_ENC_WAVES) void k_step4_fixup_enc(con
     const uint64_t gs_row = sm64(policy_seed + ((CEnv*)Ep)->game_offset + (uint64_t)g);
 #pragma unroll 1
     for (uint32_t it = 0; it < n_steps; it++)
-        step4_call_enc<true, POL>(Ep, policy_seed, flags | (it + 1u < n_steps ? STEP_F_QUIET : STEP_F_ALLROWS), 0u, n_games, it == 0 ? 1u : 0u, gs_row, 0xFFFFFFFFu, out);
+        step4_call_enc_ool<true, POL>(Ep, policy_seed, flags | (it + 1u < n_steps ? STEP_F_QUIET : STEP_F_ALLROWS), 0u, n_games, it == 0 ? 1u : 0u, gs_row, 0xFFFFFFFFu, out);
 }
 
 }  // namespace RMJ_NS
