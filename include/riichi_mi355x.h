@@ -601,6 +601,120 @@ int rmj_ppo_counts(rmj_ppo_handle p, RmjPpoCounts* out);
 /* Empties the pool and forgets the open trajectories (a new collect_episodes call). */
 int rmj_ppo_clear(rmj_ppo_handle p);
 
+/* ------------------------------------------------------------------ log sample builder
+ * What riichienv-ml's MCDataset yields from MJAI logs (datasets/mjai_logs.py:62-129) - per decision of every seat the feature row, the
+ * action id, the decayed return G_t = reward x gamma ** (T - t - 1), the action mask and the seat's rank in the kyoku's end scores -
+ * built on the device: M logs are replayed in lock-step in the n <= M games of a handle, with no host work per event and no host
+ * synchronisation inside the replay.
+ *
+ * A log set is the logs' events as ONE resident array of records, events[total][3] as rmj_apply_events takes them (the host packs
+ * every MJAI event once; riichienv_amd/abi.py event_records_from_mjai), with offsets[n_logs + 1] = the first event of every log.  A
+ * kyoku of a log is numbered by the start_kyoku events of the log so far (the first kyoku is 1); its row in the per-kyoku tables
+ * (reward, end scores) is kyoku_offsets[log] + kyoku - 1, kyoku_offsets [n_logs + 1] from the info call (NULL: not wanted). */
+typedef struct rmj_logset* rmj_logset_handle;
+typedef struct RmjLogsetInfo {
+    uint32_t n_logs, n_events, n_kyokus, longest_log;
+} RmjLogsetInfo;
+int rmj_logset_create(int device, const RmjEvent* events /*[total][3]*/, const uint32_t* offsets /*[n_logs + 1]*/, uint32_t n_logs, rmj_logset_handle* out);
+int rmj_logset_destroy(rmj_logset_handle s);
+int rmj_logset_info(rmj_logset_handle s, RmjLogsetInfo* out, uint32_t* kyoku_offsets /*[n_logs + 1]*/);
+/* Which slot replays which logs (host only, no device needed): the logs are handed out in log order, each to the slot that is free
+ * first when every event takes one step, ties to the lowest slot - a pure function of (n_logs, n_slots, the logs' lengths), so the
+ * order of the samples is the same run after run.  slot_of_log [n_logs]; slot s replays slot_logs[slot_first[s] .. slot_first[s + 1])
+ * in that order (slot_logs [n_logs], slot_first [n_slots + 1]); *steps = the events of the busiest slot = the steps of a whole replay.
+ * Any output may be NULL.  RMJ_ERR_ARG unless 1 <= n_slots <= n_logs (or both are 0). */
+int rmj_logreplay_assign(const uint32_t* offsets, uint32_t n_logs, uint32_t n_slots, uint32_t* slot_of_log, uint32_t* slot_logs, uint32_t* slot_first,
+                         uint32_t* steps);
+#define RMJ_LOGREPLAY_INCLUDE_PASS 1u        /* the Pass of every seat that was offered a claim and let it go is a sample */
+#define RMJ_LOGREPLAY_SKIP_SINGLE_ACTION 2u  /* a decision over a list of at most one action is no sample (LogKyoku.steps' default) */
+typedef struct RmjLogReplayConfig {
+    int32_t features;           /* RMJ_FEATURES_*: the rows the pool stores */
+    uint32_t capacity;          /* samples: capacity x (C x W x 4 + A + 52) bytes of device memory */
+    uint32_t flags;             /* RMJ_LOGREPLAY_* */
+    uint32_t n_powers;
+    double gamma;
+    const double* gamma_powers; /* host array [n_powers], P[k] = gamma ** k as the trainer's own arithmetic gives it (Python: gamma ** k), at
+                                   least longest_log + 1 entries: a return is ONE float64 product reward x P[T - t - 1], so it has the
+                                   dataset's bits without a device pow.  NULL: the library fills the table with pow(gamma, k). */
+} RmjLogReplayConfig;
+typedef struct rmj_logreplay* rmj_logreplay_handle;
+/* The handle's games are the slots (n_slots = n_games <= n_logs, else RMJ_ERR_ARG; so are a zero capacity, an unknown feature set or
+ * flag, DISCARD_SHANTEN in 3P).  The handle should be used for nothing else while a replay is under way: start_kyoku events rewrite
+ * its games.  The builder lives until its destroy call or the handle's rmj_destroy; the log set must outlive it. */
+int rmj_logreplay_create(rmj_handle h, rmj_logset_handle set, const RmjLogReplayConfig* cfg, rmj_logreplay_handle* out);
+int rmj_logreplay_destroy(rmj_logreplay_handle r);
+/* n_steps steps of the replay (0 = to the end), asynchronous on the handle's stream; *steps_left (may be NULL) = what remains.  A step
+ * takes the next event of every slot's log: the decisions it stands for are matched on the device against the published legal lists
+ * (Observation.select_action_from_mjai, observation/mjai_select.rs:88-194: the first match in list order; the tsumogiri / drawn-tile
+ * rule of a dahai; consumed tiles compared as a multiset of MJAI names, so red fives are distinct; hora = Tsumo or Ron; ryukyoku =
+ * KyushuKyuhai), together with what the reference's log walker yields without a direct match - the Pass decisions (flag), the Ron on
+ * a robbed kakan / ankan, which the published lists do not hold (replay/mod.rs:483-527) - and every sample is written to the pool:
+ * feature row, mask, action id, packed action, (log, kyoku, seat, t) with t the position in the seat's trajectory of that kyoku.
+ * Then the event is applied with RMJ_EVF_REPLAY_PASS.  Pool slots are handed out in (step, slot, decision) order, passes first, highest
+ * seat first (LogKyoku.steps' order).  When the pool is full nothing is written: the sample is counted as overflowed and its
+ * trajectory marked broken.  A log in which a decision event finds no match in the list its actor is offered is marked failed (a
+ * status word, no trap) and left at once; its slot goes on with its next log (mjai_logs.py:119-122 drops such a file whole).
+ * NOT detected: an event that does not fit the state in any other way (a decision event by a seat that is not to act, a tsumo out of
+ * turn, a meld from tiles the hand does not hold when no list is offered).  The event handler reports no error, like the reference's
+ * apply_mjai_event; such an event is applied as rmj_apply_events applies it and the log counts as complete.
+ * The records carry less than the MJAI text, and matching follows the records: a dahai without a tsumogiri field reads as
+ * tsumogiri = false (select_action_from_mjai skips the drawn-tile rule when the field is absent: on such third-party logs the twin
+ * of the same name may be picked), a kakan is matched by its tile name without its consumed tiles, and the seat a robbed kan is
+ * taken from is the log's previous actor, not the hora's target field.  On logs that a game produced these agree. */
+int rmj_logreplay_run_device(rmj_logreplay_handle r, uint32_t n_steps, uint32_t* steps_left);
+/* Returns and ranks of the samples in the pool: d_reward [n_kyokus][4] f64 = the reward of (kyoku row, seat) - where
+ * RewardPredictor.calc_all_player_rewards plugs in - and d_end_scores [n_kyokus][4] i32 = the kyoku's end scores; return64 = reward x
+ * P[T - t - 1] (T = the samples of the trajectory), `ret` = that rounded to f32, rank = the seat's place in a stable descending sort
+ * of the end scores (mjai_logs.py:14-17: ties to the lower seat). */
+int rmj_logreplay_finalize_device(rmj_logreplay_handle r, const double* d_reward, const int32_t* d_end_scores);
+/* The samples of the logs that were replayed to their end, minus the trajectories that lost a sample to a full pool, in pool order,
+ * into the caller's device arrays of `rows` rows.  d_count [2] u32: [0] the samples that qualify (when above `rows` only the first
+ * `rows` were written), [1] the pool slots left out (failed or unfinished logs, broken trajectories). */
+typedef struct RmjLogBatch {
+    float* d_features;    /* [rows][C][W] */
+    uint8_t* d_mask;      /* [rows][A] */
+    int64_t* d_action;    /* action id */
+    uint64_t* d_packed;   /* packed action */
+    float* d_return;
+    double* d_return64;
+    int64_t* d_rank;
+    int32_t *d_log, *d_kyoku, *d_seat, *d_t;
+    uint32_t* d_count;    /* [2] */
+    uint32_t rows, reserved;
+} RmjLogBatch;
+int rmj_logreplay_emit_device(rmj_logreplay_handle r, const RmjLogBatch* out);
+/* The pool itself, without a copy (slot s < fill).  row_stride: floats from one feature row to the next; steps: the steps of a whole
+ * replay.  log_status [n_logs] u8: 0 not finished, 1 replayed to its end, 2 failed; traj_len / traj_broken [n_kyokus][4]; counters:
+ * device u32 [6] = fill, overflowed, failed logs, (internal), decisions, events applied. */
+typedef struct RmjLogReplayViews {
+    uint32_t capacity, row_stride, action_space, steps;
+    const float* features;
+    const uint8_t* mask;
+    const int32_t* action;
+    const uint64_t* packed;
+    const float* ret;
+    const double* ret64;
+    const int32_t *rank, *log, *kyoku, *seat, *t;
+    const uint8_t* log_status;
+    const uint32_t* traj_len;
+    const uint8_t* traj_broken;
+    const uint32_t* counters;
+} RmjLogReplayViews;
+int rmj_logreplay_views(rmj_logreplay_handle r, RmjLogReplayViews* out);
+/* Waits for the handle's stream. */
+typedef struct RmjLogReplayCounts {
+    uint32_t fill;           /* pool slots in use */
+    uint32_t overflowed;     /* samples that found no slot */
+    uint32_t failed_logs;
+    uint32_t complete_logs;
+    uint32_t decisions;      /* samples matched (fill + overflowed) */
+    uint32_t events;         /* events taken from the stream */
+    uint32_t steps_done, steps_left;
+} RmjLogReplayCounts;
+int rmj_logreplay_counts(rmj_logreplay_handle r, RmjLogReplayCounts* out);
+/* Empties the pool and rewinds every slot to its first log (the handle's games are rewritten by the logs' own start events). */
+int rmj_logreplay_clear(rmj_logreplay_handle r);
+
 /* Round boundaries and per-round score deltas for a trainer on the same GPU (what riichienv-ml's PPO worker computes on the host
  * between steps: trainers/_ppo_worker.py:100-116 GRP features, :240-266 the reward at a kyoku boundary, :283-291 rank rewards).
  * Call after every step (asynchronous on the handle's stream): d_ended [n] u8 = 0 the round goes on, 1 a round ended in this step and

@@ -257,6 +257,33 @@ class PpoCounts(C.Structure):   # RmjPpoCounts
     _fields_ = [(k, C.c_uint32) for k in ("fill", "valid", "dropped", "overflowed", "segments", "open")]
 
 
+class LogsetInfo(C.Structure):       # RmjLogsetInfo
+    _fields_ = [(k, C.c_uint32) for k in ("n_logs", "n_events", "n_kyokus", "longest_log")]
+
+
+LOGREPLAY_INCLUDE_PASS, LOGREPLAY_SKIP_SINGLE_ACTION = 1, 2   # RMJ_LOGREPLAY_*
+
+
+class LogReplayConfig(C.Structure):  # RmjLogReplayConfig
+    _fields_ = [("features", C.c_int32), ("capacity", C.c_uint32), ("flags", C.c_uint32), ("n_powers", C.c_uint32), ("gamma", C.c_double),
+                ("gamma_powers", C.c_void_p)]
+
+
+class LogBatch(C.Structure):         # RmjLogBatch (rmj_logreplay_emit_device)
+    _fields_ = [(k, C.c_void_p) for k in ("features", "mask", "action", "packed", "ret", "ret64", "rank", "log", "kyoku", "seat", "t", "count")] + [
+        ("rows", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class LogReplayViews(C.Structure):   # RmjLogReplayViews
+    _fields_ = [(k, C.c_uint32) for k in ("capacity", "row_stride", "action_space", "steps")] + [
+        (k, C.c_void_p) for k in ("features", "mask", "action", "packed", "ret", "ret64", "rank", "log", "kyoku", "seat", "t", "log_status", "traj_len",
+                                  "traj_broken", "counters")]
+
+
+class LogReplayCounts(C.Structure):  # RmjLogReplayCounts
+    _fields_ = [(k, C.c_uint32) for k in ("fill", "overflowed", "failed_logs", "complete_logs", "decisions", "events", "steps_done", "steps_left")]
+
+
 class BenchResult(C.Structure):
     _fields_ = [("total_ms", C.c_double), ("step_kernel_ms", C.c_double), ("env_steps", C.c_uint64),
                 ("launches", C.c_uint32), ("launches_in_flight", C.c_uint32), ("full_path_steps", C.c_uint64),

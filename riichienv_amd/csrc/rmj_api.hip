@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -773,11 +774,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RMJ_ENCX_WAV
 // and its occupancy cap: the extended rows wait on the ukeire walk, and a wave per seat keeps the two or three claimants of a discard
 // in parallel.  A seat that does not act leaves on the 4-byte status word.  The compact slot is k_obs_offsets' offset of the game,
 // plus the totals of the scan blocks before it, plus the acting seats of the game below this one.
-template <bool SANMA, int FEAT, bool COMPACT>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RMJ_ENCX_WAVES, RMJ_ENCX_WAVES))) void k_encode_batch(Env E, const float* __restrict__ decay, float* __restrict__ out, uint32_t RS,
-                                                                  const uint32_t* __restrict__ offs, const uint32_t* __restrict__ totals,
-                                                                  int32_t* __restrict__ index, uint32_t capacity, uint32_t* __restrict__ count) {
-    constexpr int W = SANMA ? ENC_W3 : ENC_W4, NPP = SANMA ? 3 : 4;
+// one row of a feature set: seat `seat` of game `g` into dst (4-byte aligned), by one wave that is a block of its own (the staging areas are the block's LDS)
+template <bool SANMA, int FEAT>
+__device__ __forceinline__ void encode_batch_row(const Env& E, uint32_t g, int seat, const float* __restrict__ decay, float* __restrict__ dst, int lane) {
+    constexpr int W = SANMA ? ENC_W3 : ENC_W4;
     constexpr bool EXT = FEAT == RMJ_FEATURES_EXTENDED;
     constexpr int SLOTS = EXT ? ENC_EXT_C_SLOTS : ENC_CH;
     __shared__ GState st;
@@ -786,25 +786,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RMJ_ENCX_WAV
     __shared__ float tab[ENC_EXT_B_SLOTS];
     __shared__ float col4[4 * W];
     __shared__ uint32_t hist[ENC_HIST_WORDS];
-    const int lane = threadIdx.x & 63;
-    const uint32_t g = blockIdx.x >> 2;
-    const int seat = blockIdx.x & 3;
-    if (COMPACT && blockIdx.x == 0) {   // the size of the batch: all block totals
-        const uint32_t all = obs_block_prefix(totals, (E.n_games + OBS_SCAN_BLOCK - 1) / OBS_SCAN_BLOCK, lane);
-        if (lane == 0) *count = all;
-    }
-    const uint32_t stw = E.status[g];
-    const uint32_t am = ((stw >> 16) & 0xFFu) ? 0u : (stw & 0xFu);   // the seats k_obs_offsets counts
-    if (seat >= NPP || !((am >> seat) & 1u)) return;
-    float* dst;
-    if (COMPACT) {
-        const uint32_t slot = offs[g] + obs_block_prefix(totals, g / OBS_SCAN_BLOCK, lane) + (uint32_t)__popc(am & ((1u << seat) - 1u));
-        if (slot >= capacity) return;                  // (the count tells the caller that the buffer was too small)
-        if (lane == 0) index[slot] = (int32_t)(g * 4u + (uint32_t)seat);
-        dst = out + (size_t)slot * RS;
-    } else {
-        dst = out + ((size_t)g * 4 + seat) * RS;
-    }
     if (lane < (int)(sizeof(GState) / 16)) reinterpret_cast<uint4*>(&st)[lane] = reinterpret_cast<const uint4*>(E.core + g)[lane];
     enc_lut_init(lut, lane);
     wave_sync();
@@ -834,6 +815,33 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RMJ_ENCX_WAV
         enc_emit_bytes<W, ENC_EXT_C_SLOTS>(d, cells, lut, lane, head);
     }
 }
+template <bool SANMA, int FEAT, bool COMPACT>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RMJ_ENCX_WAVES, RMJ_ENCX_WAVES))) void k_encode_batch(Env E, const float* __restrict__ decay, float* __restrict__ out, uint32_t RS,
+                                                                  const uint32_t* __restrict__ offs, const uint32_t* __restrict__ totals,
+                                                                  int32_t* __restrict__ index, uint32_t capacity, uint32_t* __restrict__ count) {
+    constexpr int NPP = SANMA ? 3 : 4;
+    const int lane = threadIdx.x & 63;
+    const uint32_t g = blockIdx.x >> 2;
+    const int seat = blockIdx.x & 3;
+    if (COMPACT && blockIdx.x == 0) {   // the size of the batch: all block totals
+        const uint32_t all = obs_block_prefix(totals, (E.n_games + OBS_SCAN_BLOCK - 1) / OBS_SCAN_BLOCK, lane);
+        if (lane == 0) *count = all;
+    }
+    const uint32_t stw = E.status[g];
+    const uint32_t am = ((stw >> 16) & 0xFFu) ? 0u : (stw & 0xFu);   // the seats k_obs_offsets counts
+    if (seat >= NPP || !((am >> seat) & 1u)) return;
+    float* dst;
+    if (COMPACT) {
+        const uint32_t slot = offs[g] + obs_block_prefix(totals, g / OBS_SCAN_BLOCK, lane) + (uint32_t)__popc(am & ((1u << seat) - 1u));
+        if (slot >= capacity) return;                  // (the count tells the caller that the buffer was too small)
+        if (lane == 0) index[slot] = (int32_t)(g * 4u + (uint32_t)seat);
+        dst = out + (size_t)slot * RS;
+    } else {
+        dst = out + ((size_t)g * 4 + seat) * RS;
+    }
+    encode_batch_row<SANMA, FEAT>(E, g, seat, decay, dst, lane);
+}
+#include "rmj_logreplay.hip.h"
 
 // ---- auxiliary encoders (row N3): kawa overview, yaku possibility, furiten-ron possibility ----------------------
 // One wave per game; absolute seat order, public information only (the same for every observing seat).
@@ -1073,6 +1081,7 @@ struct rmj_env {
     uint32_t max_xcc_id = 0;        // largest HW_REG_XCC_ID seen by a probe launch at create: the ticket rollout assumes ids 0..7 (one L2 per queue)
     uint32_t* d_ev_lost = nullptr;  // [n_games] records a game's ring lost to a late drain (rmj_drain_events), cumulative
     std::vector<struct rmj_ppo*> ppo;   // transition collectors bound to this handle (rmj_ppo_create): destroyed with it
+    std::vector<struct rmj_logreplay*> logreplay;   // log sample builders bound to this handle (rmj_logreplay_create): destroyed with it
     void* d_track = nullptr;        // round tracker (rmj_round_track_device): hand index / scores / meta where every game's round began
     // staging of rmj_drain_format's size call (the records sit in h_pin): reused by the call that brings the text buffer
     bool stage_valid = false;
@@ -1157,6 +1166,26 @@ struct rmj_ppo {
     double gamma_lambda = 0.0;   // gamma * lambda as the worker forms it (_ppo_worker.py:322), in double
     void* mem = nullptr;
     PpoPool P{};
+};
+// a set of MJAI logs as one device-resident event stream (rmj_logset_create)
+struct rmj_logset {
+    int device = 0;
+    uint32_t M = 0, total = 0, K = 0, max_len = 0;
+    std::vector<uint32_t> off, koff;   // [M + 1] first event / first kyoku row of every log
+    RmjEvent* d_ev = nullptr;
+    uint32_t *d_off = nullptr, *d_koff = nullptr;
+};
+// a log sample builder bound to a handle and a log set (rmj_logreplay_create): its pool and bookkeeping are one device allocation
+struct rmj_logreplay {
+    rmj_env* env = nullptr;
+    rmj_logset* set = nullptr;
+    RmjLogReplayConfig cfg{};
+    void* mem = nullptr;
+    LogRun R{};
+    double* d_powers = nullptr;
+    uint32_t n_powers = 0;
+    uint32_t steps = 0, step = 0;      // steps of a whole replay (the longest slot's events), steps taken
+    std::vector<uint32_t> slot_first, slot_logs;
 };
 static int shanten_tables_for(int device, ShantenTables* out);
 static void launch_encode_base_range(rmj_env* h, hipStream_t st, int only_active, float* d_out, uint32_t g0, uint32_t g1);
@@ -1293,6 +1322,7 @@ int rmj_destroy(rmj_handle h) {
     hipFree(h->d.waits); hipFree(h->d.status); hipFree(h->d.events); hipFree(h->d.win); hipFree(h->d_actions); hipFree(h->d_counter); hipFree(h->d_obs_offs); hipFree(h->d_env); hipFree(h->d_qheads);   // (d_qdone lives in the same allocation)
     hipFree(h->d_ev_lost); hipFree(h->d_track); hipFree(h->d_heavy);
     while (!h->ppo.empty()) rmj_ppo_destroy(h->ppo.back());
+    while (!h->logreplay.empty()) rmj_logreplay_destroy(h->logreplay.back());
     hipFree(h->d_txt); hipFree(h->d_txt_offs); hipFree(h->d_txt_work);
     if (h->h_txt) hipHostFree(h->h_txt);
     if (h->h_txt_offs) hipHostFree(h->h_txt_offs);
@@ -3248,6 +3278,248 @@ int rmj_ppo_counts(rmj_ppo_handle p, RmjPpoCounts* out) {
     HIPCHK(hipMemcpyAsync(c, p->P.ctr, sizeof(c), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     *out = RmjPpoCounts{c[PPO_C_FILL], c[PPO_C_VALID], c[PPO_C_DROPPED], c[PPO_C_OVERFLOWED], c[PPO_C_SEGMENTS], c[PPO_C_FILL] - c[PPO_C_VALID] - c[PPO_C_DROPPED]};
+    return RMJ_OK;
+}
+
+// ---- log sample builder (rmj_logreplay.hip.h) ------------------------------------------------------------------
+int rmj_logset_create(int device, const RmjEvent* events, const uint32_t* offsets, uint32_t n_logs, rmj_logset_handle* out) {
+    if (!out || !offsets || (!events && offsets[n_logs])) return fail(RMJ_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (offsets[0] != 0u) return fail(RMJ_ERR_ARG, "rmj_logset_create: offsets[0] must be 0");
+    for (uint32_t l = 0; l < n_logs; l++)
+        if (offsets[l + 1] < offsets[l]) return fail(RMJ_ERR_ARG, "rmj_logset_create: offsets must not decrease");
+    int rc = ensure_device(device);
+    if (rc) return rc;
+    rmj_logset* s = new rmj_logset();
+    s->device = device;
+    s->M = n_logs;
+    s->total = offsets[n_logs];
+    s->off.assign(offsets, offsets + n_logs + 1);
+    s->koff.assign(n_logs + 1, 0u);
+    for (uint32_t l = 0; l < n_logs; l++) {
+        uint32_t k = 0;
+        for (uint32_t i = offsets[l]; i < offsets[l + 1]; i++) k += events[(size_t)i * 3].type == RMJ_EV_START_KYOKU ? 1u : 0u;
+        s->koff[l + 1] = s->koff[l] + k;
+        if (offsets[l + 1] - offsets[l] > s->max_len) s->max_len = offsets[l + 1] - offsets[l];
+    }
+    s->K = s->koff[n_logs];
+    const size_t eb = (size_t)(s->total ? s->total : 1u) * 3 * sizeof(RmjEvent), ob = (size_t)(n_logs + 1) * 4;
+    if (hipMalloc(&s->d_ev, eb) != hipSuccess || hipMalloc(&s->d_off, ob) != hipSuccess || hipMalloc(&s->d_koff, ob) != hipSuccess ||
+        (s->total && hipMemcpy(s->d_ev, events, (size_t)s->total * 3 * sizeof(RmjEvent), hipMemcpyHostToDevice) != hipSuccess) ||
+        hipMemcpy(s->d_off, s->off.data(), ob, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(s->d_koff, s->koff.data(), ob, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError();
+        rmj_logset_destroy(s);
+        return fail(RMJ_ERR_HIP, "rmj_logset_create: no device memory for the event stream, or the upload failed");
+    }
+    *out = s;
+    return RMJ_OK;
+}
+int rmj_logset_destroy(rmj_logset_handle s) {
+    if (!s) return RMJ_OK;
+    hipSetDevice(s->device);
+    hipFree(s->d_ev); hipFree(s->d_off); hipFree(s->d_koff);
+    delete s;
+    return RMJ_OK;
+}
+int rmj_logset_info(rmj_logset_handle s, RmjLogsetInfo* out, uint32_t* kyoku_offsets) {
+    if (!s || !out) return fail(RMJ_ERR_ARG, "null argument");
+    *out = RmjLogsetInfo{s->M, s->total, s->K, s->max_len};
+    if (kyoku_offsets) memcpy(kyoku_offsets, s->koff.data(), (size_t)(s->M + 1) * 4);
+    return RMJ_OK;
+}
+int rmj_logreplay_assign(const uint32_t* offsets, uint32_t n_logs, uint32_t n_slots, uint32_t* slot_of_log, uint32_t* slot_logs, uint32_t* slot_first, uint32_t* steps) {
+    if (!offsets) return fail(RMJ_ERR_ARG, "null argument");
+    if (n_slots > n_logs || (!n_slots && n_logs)) return fail(RMJ_ERR_ARG, "rmj_logreplay_assign: 1 <= n_slots <= n_logs (a slot without a log replays nothing)");
+    const uint32_t st = n_slots ? lr_assign(offsets, n_logs, n_slots, slot_of_log, slot_logs, slot_first) : 0u;
+    if (!n_slots && slot_first) slot_first[0] = 0u;
+    if (steps) *steps = st;
+    return RMJ_OK;
+}
+static int logreplay_clear_impl(rmj_logreplay* r) {
+    rmj_env* h = r->env;
+    LogRun& R = r->R;
+    const uint32_t n = R.n;
+    std::vector<uint32_t> pos(n), cur(n);
+    for (uint32_t s = 0; s < n; s++) {
+        pos[s] = r->slot_first[s];
+        cur[s] = pos[s] < r->slot_first[s + 1] ? r->set->off[r->slot_logs[pos[s]]] : 0u;
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(R.pos, pos.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(R.cur, cur.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemsetAsync(R.kcount, 0, (size_t)n * 4, h->stream));
+    HIPCHK(hipMemsetAsync(R.tcount, 0, (size_t)n * 16, h->stream));
+    HIPCHK(hipMemsetAsync(R.apply_at, 0xFF, (size_t)n * 4, h->stream));
+    HIPCHK(hipMemsetAsync(R.dec_n, 0, n, h->stream));
+    HIPCHK(hipMemsetAsync(R.log_status, 0, R.M ? R.M : 1u, h->stream));
+    HIPCHK(hipMemsetAsync(R.traj_len, 0, (size_t)(R.K ? R.K : 1u) * 16, h->stream));
+    HIPCHK(hipMemsetAsync(R.traj_broken, 0, (size_t)(R.K ? R.K : 1u) * 4, h->stream));
+    HIPCHK(hipMemsetAsync(R.ctr, 0, LR_C_WORDS * 4, h->stream));
+    r->step = 0;
+    return RMJ_OK;
+}
+int rmj_logreplay_create(rmj_handle h, rmj_logset_handle set, const RmjLogReplayConfig* cfg, rmj_logreplay_handle* out) {
+    if (!h || !set || !cfg || !out) return fail(RMJ_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (!cfg->capacity) return fail(RMJ_ERR_ARG, "rmj_logreplay_create: the pool needs a capacity (samples)");
+    if (set->device != h->cfg.device) return fail(RMJ_ERR_ARG, "rmj_logreplay_create: the log set lives on another device");
+    const uint32_t n = h->cfg.n_games;
+    if (n > set->M) return fail(RMJ_ERR_ARG, "rmj_logreplay_create: more slots (the handle's games) than logs: n_slots <= M");
+    if (cfg->flags & ~(uint32_t)(RMJ_LOGREPLAY_INCLUDE_PASS | RMJ_LOGREPLAY_SKIP_SINGLE_ACTION)) return fail(RMJ_ERR_ARG, "rmj_logreplay_create: unknown flag");
+    uint32_t ch, w, rs;
+    float dummy;
+    RmjObsBatch b{};
+    b.features = cfg->features;
+    b.d_out = &dummy;   // (shape check only)
+    int rc = batch_shape(h, &b, &ch, &w, &rs);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    rmj_logreplay* r = new rmj_logreplay();
+    r->env = h;
+    r->set = set;
+    r->cfg = *cfg;
+    r->cfg.gamma_powers = nullptr;
+    const bool sanma = h->cfg.game_mode >= 3;
+    const uint32_t cap = cfg->capacity, M = set->M, K = set->K ? set->K : 1u, A = sanma ? RMJ_ACTION_SPACE_3P : RMJ_ACTION_SPACE_4P;
+    r->slot_first.assign(n + 1, 0u);
+    r->slot_logs.assign(M ? M : 1u, 0u);
+    r->steps = lr_assign(set->off.data(), M, n, nullptr, r->slot_logs.data(), r->slot_first.data());
+    // P[k] = gamma ** k, k < the longest log + 1 (a trajectory has fewer decisions than its log has events)
+    r->n_powers = cfg->gamma_powers ? cfg->n_powers : set->max_len + 1u;
+    if (!r->n_powers || (cfg->gamma_powers && cfg->n_powers < set->max_len + 1u)) {
+        delete r;
+        return fail(RMJ_ERR_ARG, "rmj_logreplay_create: the table of powers needs an entry per event of the longest log, plus one");
+    }
+    std::vector<double> pw(r->n_powers);
+    for (uint32_t k = 0; k < r->n_powers; k++) pw[k] = cfg->gamma_powers ? cfg->gamma_powers[k] : std::pow(cfg->gamma, (double)k);
+    LogRun& R = r->R;
+    R.n = n; R.M = M; R.K = set->K; R.capacity = cap; R.feat_floats = ch * w; R.row_floats = (ch * w + 3u) & ~3u; R.A = A; R.NP = sanma ? 3u : 4u;
+    R.include_pass = (cfg->flags & RMJ_LOGREPLAY_INCLUDE_PASS) ? 1u : 0u;
+    R.skip_single = (cfg->flags & RMJ_LOGREPLAY_SKIP_SINGLE_ACTION) ? 1u : 0u;
+    R.sanma = sanma ? 1u : 0u;
+    R.ev = set->d_ev; R.off = set->d_off; R.koff = set->d_koff;
+    const size_t big = n > cap ? n : cap;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t o_feat = take((size_t)cap * R.row_floats * 4), o_packed = take((size_t)cap * 8), o_ret64 = take((size_t)cap * 8), o_dact = take((size_t)n * 32),
+                 o_powers = take((size_t)r->n_powers * 8), o_action = take((size_t)cap * 4), o_log = take((size_t)cap * 4), o_kyoku = take((size_t)cap * 4),
+                 o_seat = take((size_t)cap * 4), o_t = take((size_t)cap * 4), o_krow = take((size_t)cap * 4), o_ret = take((size_t)cap * 4), o_rank = take((size_t)cap * 4),
+                 o_sfirst = take((size_t)(n + 1) * 4), o_slogs = take((size_t)(M ? M : 1u) * 4), o_pos = take((size_t)n * 4), o_cur = take((size_t)n * 4),
+                 o_kcount = take((size_t)n * 4), o_tcount = take((size_t)n * 16), o_apply = take((size_t)n * 4), o_dt = take((size_t)n * 16), o_dlog = take((size_t)n * 4),
+                 o_dkrow = take((size_t)n * 4), o_tlen = take((size_t)K * 16), o_offs = take(big * 4), o_totals = take(((big + PPO_SCAN_BLOCK - 1) / PPO_SCAN_BLOCK) * 4),
+                 o_ctr = take(LR_C_WORDS * 4), o_mask = take((size_t)cap * A), o_dn = take(n), o_dseat = take((size_t)n * 4), o_status = take(M ? M : 1u),
+                 o_broken = take((size_t)K * 4);
+    if (hipMalloc(&r->mem, off) != hipSuccess) {
+        (void)hipGetLastError();
+        delete r;
+        return fail(RMJ_ERR_HIP, "rmj_logreplay_create: no device memory for a pool of " + std::to_string(off >> 20) + " MiB (capacity x row bytes: choose a smaller capacity)");
+    }
+    uint8_t* m = (uint8_t*)r->mem;
+    R.feat = (float*)(m + o_feat); R.packed = (uint64_t*)(m + o_packed); R.ret64 = (double*)(m + o_ret64); R.dec_action = (uint64_t*)(m + o_dact);
+    r->d_powers = (double*)(m + o_powers);
+    R.action = (int32_t*)(m + o_action); R.log = (int32_t*)(m + o_log); R.kyoku = (int32_t*)(m + o_kyoku); R.seat = (int32_t*)(m + o_seat); R.t = (int32_t*)(m + o_t);
+    R.krow = (uint32_t*)(m + o_krow); R.ret = (float*)(m + o_ret); R.rank = (int32_t*)(m + o_rank);
+    R.slot_first = (uint32_t*)(m + o_sfirst); R.slot_logs = (uint32_t*)(m + o_slogs); R.pos = (uint32_t*)(m + o_pos); R.cur = (uint32_t*)(m + o_cur);
+    R.kcount = (uint32_t*)(m + o_kcount); R.tcount = (uint32_t*)(m + o_tcount); R.apply_at = (uint32_t*)(m + o_apply); R.dec_t = (uint32_t*)(m + o_dt);
+    R.dec_log = (uint32_t*)(m + o_dlog); R.dec_krow = (uint32_t*)(m + o_dkrow); R.traj_len = (uint32_t*)(m + o_tlen); R.offs = (uint32_t*)(m + o_offs);
+    R.totals = (uint32_t*)(m + o_totals); R.ctr = (uint32_t*)(m + o_ctr); R.mask = m + o_mask; R.dec_n = m + o_dn; R.dec_seat = m + o_dseat;
+    R.log_status = m + o_status; R.traj_broken = m + o_broken;
+    h->logreplay.push_back(r);
+    // everything behind the feature rows starts as zeros (the views show defined values in slots that were never filled)
+    if (hipMemsetAsync(m + o_packed, 0, off - o_packed, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
+        hipMemcpy(m + o_sfirst, r->slot_first.data(), (size_t)(n + 1) * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        (M && hipMemcpy(m + o_slogs, r->slot_logs.data(), (size_t)M * 4, hipMemcpyHostToDevice) != hipSuccess) ||
+        hipMemcpy(r->d_powers, pw.data(), (size_t)r->n_powers * 8, hipMemcpyHostToDevice) != hipSuccess || (rc = logreplay_clear_impl(r))) {
+        rmj_logreplay_destroy(r);
+        return rc ? rc : fail(RMJ_ERR_HIP, "rmj_logreplay_create: initialising the pool failed");
+    }
+    *out = r;
+    return RMJ_OK;
+}
+int rmj_logreplay_destroy(rmj_logreplay_handle r) {
+    if (!r) return RMJ_OK;
+    rmj_env* h = r->env;
+    hipSetDevice(h->cfg.device);
+    if (h->stream) hipStreamSynchronize(h->stream);
+    for (size_t i = 0; i < h->logreplay.size(); i++)
+        if (h->logreplay[i] == r) { h->logreplay.erase(h->logreplay.begin() + i); break; }
+    hipFree(r->mem);
+    delete r;
+    return RMJ_OK;
+}
+int rmj_logreplay_clear(rmj_logreplay_handle r) {
+    if (!r) return fail(RMJ_ERR_ARG, "null argument");
+    HIPCHK(hipSetDevice(r->env->cfg.device));
+    return logreplay_clear_impl(r);
+}
+int rmj_logreplay_run_device(rmj_logreplay_handle r, uint32_t n_steps, uint32_t* steps_left) {
+    if (!r) return fail(RMJ_ERR_ARG, "null argument");
+    rmj_env* h = r->env;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const LogRun& R = r->R;
+    const uint32_t n = R.n, nb = (n + PPO_SCAN_BLOCK - 1) / PPO_SCAN_BLOCK, left = r->steps - r->step;
+    const uint32_t todo = n_steps && n_steps < left ? n_steps : left;
+    const bool sanma = h->cfg.game_mode >= 3;
+    const int feat = r->cfg.features;
+    const float* decay = h->d_decay;
+    for (uint32_t i = 0; i < todo; i++) {
+        hipLaunchKernelGGL(k_log_decide, game_grid(n), dim3(256), 0, h->stream, h->d, R, 0);
+        hipLaunchKernelGGL(k_log_scan, dim3(nb), dim3(PPO_SCAN_BLOCK), 0, h->stream, R);
+#define RMJ_LAUNCH_RECORD(SM, F) hipLaunchKernelGGL((k_log_record<SM, F>), dim3(n * 4), dim3(64), 0, h->stream, h->d, R, decay)
+        if (sanma && feat == RMJ_FEATURES_EXTENDED) RMJ_LAUNCH_RECORD(true, RMJ_FEATURES_EXTENDED);
+        else if (sanma) RMJ_LAUNCH_RECORD(true, RMJ_FEATURES_BASE);
+        else if (feat == RMJ_FEATURES_EXTENDED) RMJ_LAUNCH_RECORD(false, RMJ_FEATURES_EXTENDED);
+        else if (feat == RMJ_FEATURES_DISCARD_SHANTEN) RMJ_LAUNCH_RECORD(false, RMJ_FEATURES_DISCARD_SHANTEN);
+        else RMJ_LAUNCH_RECORD(false, RMJ_FEATURES_BASE);
+#undef RMJ_LAUNCH_RECORD
+        if (sanma) hipLaunchKernelGGL(rmj3::k_log_apply, game_grid(n), dim3(256), 0, h->stream, (const Env*)h->d_env, R.ev, (const uint32_t*)R.apply_at);
+        else hipLaunchKernelGGL(rmj4::k_log_apply, game_grid(n), dim3(256), 0, h->stream, (const Env*)h->d_env, R.ev, (const uint32_t*)R.apply_at);
+    }
+    r->step += todo;
+    // the bookkeeping of the last step: its samples join the fill, the logs that just ended become complete
+    if (n) hipLaunchKernelGGL(k_log_decide, game_grid(n), dim3(256), 0, h->stream, h->d, R, 1);
+    HIPCHK(hipGetLastError());
+    if (steps_left) *steps_left = r->steps - r->step;
+    return RMJ_OK;
+}
+int rmj_logreplay_finalize_device(rmj_logreplay_handle r, const double* d_reward, const int32_t* d_end_scores) {
+    if (!r || !d_reward || !d_end_scores) return fail(RMJ_ERR_ARG, "null argument");
+    rmj_env* h = r->env;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    hipLaunchKernelGGL(k_log_finalize, dim3((r->R.capacity + 255u) / 256u), dim3(256), 0, h->stream, r->R, d_reward, d_end_scores, (const double*)r->d_powers, r->n_powers);
+    HIPCHK(hipGetLastError());
+    return RMJ_OK;
+}
+int rmj_logreplay_emit_device(rmj_logreplay_handle r, const RmjLogBatch* out) {
+    if (!r || !out || !out->d_count) return fail(RMJ_ERR_ARG, "null argument");
+    if (out->rows && (!out->d_features || !out->d_mask || !out->d_action || !out->d_packed || !out->d_return || !out->d_return64 || !out->d_rank || !out->d_log ||
+                      !out->d_kyoku || !out->d_seat || !out->d_t))
+        return fail(RMJ_ERR_ARG, "null argument");
+    rmj_env* h = r->env;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const uint32_t cap = r->R.capacity;
+    LogOut O{out->d_features, out->d_mask, out->d_action, out->d_packed, out->d_return, out->d_return64, out->d_rank, out->d_log, out->d_kyoku, out->d_seat, out->d_t,
+             out->d_count, out->rows};
+    hipLaunchKernelGGL(k_log_emit_scan, dim3((cap + PPO_SCAN_BLOCK - 1) / PPO_SCAN_BLOCK), dim3(PPO_SCAN_BLOCK), 0, h->stream, r->R);
+    hipLaunchKernelGGL(k_log_emit, ppo_wave_grid(cap), dim3(256), 0, h->stream, r->R, O);
+    HIPCHK(hipGetLastError());
+    return RMJ_OK;
+}
+int rmj_logreplay_views(rmj_logreplay_handle r, RmjLogReplayViews* out) {
+    if (!r || !out) return fail(RMJ_ERR_ARG, "null argument");
+    const LogRun& R = r->R;
+    *out = RmjLogReplayViews{R.capacity, R.row_floats, R.A, r->steps, R.feat, R.mask, R.action, R.packed, R.ret, R.ret64, R.rank, R.log, R.kyoku, R.seat, R.t,
+                             R.log_status, R.traj_len, R.traj_broken, R.ctr};
+    return RMJ_OK;
+}
+int rmj_logreplay_counts(rmj_logreplay_handle r, RmjLogReplayCounts* out) {
+    if (!r || !out) return fail(RMJ_ERR_ARG, "null argument");
+    rmj_env* h = r->env;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    uint32_t c[LR_C_WORDS];
+    HIPCHK(hipMemcpyAsync(c, r->R.ctr, sizeof(c), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    *out = RmjLogReplayCounts{c[LR_C_FILL], c[LR_C_OVERFLOWED], c[LR_C_FAILED], c[LR_C_COMPLETE], c[LR_C_DECISIONS], c[LR_C_EVENTS], r->step, r->steps - r->step};
     return RMJ_OK;
 }
 

@@ -222,6 +222,33 @@ __global__ __launch_bounds__(256, 4) void k_apply_event(const Env* __restrict__ 
     store_state(S, E.core + g, lane);
 }
 
+// The log replay's step (rmj_logreplay_run_device): k_apply_event reading every game's event from a resident stream - game g applies
+// the three records at stream[at[g]] (0xFFFFFFFF: none in this step) - with the log walker's bookkeeping (RMJ_EVF_REPLAY_PASS), as
+// rmj_apply_events does for a replay.  The stream itself is not written: the flag is set on the copy in LDS.
+__global__ __launch_bounds__(256, 4) void k_log_apply(const Env* __restrict__ Ep, const RmjEvent* __restrict__ stream, const uint32_t* __restrict__ at) {
+    CEnv& E = *(CEnv*)Ep;
+    __shared__ BlockShared sh;
+    __shared__ __attribute__((aligned(16))) RmjEvent evb[WPB][3];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint32_t g = blockIdx.x * WPB + wave;
+    if (g >= E.n_games) return;
+    const uint32_t k = at[g];
+    if (k == 0xFFFFFFFFu) return;
+    const RmjEvent* src = stream + (size_t)k * 3;
+    if (src[0].type == RMJ_EV_NONE || src[0].type == RMJ_EV_END_GAME || src[0].type == RMJ_EV_TEHAI) return;
+    if (lane < (int)(3 * sizeof(RmjEvent) / 4)) reinterpret_cast<uint32_t*>(evb[wave])[lane] = reinterpret_cast<const uint32_t*>(src)[lane];
+    wave_sync();
+    if (lane == 0) evb[wave][0].pad |= RMJ_EVF_REPLAY_PASS;
+    GState& S = sh.st[wave];
+    load_state(S, E.core + g, lane);   // (ends in a wave_sync: the flag is in place)
+    Ctx c{S, E, sh.x[wave], g, lane, E.wall + (size_t)g * RMJ_WALL_STRIDE, E.legal + (size_t)g * 4 * RMJ_MAX_LEGAL};
+    const RmjEvent* mine = evb[wave];
+    const bool passive = mine[0].type == RMJ_EV_REACH_ACCEPTED || mine[0].type == RMJ_EV_DORA;
+    apply_event(c, mine);
+    if (!passive) finalize_outputs<false>(c, true, false);
+    store_state(S, E.core + g, lane);
+}
+
 // recompute observation outputs of one game after rmj_poke_state
 __global__ __launch_bounds__(64, 4) void k_refresh(const Env* __restrict__ Ep, uint32_t g) {
     CEnv& E = *(CEnv*)Ep;

@@ -38,6 +38,9 @@ EXPORTS = [
     "rmj_encode_batch_device", "rmj_encode_batch", "rmj_step_ids_encode_batch_device", "rmj_step_sample_encode_batch_device",
     "rmj_select_ids_device", "rmj_ppo_create", "rmj_ppo_destroy", "rmj_ppo_record_device", "rmj_ppo_close_device", "rmj_ppo_emit_device",
     "rmj_ppo_views", "rmj_ppo_counts", "rmj_ppo_clear",
+    "rmj_logset_create", "rmj_logset_destroy", "rmj_logset_info", "rmj_logreplay_assign", "rmj_logreplay_create", "rmj_logreplay_destroy",
+    "rmj_logreplay_run_device", "rmj_logreplay_finalize_device", "rmj_logreplay_emit_device", "rmj_logreplay_views", "rmj_logreplay_counts",
+    "rmj_logreplay_clear",
 ]
 
 
@@ -175,6 +178,18 @@ def load_lib():
     L.rmj_ppo_views.argtypes = [vp, C.POINTER(abi.PpoViews)]
     L.rmj_ppo_counts.argtypes = [vp, C.POINTER(abi.PpoCounts)]
     L.rmj_ppo_clear.argtypes = [vp]
+    L.rmj_logset_create.argtypes = [C.c_int, vp, vp, C.c_uint32, C.POINTER(vp)]
+    L.rmj_logset_destroy.argtypes = [vp]
+    L.rmj_logset_info.argtypes = [vp, C.POINTER(abi.LogsetInfo), vp]
+    L.rmj_logreplay_assign.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.POINTER(C.c_uint32)]
+    L.rmj_logreplay_create.argtypes = [vp, vp, C.POINTER(abi.LogReplayConfig), C.POINTER(vp)]
+    L.rmj_logreplay_destroy.argtypes = [vp]
+    L.rmj_logreplay_run_device.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32)]
+    L.rmj_logreplay_finalize_device.argtypes = [vp, vp, vp]
+    L.rmj_logreplay_emit_device.argtypes = [vp, C.POINTER(abi.LogBatch)]
+    L.rmj_logreplay_views.argtypes = [vp, C.POINTER(abi.LogReplayViews)]
+    L.rmj_logreplay_counts.argtypes = [vp, C.POINTER(abi.LogReplayCounts)]
+    L.rmj_logreplay_clear.argtypes = [vp]
     _LIB = L
     return L
 
