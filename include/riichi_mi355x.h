@@ -618,6 +618,48 @@ typedef struct RmjLogsetInfo {
 int rmj_logset_create(int device, const RmjEvent* events /*[total][3]*/, const uint32_t* offsets /*[n_logs + 1]*/, uint32_t n_logs, rmj_logset_handle* out);
 int rmj_logset_destroy(rmj_logset_handle s);
 int rmj_logset_info(rmj_logset_handle s, RmjLogsetInfo* out, uint32_t* kyoku_offsets /*[n_logs + 1]*/);
+/* A log set straight from MJAI JSONL text, parsed on the device (csrc/rmj_evparse.h, csrc/rmj_logtext.hip.h): log i is the bytes
+ * text[ranges[i][0] .. ranges[i][1]), one JSON object per line ('\n'; the last line may lack it; lines that are empty after trimming
+ * spaces, tabs and a trailing '\r' are not events).  The ranges need not be contiguous or ordered (leaving a range out drops a log); a
+ * log is at most 4 GiB - 1 of text.  Every line becomes the three records abi.event_records_from_mjai gives for it (num_players: 3 or 4,
+ * the seats whose tehais are read; RMJ_LOGTEXT_MASKED_OK: unmappable tile names read as tile 0), and the set also holds, resident, the
+ * per-kyoku score tables of datasets.kyoku_tables (start / end scores [n_kyokus][4] int32), every log's decision-event count and its
+ * status: RMJ_LOGTEXT_OK, or the status of its first line that did not parse (error_line: that line, numbered from 1, blank lines
+ * included; 0 when the log is fine or failed in the kyoku walk).  A line that fails gives three NONE records; a set with failed logs is
+ * still returned.  Statuses (never silently different from the host packer: csrc/rmj_evparse.h lists what is declined):
+ * ERR_* where json.loads or the packer raises, UNSUPPORTED for valid input the parser declines to interpret.
+ * Without RMJ_LOGTEXT_ON_DEVICE text and ranges are host memory (the bytes between the lowest begin and the highest end are uploaded in
+ * one copy); with it both are device pointers.  Synchronous like rmj_logset_create: the set is complete on return, the temporaries are
+ * freed, and rmj_logset_info / rmj_logreplay_create / rmj_logreplay_assign work on it unchanged.  RMJ_ERR_RANGE when the logs hold more
+ * than UINT32_MAX events or a log is 4 GiB or longer; RMJ_ERR_ARG for a range with end < begin, num_players not 3 or 4, an unknown flag. */
+#define RMJ_LOGTEXT_OK 0
+#define RMJ_LOGTEXT_UNSUPPORTED 1  /* valid JSON the device parser declines to interpret (escaped key, 1.5 as actor, duplicate key, ...) */
+#define RMJ_LOGTEXT_ERR_JSON 2     /* not a JSON object (json.loads raises) */
+#define RMJ_LOGTEXT_ERR_KEY 3      /* a key the event's type requires is missing */
+#define RMJ_LOGTEXT_ERR_TEHAI 4    /* start_kyoku: a tehai that does not hold 13 tiles */
+#define RMJ_LOGTEXT_ERR_TILE 5     /* a tile name that maps to nothing (without RMJ_LOGTEXT_MASKED_OK) */
+#define RMJ_LOGTEXT_ERR_VALUE 6    /* null where the event's type requires a value */
+#define RMJ_LOGTEXT_ERR_REPLAY 7   /* the kyoku walk (MjaiReplay.from_events) raises: an actor that is no seat of the kyoku, a call without target */
+#define RMJ_LOGTEXT_ON_DEVICE 1u
+#define RMJ_LOGTEXT_MASKED_OK 2u
+int rmj_logset_create_from_text(int device, const uint8_t* text, const uint64_t* ranges /*[n_logs][2] begin, end*/, uint32_t n_logs, uint32_t num_players,
+                                uint32_t flags, rmj_logset_handle* out);
+/* Device pointers into a set.  The score tables, status, error_line and decisions are NULL for a set made by rmj_logset_create. */
+typedef struct RmjLogsetViews {
+    const RmjEvent* events;          /* [n_events][3] */
+    const uint32_t* offsets;         /* [n_logs + 1] */
+    const uint32_t* kyoku_offsets;   /* [n_logs + 1] */
+    const int32_t* start_scores;     /* [n_kyokus][4] */
+    const int32_t* end_scores;       /* [n_kyokus][4] */
+    const uint8_t* status;           /* [n_logs] RMJ_LOGTEXT_* */
+    const uint32_t* error_line;      /* [n_logs] */
+    const uint32_t* decisions;       /* [n_logs] events of a decision type (dahai chi pon daiminkan kan ankan kakan reach hora kita ryukyoku) */
+} RmjLogsetViews;
+int rmj_logset_views(rmj_logset_handle s, RmjLogsetViews* out);
+/* Host copies of a text set's per-log results (any may be NULL); RMJ_ERR_ARG for status / error_line / decisions of a set made by
+ * rmj_logset_create. */
+int rmj_logset_status(rmj_logset_handle s, uint8_t* status /*[n_logs]*/, uint32_t* error_line /*[n_logs]*/, uint32_t* decisions /*[n_logs]*/,
+                      uint32_t* offsets /*[n_logs + 1]*/);
 /* Which slot replays which logs (host only, no device needed): the logs are handed out in log order, each to the slot that is free
  * first when every event takes one step, ties to the lowest slot - a pure function of (n_logs, n_slots, the logs' lengths), so the
  * order of the samples is the same run after run.  slot_of_log [n_logs]; slot s replays slot_logs[slot_first[s] .. slot_first[s + 1])

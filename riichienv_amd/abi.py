@@ -261,6 +261,15 @@ class LogsetInfo(C.Structure):       # RmjLogsetInfo
     _fields_ = [(k, C.c_uint32) for k in ("n_logs", "n_events", "n_kyokus", "longest_log")]
 
 
+class LogsetViews(C.Structure):      # RmjLogsetViews: device pointers (the tables and per-log results are NULL unless the set was parsed from text)
+    _fields_ = [(k, C.c_void_p) for k in ("events", "offsets", "kyoku_offsets", "start_scores", "end_scores", "status", "error_line", "decisions")]
+
+
+# RMJ_LOGTEXT_*: per-line / per-log parse statuses and the flags of rmj_logset_create_from_text
+LOGTEXT_OK, LOGTEXT_UNSUPPORTED, LOGTEXT_ERR_JSON, LOGTEXT_ERR_KEY, LOGTEXT_ERR_TEHAI, LOGTEXT_ERR_TILE, LOGTEXT_ERR_VALUE, LOGTEXT_ERR_REPLAY = range(8)
+LOGTEXT_STATUS_NAMES = ["OK", "UNSUPPORTED", "ERR_JSON", "ERR_KEY", "ERR_TEHAI", "ERR_TILE", "ERR_VALUE", "ERR_REPLAY"]
+LOGTEXT_ON_DEVICE, LOGTEXT_MASKED_OK = 1, 2
+
 LOGREPLAY_INCLUDE_PASS, LOGREPLAY_SKIP_SINGLE_ACTION = 1, 2   # RMJ_LOGREPLAY_*
 
 

@@ -842,6 +842,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RMJ_ENCX_WAV
     encode_batch_row<SANMA, FEAT>(E, g, seat, decay, dst, lane);
 }
 #include "rmj_logreplay.hip.h"
+#include "rmj_logtext.hip.h"
 
 // ---- auxiliary encoders (row N3): kawa overview, yaku possibility, furiten-ron possibility ----------------------
 // One wave per game; absolute seat order, public information only (the same for every observing seat).
@@ -1174,6 +1175,10 @@ struct rmj_logset {
     std::vector<uint32_t> off, koff;   // [M + 1] first event / first kyoku row of every log
     RmjEvent* d_ev = nullptr;
     uint32_t *d_off = nullptr, *d_koff = nullptr;
+    // a set parsed from text (rmj_logset_create_from_text) also holds its score tables and per-log results
+    int32_t *d_start = nullptr, *d_end = nullptr;   // [K][4]
+    uint8_t* d_status = nullptr;                    // [M]
+    uint32_t *d_errline = nullptr, *d_dec = nullptr;
 };
 // a log sample builder bound to a handle and a log set (rmj_logreplay_create): its pool and bookkeeping are one device allocation
 struct rmj_logreplay {
@@ -3318,6 +3323,7 @@ int rmj_logset_destroy(rmj_logset_handle s) {
     if (!s) return RMJ_OK;
     hipSetDevice(s->device);
     hipFree(s->d_ev); hipFree(s->d_off); hipFree(s->d_koff);
+    hipFree(s->d_start); hipFree(s->d_end); hipFree(s->d_status); hipFree(s->d_errline); hipFree(s->d_dec);
     delete s;
     return RMJ_OK;
 }
@@ -3325,6 +3331,147 @@ int rmj_logset_info(rmj_logset_handle s, RmjLogsetInfo* out, uint32_t* kyoku_off
     if (!s || !out) return fail(RMJ_ERR_ARG, "null argument");
     *out = RmjLogsetInfo{s->M, s->total, s->K, s->max_len};
     if (kyoku_offsets) memcpy(kyoku_offsets, s->koff.data(), (size_t)(s->M + 1) * 4);
+    return RMJ_OK;
+}
+// body of rmj_logset_create_from_text: everything in `tmp` is freed by the caller, whatever happens
+static int logset_from_text_impl(rmj_logset* s, const uint8_t* text, const uint64_t* ranges, uint32_t num_players, uint32_t flags, std::vector<void*>& tmp) {
+    using namespace rmjlt;
+    const uint32_t M = s->M;
+    const bool on_device = (flags & RMJ_LOGTEXT_ON_DEVICE) != 0u;
+    auto dalloc = [&](void** p, size_t bytes, bool keep) -> bool {
+        if (hipMalloc(p, bytes ? bytes : 16u) != hipSuccess) { *p = nullptr; (void)hipGetLastError(); return false; }
+        if (!keep) tmp.push_back(*p);
+        return true;
+    };
+#define LT_ALLOC(ptr, bytes, keep) \
+    if (!dalloc((void**)&(ptr), (bytes), (keep))) return fail(RMJ_ERR_HIP, "rmj_logset_create_from_text: no device memory")
+    // the ranges on the host: O(n_logs) words, checked before a kernel trusts them
+    std::vector<uint64_t> hr((size_t)2 * M);
+    if (M) {
+        if (on_device) HIPCHK(hipMemcpy(hr.data(), ranges, hr.size() * 8, hipMemcpyDeviceToHost));
+        else memcpy(hr.data(), ranges, hr.size() * 8);
+    }
+    uint64_t lo = ~0ull, hi = 0;
+    for (uint32_t l = 0; l < M; l++) {
+        const uint64_t b = hr[2 * (size_t)l], e = hr[2 * (size_t)l + 1];
+        if (e < b) return fail(RMJ_ERR_ARG, "rmj_logset_create_from_text: a range ends before it begins");
+        if (e - b > 0xFFFFFFFFull) return fail(RMJ_ERR_RANGE, "rmj_logset_create_from_text: a log of 4 GiB or more");
+        if (e > b) { lo = b < lo ? b : lo; hi = e > hi ? e : hi; }
+    }
+    if (lo > hi) lo = hi = 0;
+    if (hi > lo && !text) return fail(RMJ_ERR_ARG, "null argument");
+    const uint8_t* d_text = text;
+    const uint64_t* d_ranges = ranges;
+    if (!on_device) {   // one upload of the bytes the ranges span, the ranges rebased on it
+        uint8_t* t = nullptr;
+        uint64_t* r = nullptr;
+        LT_ALLOC(t, (size_t)(hi - lo), false);
+        LT_ALLOC(r, hr.size() * 8, false);
+        if (hi > lo) HIPCHK(hipMemcpy(t, text + lo, (size_t)(hi - lo), hipMemcpyHostToDevice));
+        for (uint32_t l = 0; l < M; l++) {
+            if (hr[2 * (size_t)l + 1] == hr[2 * (size_t)l]) hr[2 * (size_t)l] = hr[2 * (size_t)l + 1] = lo;   // an empty range may lie anywhere
+            hr[2 * (size_t)l] -= lo;
+            hr[2 * (size_t)l + 1] -= lo;
+        }
+        if (M) HIPCHK(hipMemcpy(r, hr.data(), hr.size() * 8, hipMemcpyHostToDevice));
+        d_text = t;
+        d_ranges = r;
+    }
+    uint32_t *d_cnt = nullptr, *d_choff = nullptr, *d_max = nullptr, *d_kcnt = nullptr;
+    unsigned long long *d_tot = nullptr, *d_ferr = nullptr;
+    const size_t ob = (size_t)(M + 1) * 4;
+    LT_ALLOC(d_cnt, (size_t)M * 4, false);
+    LT_ALLOC(d_choff, ob, false);
+    LT_ALLOC(d_max, 4, false);
+    LT_ALLOC(d_kcnt, (size_t)M * 4, false);
+    LT_ALLOC(d_tot, 3 * 8, false);
+    LT_ALLOC(d_ferr, (size_t)M * 8, false);
+    LT_ALLOC(s->d_off, ob, true);
+    LT_ALLOC(s->d_koff, ob, true);
+    LT_ALLOC(s->d_status, M, true);
+    LT_ALLOC(s->d_errline, (size_t)M * 4, true);
+    LT_ALLOC(s->d_dec, (size_t)M * 4, true);
+    HIPCHK(hipMemset(d_max, 0, 4));
+    HIPCHK(hipMemset(d_kcnt, 0, (size_t)M * 4 + (M ? 0 : 16)));
+    HIPCHK(hipMemset(s->d_dec, 0, (size_t)M * 4 + (M ? 0 : 16)));
+    HIPCHK(hipMemset(d_ferr, 0xFF, (size_t)M * 8 + (M ? 0 : 16)));
+    const dim3 per_log((M + 3u) / 4u ? (M + 3u) / 4u : 1u), b256(256);
+    // line census, event offsets, chunk offsets of the parse grid
+    if (M) hipLaunchKernelGGL(k_lt_lines<false>, per_log, b256, 0, 0, d_text, d_ranges, M, d_cnt, (const uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr);
+    hipLaunchKernelGGL(k_lt_scan, dim3(1), dim3(1024), 0, 0, d_cnt, M, 1u, s->d_off, d_tot, d_max);
+    hipLaunchKernelGGL(k_lt_scan, dim3(1), dim3(1024), 0, 0, d_cnt, M, 64u, d_choff, d_tot + 1, (uint32_t*)nullptr);
+    HIPCHK(hipGetLastError());
+    unsigned long long tot[3] = {0, 0, 0};
+    HIPCHK(hipMemcpy(tot, d_tot, 16, hipMemcpyDeviceToHost));
+    if (tot[0] > 0xFFFFFFFFull) return fail(RMJ_ERR_RANGE, "rmj_logset_create_from_text: the logs hold more than UINT32_MAX events");
+    const uint32_t total = (uint32_t)tot[0], chunks = (uint32_t)tot[1];
+    s->total = total;
+    uint32_t *d_es = nullptr, *d_ee = nullptr, *d_el = nullptr;
+    rmjp::Side* d_side = nullptr;
+    LT_ALLOC(d_es, (size_t)total * 4, false);
+    LT_ALLOC(d_ee, (size_t)total * 4, false);
+    LT_ALLOC(d_el, (size_t)total * 4, false);
+    LT_ALLOC(d_side, (size_t)total * sizeof(rmjp::Side), false);
+    LT_ALLOC(s->d_ev, (size_t)total * 3 * sizeof(RmjEvent), true);
+    if (total) {
+        // line index, then the records
+        hipLaunchKernelGGL(k_lt_lines<true>, per_log, b256, 0, 0, d_text, d_ranges, M, (uint32_t*)nullptr, (const uint32_t*)s->d_off, d_es, d_ee, d_el);
+        hipLaunchKernelGGL(k_lt_parse, dim3(chunks), dim3(64), 0, 0, d_text, d_ranges, M, (const uint32_t*)s->d_off, (const uint32_t*)d_choff, (const uint32_t*)d_es,
+                           (const uint32_t*)d_ee, (const uint32_t*)d_el, num_players, (flags & RMJ_LOGTEXT_MASKED_OK) ? 1u : 0u, s->d_ev, d_side, d_kcnt, s->d_dec, d_ferr);
+    }
+    hipLaunchKernelGGL(k_lt_scan, dim3(1), dim3(1024), 0, 0, d_kcnt, M, 1u, s->d_koff, d_tot + 2, (uint32_t*)nullptr);
+    HIPCHK(hipGetLastError());
+    // the O(n_logs) host mirrors
+    s->off.assign((size_t)M + 1, 0u);
+    s->koff.assign((size_t)M + 1, 0u);
+    HIPCHK(hipMemcpy(s->off.data(), s->d_off, ob, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(s->koff.data(), s->d_koff, ob, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&s->max_len, d_max, 4, hipMemcpyDeviceToHost));
+    s->K = s->koff[M];
+    LT_ALLOC(s->d_start, (size_t)s->K * 16, true);
+    LT_ALLOC(s->d_end, (size_t)s->K * 16, true);
+    if (M) hipLaunchKernelGGL(k_lt_tables, per_log, b256, 0, 0, (const rmjp::Side*)d_side, (const uint32_t*)s->d_off, (const uint32_t*)s->d_koff, M,
+                              (const unsigned long long*)d_ferr, s->d_start, s->d_end, s->d_status, s->d_errline);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+#undef LT_ALLOC
+    return RMJ_OK;
+}
+int rmj_logset_create_from_text(int device, const uint8_t* text, const uint64_t* ranges, uint32_t n_logs, uint32_t num_players, uint32_t flags, rmj_logset_handle* out) {
+    if (!out || (!ranges && n_logs)) return fail(RMJ_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (num_players != 3u && num_players != 4u) return fail(RMJ_ERR_ARG, "rmj_logset_create_from_text: num_players is 3 or 4");
+    if (flags & ~(uint32_t)(RMJ_LOGTEXT_ON_DEVICE | RMJ_LOGTEXT_MASKED_OK)) return fail(RMJ_ERR_ARG, "rmj_logset_create_from_text: unknown flag");
+    int rc = ensure_device(device);
+    if (rc) return rc;
+    rmj_logset* s = new rmj_logset();
+    s->device = device;
+    s->M = n_logs;
+    std::vector<void*> tmp;
+    rc = logset_from_text_impl(s, text, ranges, num_players, flags, tmp);
+    if (rc) (void)hipDeviceSynchronize();
+    for (void* p : tmp) hipFree(p);
+    if (rc) {
+        (void)hipGetLastError();
+        rmj_logset_destroy(s);
+        return rc;
+    }
+    *out = s;
+    return RMJ_OK;
+}
+int rmj_logset_views(rmj_logset_handle s, RmjLogsetViews* out) {
+    if (!s || !out) return fail(RMJ_ERR_ARG, "null argument");
+    *out = RmjLogsetViews{s->d_ev, s->d_off, s->d_koff, s->d_start, s->d_end, s->d_status, s->d_errline, s->d_dec};
+    return RMJ_OK;
+}
+int rmj_logset_status(rmj_logset_handle s, uint8_t* status, uint32_t* error_line, uint32_t* decisions, uint32_t* offsets) {
+    if (!s) return fail(RMJ_ERR_ARG, "null argument");
+    if ((status || error_line || decisions) && !s->d_status) return fail(RMJ_ERR_ARG, "rmj_logset_status: the set was not parsed from text, it has no status");
+    HIPCHK(hipSetDevice(s->device));
+    if (status && s->M) HIPCHK(hipMemcpy(status, s->d_status, s->M, hipMemcpyDeviceToHost));
+    if (error_line && s->M) HIPCHK(hipMemcpy(error_line, s->d_errline, (size_t)s->M * 4, hipMemcpyDeviceToHost));
+    if (decisions && s->M) HIPCHK(hipMemcpy(decisions, s->d_dec, (size_t)s->M * 4, hipMemcpyDeviceToHost));
+    if (offsets) memcpy(offsets, s->off.data(), (size_t)(s->M + 1) * 4);
     return RMJ_OK;
 }
 int rmj_logreplay_assign(const uint32_t* offsets, uint32_t n_logs, uint32_t n_slots, uint32_t* slot_of_log, uint32_t* slot_logs, uint32_t* slot_first, uint32_t* steps) {

@@ -103,6 +103,73 @@ def kyoku_tables(logs, n_players):
     return np.array(start, dtype=np.int32).reshape(-1, 4), np.array(end, dtype=np.int32).reshape(-1, 4)
 
 
+def _text_and_ranges(text, ranges):
+    """(uint8 array, [M, 2] uint64 ranges) of from_text's two input forms"""
+    if ranges is None:
+        parts = [bytes(t) for t in text]
+        ends = np.cumsum([len(p) for p in parts], dtype=np.uint64) if parts else np.zeros(0, np.uint64)
+        rng = np.zeros((len(parts), 2), dtype=np.uint64)
+        rng[:, 1] = ends
+        rng[1:, 0] = ends[:-1]
+        text = b"".join(parts)
+    else:
+        rng = np.ascontiguousarray(np.asarray(ranges, dtype=np.uint64).reshape(-1, 2))
+    buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, dtype=np.uint8)
+    if len(rng) and int(rng[:, 1].max()) > buf.size:
+        raise ValueError("a range ends behind the text")
+    if buf.size == 0:
+        buf = np.zeros(1, np.uint8)
+    return buf, rng
+
+
+def _read_log_file(path):
+    import gzip
+
+    with open(path, "rb") as f:
+        raw = f.read()
+    return gzip.decompress(raw) if raw[:2] == b"\x1f\x8b" else raw
+
+
+def parse_logs_device(text, ranges=None, num_players=4, masked_ok=False, device=0):
+    """MJAI JSONL text -> the packed records, parsed on the device (rmj_logset_create_from_text), as a dict of torch tensors on the GPU:
+    events [N, 3, 32] uint8 (abi.Event records, what pack_logs gives), offsets / kyoku_offsets [M + 1] int64, start_scores / end_scores
+    [K, 4] int32, status [M] uint8 (abi.LOGTEXT_*), error_line / decisions [M] int64.  text / ranges as in LogSampleBuilder.from_text, or a
+    uint8 tensor on the GPU with ranges an int64 [M, 2] tensor there."""
+    import torch
+
+    L = vecenv.load_lib()
+    flags = abi.LOGTEXT_MASKED_OK if masked_ok else 0
+    h = C.c_void_p()
+    if isinstance(text, torch.Tensor) and text.is_cuda:
+        text, rng = text.contiguous(), ranges.to(torch.int64).contiguous()
+        device, m = text.device.index, int(rng.shape[0])
+        torch.cuda.current_stream(text.device).synchronize()
+        vecenv._chk(L.rmj_logset_create_from_text(device, C.c_void_p(text.data_ptr() if text.numel() else 0), C.c_void_p(rng.data_ptr() if m else 0), m,
+                                                  int(num_players), flags | abi.LOGTEXT_ON_DEVICE, C.byref(h)))
+    else:
+        buf, rng = _text_and_ranges(text, ranges)
+        m = len(rng)
+        vecenv._chk(L.rmj_logset_create_from_text(int(device), buf.ctypes.data, rng.ctypes.data, m, int(num_players), flags, C.byref(h)))
+    try:
+        info, v = abi.LogsetInfo(), abi.LogsetViews()
+        vecenv._chk(L.rmj_logset_info(h, C.byref(info), None))
+        vecenv._chk(L.rmj_logset_views(h, C.byref(v)))
+        from .torch_env import _CudaArray
+
+        dev = torch.device("cuda", device)
+        keep = object()
+        get = lambda ptr, shape, ts: torch.as_tensor(_CudaArray(ptr, shape, ts, keep), device=dev).clone() if int(np.prod(shape)) else torch.zeros(shape, dtype=torch.uint8, device=dev)  # noqa: E731
+        n, k = int(info.n_events), int(info.n_kyokus)
+        out = {"events": get(v.events, (n, 3, 32), "|u1"), "offsets": get(v.offsets, (m + 1,), "<i4").to(torch.int64),
+               "kyoku_offsets": get(v.kyoku_offsets, (m + 1,), "<i4").to(torch.int64), "start_scores": get(v.start_scores, (k, 4), "<i4").to(torch.int32),
+               "end_scores": get(v.end_scores, (k, 4), "<i4").to(torch.int32), "status": get(v.status, (m,), "|u1"),
+               "error_line": get(v.error_line, (m,), "<i4").to(torch.int64), "decisions": get(v.decisions, (m,), "<i4").to(torch.int64)}
+        torch.cuda.synchronize(dev)
+    finally:
+        L.rmj_logset_destroy(h)
+    return out
+
+
 class LogSampleBuilder:
     """b = LogSampleBuilder(logs, game_mode=2, features="base"); b.run(); s = b.samples()
 
@@ -116,38 +183,12 @@ class LogSampleBuilder:
 
     def __init__(self, logs, game_mode=2, features="base", n_slots=None, capacity=None, gamma=0.99, include_pass=True, skip_single_action=True,
                  rule=None, device=0, share_stream=True, masked_ok=False, kyoku_scale=1.0 / 1000.0):
-        import torch
-
-        from .torch_env import _CudaArray
-
-        self.torch = torch
-        if features not in abi.FEATURES:
-            raise ValueError(f"unknown feature set {features!r}: one of {sorted(abi.FEATURES)}")
-        if rule not in (None, "tenhou", "mjsoul"):
-            raise ValueError(f"Unknown rule: '{rule}'. Expected 'tenhou' or 'mjsoul'")
+        self._check(features, rule)
         self.logs = [_events_of(l) for l in logs]
-        self.M = len(self.logs)
-        self.game_mode = vecenv._mode_id(game_mode)
-        self.sanma = self.game_mode >= 3
-        self.n_players = 3 if self.sanma else 4
-        self.features, self._feat = features, abi.FEATURES[features]
-        self.channels, self.width = abi.FEATURE_CHANNELS[self._feat], 27 if self.sanma else 34
-        self.A = abi.ACTION_SPACE_3P if self.sanma else abi.ACTION_SPACE_4P
-        self.n_slots = self.M if n_slots is None else int(n_slots)
-        if self.n_slots > self.M or (self.M and self.n_slots < 1):
-            raise ValueError(f"n_slots must be between 1 and the number of logs ({self.M})")
+        self._configure(len(self.logs), game_mode, features, n_slots, gamma, include_pass, skip_single_action, rule, device, share_stream, kyoku_scale)
         if capacity is None:
             capacity = 2 * sum(1 for l in self.logs for ev in l if ev.get("type") in _DECISION_TYPES) + 64
-        self.capacity = int(capacity)
-        if self.capacity <= 0:
-            raise ValueError("capacity must be positive (samples)")
-        self.gamma, self.kyoku_scale = float(gamma), float(kyoku_scale)
-        self.include_pass, self.skip_single_action = bool(include_pass), bool(skip_single_action)
-        self.device = torch.device("cuda", device)
-        self.shared = bool(share_stream)
-        self._finalized = False
-        self._emitted = None    # what samples() returned last, until run() / finalize() / clear()
-        self.h = self.set = self.env = None
+        self._set_capacity(capacity)
         import time
 
         t0 = time.perf_counter()
@@ -163,11 +204,78 @@ class LogSampleBuilder:
         L = self.L = vecenv.load_lib()
         self.set = C.c_void_p()
         vecenv._chk(L.rmj_logset_create(device, C.addressof(recs), offsets.ctypes.data, self.M, C.byref(self.set)))
+        self._attach()
+        assert self.n_kyokus == len(self.end_scores), "the stream's start_kyoku records and the parsed rounds disagree"
+
+    @staticmethod
+    def _check(features, rule):
+        if features not in abi.FEATURES:
+            raise ValueError(f"unknown feature set {features!r}: one of {sorted(abi.FEATURES)}")
+        if rule not in (None, "tenhou", "mjsoul"):
+            raise ValueError(f"Unknown rule: '{rule}'. Expected 'tenhou' or 'mjsoul'")
+
+    def _configure(self, n_logs, game_mode, features, n_slots, gamma, include_pass, skip_single_action, rule, device, share_stream, kyoku_scale):
+        """the settings every constructor shares (no device work)"""
+        import torch
+
+        self.torch = torch
+        self.M = int(n_logs)
+        self.rule, self._device_index = rule, int(device)
+        self._d_start = self._d_end = None    # device score tables (sets parsed from text)
+        self._h_start = self._h_end = None
+        self.game_mode = vecenv._mode_id(game_mode)
+        self.sanma = self.game_mode >= 3
+        self.n_players = 3 if self.sanma else 4
+        self.features, self._feat = features, abi.FEATURES[features]
+        self.channels, self.width = abi.FEATURE_CHANNELS[self._feat], 27 if self.sanma else 34
+        self.A = abi.ACTION_SPACE_3P if self.sanma else abi.ACTION_SPACE_4P
+        self.n_slots = self.M if n_slots is None else int(n_slots)
+        if self.n_slots > self.M or (self.M and self.n_slots < 1):
+            raise ValueError(f"n_slots must be between 1 and the number of logs ({self.M})")
+        self.gamma, self.kyoku_scale = float(gamma), float(kyoku_scale)
+        self.include_pass, self.skip_single_action = bool(include_pass), bool(skip_single_action)
+        self.device = torch.device("cuda", device)
+        self.shared = bool(share_stream)
+        self._finalized = False
+        self._emitted = None    # what samples() returned last, until run() / finalize() / clear()
+        self.h = self.set = self.env = None
+
+    def _set_capacity(self, capacity):
+        self.capacity = int(capacity)
+        if self.capacity <= 0:
+            raise ValueError("capacity must be positive (samples)")
+
+    # the kyoku score tables: host arrays for dict logs; for a set parsed from text they stay on the device and a host copy is made only
+    # when the attribute is read
+    @property
+    def start_scores(self):
+        if self._h_start is None and self._d_start is not None:
+            self._h_start = self._d_start.cpu().numpy()
+        return self._h_start
+
+    @start_scores.setter
+    def start_scores(self, v):
+        self._h_start = v
+
+    @property
+    def end_scores(self):
+        if self._h_end is None and self._d_end is not None:
+            self._h_end = self._d_end.cpu().numpy()
+        return self._h_end
+
+    @end_scores.setter
+    def end_scores(self, v):
+        self._h_end = v
+
+    def _attach(self):
+        """the environment, the replay and the pool views over self.set (whichever call made it)"""
+        from .torch_env import _CudaArray
+
+        torch, L, device, rule = self.torch, self.L, self._device_index, self.rule
         info = abi.LogsetInfo()
         self.kyoku_offsets = np.zeros(self.M + 1, dtype=np.uint32)
         vecenv._chk(L.rmj_logset_info(self.set, C.byref(info), self.kyoku_offsets.ctypes.data))
         self.n_kyokus = int(info.n_kyokus)
-        assert self.n_kyokus == len(self.end_scores), "the stream's start_kyoku records and the parsed rounds disagree"
         bits = abi.RULE_MJSOUL if rule == "mjsoul" else abi.RULE_TENHOU
         self.env = vecenv.VecRiichiEnv(self.n_slots, game_mode=self.game_mode, seed=0, rule_bits=bits, device=device, skip_mjai_logging=True)
         if self.shared:
@@ -195,6 +303,131 @@ class LogSampleBuilder:
                      "log_status": wrap(v.log_status, (self.M,), "|u1"), "traj_len": wrap(v.traj_len, (K, 4), "<i4"),
                      "traj_broken": wrap(v.traj_broken, (K, 4), "|u1"), "counters": wrap(v.counters, (6,), "<i4")}
         self._sync()
+
+    # ---- log sets parsed from MJAI text on the device (rmj_logset_create_from_text)
+    @classmethod
+    def _from_set(cls, make_set, n_logs, game_mode, features, n_slots, capacity, gamma, include_pass, skip_single_action, rule, device, share_stream,
+                  kyoku_scale, on_error, ingest_seconds):
+        """make_set(keep) -> rmj_logset handle over the caller's logs `keep` (None: all of them)"""
+        import time
+
+        if on_error not in ("raise", "drop"):
+            raise ValueError("on_error is 'raise' or 'drop'")
+        cls._check(features, rule)
+        self = cls.__new__(cls)
+        self.logs = None
+        L = self.L = vecenv.load_lib()
+        t0 = time.perf_counter()
+        handle = make_set(None)
+        status = np.zeros(max(n_logs, 1), np.uint8)
+        line = np.zeros(max(n_logs, 1), np.uint32)
+        vecenv._chk(L.rmj_logset_status(handle, status.ctypes.data, line.ctypes.data, None, None))
+        bad = np.flatnonzero(status[:n_logs])
+        self.log_ids, self.dropped = np.arange(n_logs, dtype=np.int64), []
+        if bad.size:
+            self.dropped = [(int(i), int(line[i]), abi.LOGTEXT_STATUS_NAMES[int(status[i])]) for i in bad]
+            L.rmj_logset_destroy(handle)
+            if on_error == "raise":
+                i, ln, st = self.dropped[0]
+                raise ValueError(f"log {i}: line {ln}: {st} ({len(self.dropped)} of {n_logs} logs do not parse; on_error='drop' skips them)")
+            self.log_ids = np.flatnonzero(status[:n_logs] == 0).astype(np.int64)
+            handle = make_set(self.log_ids)    # one more create call over the ranges of the good logs
+        try:
+            self._configure(len(self.log_ids), game_mode, features, n_slots, gamma, include_pass, skip_single_action, rule, device, share_stream, kyoku_scale)
+        except Exception:
+            L.rmj_logset_destroy(handle)
+            raise
+        self.set = handle
+        self.host_seconds = {"ingest": ingest_seconds + time.perf_counter() - t0}
+        try:
+            if self.M == 0:
+                self.kyoku_offsets, self.lengths = np.zeros(1, dtype=np.uint32), np.zeros(0, dtype=np.int64)
+                self._h_start = self._h_end = np.zeros((0, 4), np.int32)
+                self._set_capacity(64 if capacity is None else capacity)
+                L.rmj_logset_destroy(self.set)
+                self.set = None
+                return self
+            dec = np.zeros(self.M, np.uint32)
+            off = np.zeros(self.M + 1, np.uint32)
+            vecenv._chk(L.rmj_logset_status(self.set, None, None, dec.ctypes.data, off.ctypes.data))
+            self.lengths = np.diff(off.astype(np.int64))
+            self._set_capacity(2 * int(dec.sum(dtype=np.int64)) + 64 if capacity is None else capacity)
+            self._attach()
+            v = abi.LogsetViews()
+            vecenv._chk(L.rmj_logset_views(self.set, C.byref(v)))
+            from .torch_env import _CudaArray
+
+            K = self.n_kyokus
+            wrap = lambda ptr: self.torch.as_tensor(_CudaArray(ptr, (K, 4), "<i4", self), device=self.device)  # noqa: E731
+            if K:
+                self._d_start, self._d_end = wrap(v.start_scores), wrap(v.end_scores)
+            else:
+                self._d_start = self._d_end = self.torch.zeros((0, 4), dtype=self.torch.int32, device=self.device)
+        except Exception:
+            self.close()
+            raise
+        return self
+
+    @classmethod
+    def from_text(cls, text, ranges=None, game_mode=2, features="base", n_slots=None, capacity=None, gamma=0.99, include_pass=True, skip_single_action=True,
+                  rule=None, device=0, share_stream=True, masked_ok=False, kyoku_scale=1.0 / 1000.0, on_error="raise"):
+        """The builder over MJAI JSONL text parsed on the device (no Python work per event).  text: bytes / bytearray / numpy uint8 with
+        ranges [M, 2] (begin, end) byte ranges of the logs (any order, gaps allowed) - or, with ranges=None, a list of per-log byte strings.
+        on_error: "raise" - a ValueError naming the first log that does not parse, its line and status; "drop" - the set is rebuilt from
+        the good logs: `log_ids[i]` is the caller's index of set log i (the `log` field of the samples counts set logs) and `dropped`
+        lists (log, line, status) of the others.  The other arguments and every method are LogSampleBuilder's."""
+        import time
+
+        t0 = time.perf_counter()
+        buf, rng = _text_and_ranges(text, ranges)
+        n_players = 3 if vecenv._mode_id(game_mode) >= 3 else 4
+        flags = abi.LOGTEXT_MASKED_OK if masked_ok else 0
+
+        def make_set(keep):
+            r = rng if keep is None else np.ascontiguousarray(rng[keep])
+            h = C.c_void_p()
+            vecenv._chk(vecenv.load_lib().rmj_logset_create_from_text(int(device), buf.ctypes.data, r.ctypes.data, len(r), n_players, flags, C.byref(h)))
+            return h
+
+        return cls._from_set(make_set, len(rng), game_mode, features, n_slots, capacity, gamma, include_pass, skip_single_action, rule, device, share_stream,
+                             kyoku_scale, on_error, time.perf_counter() - t0)
+
+    @classmethod
+    def from_jsonl(cls, paths, **kw):
+        """from_text over JSONL files read on the host: one log per path; gzip is detected by its magic bytes and decompressed with Python's
+        gzip (as MjaiReplay.from_jsonl does)."""
+        return cls.from_text([_read_log_file(p) for p in paths], **kw)
+
+    @classmethod
+    def from_device_text(cls, text, offsets, game_mode=2, features="base", n_slots=None, capacity=None, gamma=0.99, include_pass=True, skip_single_action=True,
+                         rule=None, device=None, share_stream=True, masked_ok=False, kyoku_scale=1.0 / 1000.0, on_error="raise"):
+        """The builder over text that already lies in device memory: the (text uint8, offsets int64 [M + 1]) tensors of
+        TorchVecEnv.drain_text - log i is text[offsets[i]:offsets[i + 1]].  The text is only read during this call (clone nothing).  Torch's
+        current stream is synchronised first: the create call runs on the library's own stream order."""
+        import time
+
+        import torch
+
+        t0 = time.perf_counter()
+        if not (text.is_cuda and offsets.is_cuda) or text.dtype != torch.uint8:
+            raise ValueError("from_device_text takes a uint8 text tensor and an offsets tensor on the GPU")
+        dev = text.device.index if device is None else int(device)
+        text = text.contiguous()
+        o = offsets.to(torch.int64)
+        rng = torch.stack([o[:-1], o[1:]], dim=1).contiguous().view(torch.int64)
+        n_players = 3 if vecenv._mode_id(game_mode) >= 3 else 4
+        flags = abi.LOGTEXT_ON_DEVICE | (abi.LOGTEXT_MASKED_OK if masked_ok else 0)
+
+        def make_set(keep):
+            r = rng if keep is None else rng[torch.as_tensor(keep, device=rng.device)].contiguous()
+            torch.cuda.current_stream(text.device).synchronize()
+            h = C.c_void_p()
+            vecenv._chk(vecenv.load_lib().rmj_logset_create_from_text(dev, C.c_void_p(text.data_ptr() if text.numel() else 0), C.c_void_p(r.data_ptr() if r.numel() else 0),
+                                                                      int(r.shape[0]), n_players, flags, C.byref(h)))
+            return h
+
+        return cls._from_set(make_set, int(rng.shape[0]), game_mode, features, n_slots, capacity, gamma, include_pass, skip_single_action, rule, dev, share_stream,
+                             kyoku_scale, on_error, time.perf_counter() - t0)
 
     # ---- stream order (a builder that keeps the library's own stream synchronises around every call)
     def _pre(self):
@@ -236,7 +469,11 @@ class LogSampleBuilder:
         return int(left.value)
 
     def default_rewards(self):
-        """[K, 4] float64: the seats' score change of every kyoku times kyoku_scale"""
+        """[K, 4] float64: the seats' score change of every kyoku times kyoku_scale (a device tensor, computed there, when the set was parsed
+        from text: no host round trip)"""
+        if self._d_end is not None:
+            t = self.torch
+            return (self._d_end.to(t.float64) - self._d_start.to(t.float64)) * self.kyoku_scale
         return (self.end_scores.astype(np.float64) - self.start_scores.astype(np.float64)) * self.kyoku_scale
 
     def finalize(self, rewards=None):
@@ -251,7 +488,10 @@ class LogSampleBuilder:
         assert rw.shape[0] == self.n_kyokus, f"the reward table needs one row per kyoku ({self.n_kyokus})"
         if rw.shape[0] == 0:
             rw = t.zeros((1, 4), dtype=t.float64, device=self.device)
-        es = t.as_tensor(self.end_scores if len(self.end_scores) else np.zeros((1, 4), np.int32), dtype=t.int32).to(self.device).contiguous()
+        if self._d_end is not None:
+            es = self._d_end if self.n_kyokus else t.zeros((1, 4), dtype=t.int32, device=self.device)
+        else:
+            es = t.as_tensor(self.end_scores if len(self.end_scores) else np.zeros((1, 4), np.int32), dtype=t.int32).to(self.device).contiguous()
         self._pre()
         vecenv._chk(self.L.rmj_logreplay_finalize_device(self.h, C.c_void_p(rw.data_ptr()), C.c_void_p(es.data_ptr())))
         self._sync()

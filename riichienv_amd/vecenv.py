@@ -41,6 +41,7 @@ EXPORTS = [
     "rmj_logset_create", "rmj_logset_destroy", "rmj_logset_info", "rmj_logreplay_assign", "rmj_logreplay_create", "rmj_logreplay_destroy",
     "rmj_logreplay_run_device", "rmj_logreplay_finalize_device", "rmj_logreplay_emit_device", "rmj_logreplay_views", "rmj_logreplay_counts",
     "rmj_logreplay_clear",
+    "rmj_logset_create_from_text", "rmj_logset_views", "rmj_logset_status",
 ]
 
 
@@ -180,6 +181,9 @@ def load_lib():
     L.rmj_ppo_clear.argtypes = [vp]
     L.rmj_logset_create.argtypes = [C.c_int, vp, vp, C.c_uint32, C.POINTER(vp)]
     L.rmj_logset_destroy.argtypes = [vp]
+    L.rmj_logset_create_from_text.argtypes = [C.c_int, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(vp)]
+    L.rmj_logset_views.argtypes = [vp, C.POINTER(abi.LogsetViews)]
+    L.rmj_logset_status.argtypes = [vp, vp, vp, vp, vp]
     L.rmj_logset_info.argtypes = [vp, C.POINTER(abi.LogsetInfo), vp]
     L.rmj_logreplay_assign.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.POINTER(C.c_uint32)]
     L.rmj_logreplay_create.argtypes = [vp, vp, C.POINTER(abi.LogReplayConfig), C.POINTER(vp)]
