@@ -236,8 +236,10 @@ __global__ __launch_bounds__(256) void k_lt_tables(const rmjp::Side* __restrict_
         const uint32_t cls = w[8] & 0xFFu, flags = (w[8] >> 8) & 0xFFu, actor = (w[9] >> 8) & 0xFFu;
         uint32_t before = __shfl_up(cls, 1u);
         if (lane == 0) before = prev_cls;
-        // what the walk must see: every class but a dahai of a seat every kyoku has, and whatever follows a hora (it ends the batch of horas)
-        const bool plain = cls == rmjp::CLS_OTHER || (cls == rmjp::CLS_DAHAI && !(flags & rmjp::SF_ACTOR_NONE) && actor < 3u);
+        // what the walk must see: every class but a dahai of a seat every kyoku has, and whatever follows a hora (it ends the batch of horas).
+        // A kyoku with fewer than three scores has no such seat: while one is open, or opens in this tile, every dahai is fed.
+        const bool narrow = (walk.open && walk.n_raw < 3u) || __ballot(cls == rmjp::CLS_START_KYOKU && ((w[8] >> 16) & 0xFFu) < 3u) != 0ull;
+        const bool plain = cls == rmjp::CLS_OTHER || (cls == rmjp::CLS_DAHAI && !(flags & rmjp::SF_ACTOR_NONE) && actor < 3u && !narrow);
         unsigned long long m = __ballot(i < e1 && (!plain || before == rmjp::CLS_HORA));
         while (m) {
             const int j = __builtin_ctzll(m);
