@@ -660,6 +660,34 @@ int rmj_logset_views(rmj_logset_handle s, RmjLogsetViews* out);
  * rmj_logset_create. */
 int rmj_logset_status(rmj_logset_handle s, uint8_t* status /*[n_logs]*/, uint32_t* error_line /*[n_logs]*/, uint32_t* decisions /*[n_logs]*/,
                       uint32_t* offsets /*[n_logs + 1]*/);
+/* GRP rank-model rows: the input of riichienv-ml's rank model (datasets/grp_dataset.py GrpReplayDataset._encode_features, the same
+ * layout as RewardPredictor.calc_all_player_rewards) for every seat of a round.  The row of seat p, n = num_players (3 or 4), is
+ * 4n + 4 float32:
+ *     init[0..n) / S, end[0..n) / S, delta[0..n) / 12000, chang / 3, ju / 3, ben / 4, liqibang / 4, onehot(p)[0..n)
+ * S = 25000 (4P) or 35000 (3P), delta = end - init.  Every quotient is the float64 division of the integer by the constant rounded
+ * once to float32 (Python's int / float, then np.float32): bit-equal to the reference's rows.
+ * Both calls are asynchronous on `hip_stream` (a hipStream_t, as rmj_set_stream takes it; NULL = the null stream), allocate nothing and
+ * wait for nothing.  Every table pointer is a device pointer, 16-byte aligned.
+ *
+ * rmj_grp_rows_device: the pure form - init, delta, meta int32 [rows][4] -> x [rows][n][4n + 4]; meta = (chang, ju, ben, liqibang),
+ * what rmj_round_track_device writes (the live / PPO path: init = the scores when the round was dealt, end = init + delta). */
+int rmj_grp_rows_device(int device, const int32_t* d_init, const int32_t* d_delta, const int32_t* d_meta, uint32_t rows, uint32_t num_players, float* d_x,
+                        void* hip_stream);
+/* rmj_logset_grp_device: one row block per kyoku of a log set, in table order kyoku_offsets[log] + kyoku - 1.  meta is read from the
+ * kyoku's START_KYOKU record: chang = the bakaze index, ju = kyoku - 1 (-1 for "kyoku": 0, like the host), ben = honba, liqibang = both
+ * kyotaku bytes.  rank = the seat's place (0 = first) in the end scores of its LOG'S LAST kyoku - GrpReplayDataset's label: a stable
+ * descending sort, ties to the lower seat - or 255 for every kyoku of a log whose status is not RMJ_LOGTEXT_OK (x is still written, from
+ * whatever the tables hold).  log_of = the kyoku's log.  A log without a kyoku contributes nothing.  start_scores / end_scores
+ * [n_kyokus][4]: NULL = the set's own tables (a set parsed from text); a set made by rmj_logset_create has none and RMJ_ERR_ARG is
+ * returned when they are NULL.  Any output may be NULL, except that x needs meta. */
+typedef struct RmjGrpOut {
+    int32_t* meta;      /* [n_kyokus][4] chang, ju, ben, liqibang */
+    float* x;           /* [n_kyokus][n][4n + 4] */
+    uint8_t* rank;      /* [n_kyokus][n] */
+    uint32_t* log_of;   /* [n_kyokus] */
+} RmjGrpOut;
+int rmj_logset_grp_device(rmj_logset_handle s, uint32_t num_players, const int32_t* d_start_scores, const int32_t* d_end_scores, const RmjGrpOut* out,
+                          void* hip_stream);
 /* Which slot replays which logs (host only, no device needed): the logs are handed out in log order, each to the slot that is free
  * first when every event takes one step, ties to the lowest slot - a pure function of (n_logs, n_slots, the logs' lengths), so the
  * order of the samples is the same run after run.  slot_of_log [n_logs]; slot s replays slot_logs[slot_first[s] .. slot_first[s + 1])

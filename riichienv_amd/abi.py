@@ -293,6 +293,10 @@ class LogReplayCounts(C.Structure):  # RmjLogReplayCounts
     _fields_ = [(k, C.c_uint32) for k in ("fill", "overflowed", "failed_logs", "complete_logs", "decisions", "events", "steps_done", "steps_left")]
 
 
+class GrpOut(C.Structure):           # RmjGrpOut (rmj_logset_grp_device): device pointers, any may be NULL (x needs meta)
+    _fields_ = [(k, C.c_void_p) for k in ("meta", "x", "rank", "log_of")]
+
+
 class BenchResult(C.Structure):
     _fields_ = [("total_ms", C.c_double), ("step_kernel_ms", C.c_double), ("env_steps", C.c_uint64),
                 ("launches", C.c_uint32), ("launches_in_flight", C.c_uint32), ("full_path_steps", C.c_uint64),

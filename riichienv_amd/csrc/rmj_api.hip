@@ -843,6 +843,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RMJ_ENCX_WAV
 }
 #include "rmj_logreplay.hip.h"
 #include "rmj_logtext.hip.h"
+#include "rmj_grp.hip.h"
 
 // ---- auxiliary encoders (row N3): kawa overview, yaku possibility, furiten-ron possibility ----------------------
 // One wave per game; absolute seat order, public information only (the same for every observing seat).
@@ -3472,6 +3473,41 @@ int rmj_logset_status(rmj_logset_handle s, uint8_t* status, uint32_t* error_line
     if (error_line && s->M) HIPCHK(hipMemcpy(error_line, s->d_errline, (size_t)s->M * 4, hipMemcpyDeviceToHost));
     if (decisions && s->M) HIPCHK(hipMemcpy(decisions, s->d_dec, (size_t)s->M * 4, hipMemcpyDeviceToHost));
     if (offsets) memcpy(offsets, s->off.data(), (size_t)(s->M + 1) * 4);
+    return RMJ_OK;
+}
+// ---- GRP rank-model rows (rmj_grp.hip.h): asynchronous on the caller's stream, nothing allocated, nothing waited for
+static bool grp_aligned(const void* p) { return ((uintptr_t)p & 15u) == 0u; }
+int rmj_grp_rows_device(int device, const int32_t* d_init, const int32_t* d_delta, const int32_t* d_meta, uint32_t rows, uint32_t num_players, float* d_x,
+                        void* hip_stream) {
+    using namespace rmjgrp;
+    if (num_players != 3u && num_players != 4u) return fail(RMJ_ERR_ARG, "rmj_grp_rows_device: num_players is 3 or 4");
+    if (!rows) return RMJ_OK;
+    if (!d_init || !d_delta || !d_meta || !d_x) return fail(RMJ_ERR_ARG, "null argument");
+    if (!grp_aligned(d_init) || !grp_aligned(d_delta) || !grp_aligned(d_meta) || !grp_aligned(d_x))
+        return fail(RMJ_ERR_ARG, "rmj_grp_rows_device: the tables must be 16-byte aligned");
+    HIPCHK(hipSetDevice(device));
+    hipLaunchKernelGGL(k_grp_rows<false>, grp_rows_grid(rows, num_players), dim3(GRP_BLOCK), 0, (hipStream_t)hip_stream, d_init, d_delta, d_meta, rows, num_players, d_x);
+    HIPCHK(hipGetLastError());
+    return RMJ_OK;
+}
+int rmj_logset_grp_device(rmj_logset_handle s, uint32_t num_players, const int32_t* d_start_scores, const int32_t* d_end_scores, const RmjGrpOut* out, void* hip_stream) {
+    using namespace rmjgrp;
+    if (!s || !out) return fail(RMJ_ERR_ARG, "null argument");
+    if (num_players != 3u && num_players != 4u) return fail(RMJ_ERR_ARG, "rmj_logset_grp_device: num_players is 3 or 4");
+    const int32_t* st = d_start_scores ? d_start_scores : s->d_start;
+    const int32_t* en = d_end_scores ? d_end_scores : s->d_end;
+    if (!st || !en) return fail(RMJ_ERR_ARG, "rmj_logset_grp_device: a set made by rmj_logset_create holds no score tables: pass start_scores and end_scores");
+    if (!s->K) return RMJ_OK;
+    if (out->x && !out->meta) return fail(RMJ_ERR_ARG, "rmj_logset_grp_device: x is computed from meta: give both");
+    if (!grp_aligned(st) || !grp_aligned(en) || !grp_aligned(out->meta) || !grp_aligned(out->x))
+        return fail(RMJ_ERR_ARG, "rmj_logset_grp_device: the tables must be 16-byte aligned");
+    HIPCHK(hipSetDevice(s->device));
+    hipStream_t stream = (hipStream_t)hip_stream;
+    hipLaunchKernelGGL(k_grp_logs, dim3((s->M + GRP_BLOCK / 64u - 1u) / (GRP_BLOCK / 64u)), dim3(GRP_BLOCK), 0, stream, (const RmjEvent*)s->d_ev, (const uint32_t*)s->d_off,
+                       (const uint32_t*)s->d_koff, s->M, (const uint8_t*)s->d_status, en, num_players, out->meta, out->rank, out->log_of);
+    if (out->x)
+        hipLaunchKernelGGL(k_grp_rows<true>, grp_rows_grid(s->K, num_players), dim3(GRP_BLOCK), 0, stream, st, en, (const int32_t*)out->meta, s->K, num_players, out->x);
+    HIPCHK(hipGetLastError());
     return RMJ_OK;
 }
 int rmj_logreplay_assign(const uint32_t* offsets, uint32_t n_logs, uint32_t n_slots, uint32_t* slot_of_log, uint32_t* slot_logs, uint32_t* slot_first, uint32_t* steps) {

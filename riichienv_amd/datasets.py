@@ -476,6 +476,13 @@ class LogSampleBuilder:
             return (self._d_end.to(t.float64) - self._d_start.to(t.float64)) * self.kyoku_scale
         return (self.end_scores.astype(np.float64) - self.start_scores.astype(np.float64)) * self.kyoku_scale
 
+    def grp_rows(self, num_players=None):
+        """riichienv_amd.grp.grp_rows(self): the GRP rank model's rows x, labels rank, meta, log_of of every kyoku, on the device - with a
+        model, grp.DeviceRewardPredictor(model, pts_weight).kyoku_rewards(self) is the table finalize() takes"""
+        from .grp import grp_rows
+
+        return grp_rows(self, num_players)
+
     def finalize(self, rewards=None):
         """returns and ranks of the pool's samples (rmj_logreplay_finalize_device); rewards: [K, 4] float64 (numpy or torch) by kyoku
         row, default default_rewards()"""

@@ -42,6 +42,7 @@ EXPORTS = [
     "rmj_logreplay_run_device", "rmj_logreplay_finalize_device", "rmj_logreplay_emit_device", "rmj_logreplay_views", "rmj_logreplay_counts",
     "rmj_logreplay_clear",
     "rmj_logset_create_from_text", "rmj_logset_views", "rmj_logset_status",
+    "rmj_grp_rows_device", "rmj_logset_grp_device",
 ]
 
 
@@ -194,6 +195,8 @@ def load_lib():
     L.rmj_logreplay_views.argtypes = [vp, C.POINTER(abi.LogReplayViews)]
     L.rmj_logreplay_counts.argtypes = [vp, C.POINTER(abi.LogReplayCounts)]
     L.rmj_logreplay_clear.argtypes = [vp]
+    L.rmj_grp_rows_device.argtypes = [C.c_int, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp]
+    L.rmj_logset_grp_device.argtypes = [vp, C.c_uint32, vp, vp, C.POINTER(abi.GrpOut), vp]
     _LIB = L
     return L
 
