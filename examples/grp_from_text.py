@@ -1,4 +1,4 @@
-"""The GRP rank model end to end on the device: MJAI text -> GrpDataset -> a few optimiser steps of a 4n+4 -> 128 -> 64 -> n MLP ->
+"""The GRP rank model end to end on the device: MJAI text -> one LogSet -> GrpDataset -> a few optimiser steps of a 4n+4 -> 128 -> 64 -> n MLP ->
 DeviceRewardPredictor.kyoku_rewards -> LogSampleBuilder.finalize -> one BC/CQL batch whose returns are the model's rewards.
 
     python examples/grp_from_text.py --games 64 --steps 50
@@ -15,9 +15,10 @@ def main(games=64, steps=50, batch_size=256):
 
     from riichienv_amd.datasets import LogSampleBuilder
     from riichienv_amd.grp import DeviceRewardPredictor, GrpDataset
+    from riichienv_amd.logset import LogSet
     from riichienv_amd.torch_env import TorchVecEnv
 
-    # self-play text that never leaves the device (any MJAI JSONL works: GrpDataset.from_jsonl(paths))
+    # self-play text that never leaves the device (any MJAI JSONL works: LogSet.from_jsonl(paths))
     env = TorchVecEnv(games, game_mode=2, seed=1, skip_mjai_logging=False, event_ring=8192)
     env.env.reset()
     for _ in range(40):
@@ -27,7 +28,8 @@ def main(games=64, steps=50, batch_size=256):
     text, offsets = env.drain_text(cursor=env.env.log_positions()[0].copy(), peek=True)
 
     n = 4
-    ds = GrpDataset.from_device_text(text, offsets, game_mode=2)
+    logset = LogSet.from_device_text(text, offsets, num_players=n)      # parsed once, for both stages
+    ds = GrpDataset.from_logset(logset)
     nn = torch.nn
     model = nn.Sequential(nn.Linear(4 * n + 4, 128), nn.ReLU(), nn.Linear(128, 64), nn.ReLU(), nn.Linear(64, n)).cuda()
     opt = torch.optim.Adam(model.parameters(), lr=1e-3)
@@ -44,7 +46,7 @@ def main(games=64, steps=50, batch_size=256):
     print("GRP rows:", int(ds.tensors()["x"].shape[0]), "loss after", steps, "steps:", round(float(loss), 4))
 
     # the trained model's reward per (kyoku, seat) -> the returns of the BC/CQL samples
-    b = LogSampleBuilder.from_device_text(text, offsets, game_mode=2)
+    b = LogSampleBuilder.from_logset(logset, game_mode=2)
     rewards = DeviceRewardPredictor(model, [10.0, 4.0, -4.0, -10.0], num_players=n).kyoku_rewards(b)
     b.run()
     b.finalize(rewards)
@@ -54,6 +56,7 @@ def main(games=64, steps=50, batch_size=256):
     print("rewards of", out["kyokus"], "kyokus ->", out["samples"], "samples; one batch:", out["batch"], "|G_t| max", round(out["target_abs_max"], 4))
     b.close()
     ds.close()
+    logset.close()
     env.env.close()
     return out
 

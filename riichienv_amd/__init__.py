@@ -6,8 +6,8 @@ ActionType, Observation, Meld, MeldType, Phase, GameRule, GameType, RandomAgent 
 HandEvaluator3P, Wind, WinResult, Score, calculate_score, calculate_shanten, calculate_shanten_3p, check_riichi_candidates,
 parse_hand, parse_tile (riichienv_amd.hand); MjaiReplay, MjSoulReplay, Kyoku, WinResultContext (riichienv_amd.replay); Yaku, get_yaku_by_id, get_all_yaku
 (riichienv_amd.yaku_table); the
-`convert` and `consts` modules.  PPOCollector (riichienv_amd.ppo), LogSampleBuilder (riichienv_amd.datasets) and grp_rows, GrpDataset,
-DeviceRewardPredictor (riichienv_amd.grp) are the device-side training feeds.
+`convert` and `consts` modules.  PPOCollector (riichienv_amd.ppo), LogSet (riichienv_amd.logset), LogSampleBuilder
+(riichienv_amd.datasets) and grp_rows, GrpDataset, DeviceRewardPredictor (riichienv_amd.grp) are the device-side training feeds.
 """
 from .vecenv import VecRiichiEnv, RmjError, load_lib  # noqa: F401
 
@@ -18,6 +18,7 @@ _LAZY = {
     "replay": ("MjaiReplay", "MjSoulReplay", "Kyoku", "WinResultContext"),
     "yaku_table": ("Yaku", "get_yaku_by_id", "get_all_yaku"),
     "ppo": ("PPOCollector",),
+    "logset": ("LogSet",),
     "datasets": ("LogSampleBuilder",),
     "grp": ("grp_rows", "GrpDataset", "DeviceRewardPredictor"),
 }

@@ -8,7 +8,8 @@ The rows come from the records and score tables a log set already holds on the d
 tracker's tensors of live games (rmj_grp_rows_device): csrc/rmj_grp.hip.h.  Torch is used for the model, for device memory and for
 the element-wise ops around the two calls.
 
-    grp_rows(builder)                   x, rank, meta, log_of, kyoku_offsets of every kyoku of a LogSampleBuilder / GrpDataset
+    grp_rows(source)                    x, rank, meta, log_of, kyoku_offsets of every kyoku of a LogSet (logset.py: the one owner of the
+                                        device log set), or of the set of a LogSampleBuilder / GrpDataset
     GrpDataset                          GrpReplayDataset's (x, one-hot rank) stream from logs, text, JSONL files or device text
     DeviceRewardPredictor               the [K, 4] reward table LogSampleBuilder.finalize takes, and PPOCollector's reward_fn"""
 from __future__ import annotations
@@ -18,10 +19,20 @@ import time
 
 import numpy as np
 
-from . import abi, vecenv
-from .datasets import _events_of, _read_log_file, _text_and_ranges, kyoku_tables, pack_logs
+from . import vecenv
+from .logset import LogSet, check_on_error
 
 _BUILDER_ONLY = ("features", "n_slots", "capacity", "gamma", "include_pass", "skip_single_action", "rule", "share_stream", "kyoku_scale")
+_KEEP = {"raise": "raise", "drop": "keep"}    # GrpDataset's "drop" keeps the log in the set: its kyokus get rank 255 and tensors() filters them
+
+
+def _players(game_mode, kw, on_error="raise"):
+    """the arguments of GrpDataset's constructors, checked before any device work; returns the number of players"""
+    unknown = set(kw) - set(_BUILDER_ONLY)
+    if unknown:
+        raise TypeError(f"unexpected arguments {sorted(unknown)}")
+    check_on_error(on_error, ("raise", "drop"))
+    return 3 if vecenv._mode_id(game_mode) >= 3 else 4
 
 
 def _stream_ptr(torch, device):
@@ -45,34 +56,9 @@ def live_rows(init, delta, meta, num_players, out=None):
 
 
 def grp_rows(source, num_players=None):
-    """The GRP rows of every kyoku of `source` - a LogSampleBuilder (from dicts, text, JSONL or device text) or a GrpDataset - as device
-    tensors, in table order `kyoku_offsets[log] + kyoku - 1`:
-      x [K, n, 4n + 4] f32, meta [K, 4] i32 (chang, ju, ben, liqibang), rank [K, n] u8 (the seat's place in its LOG'S final scores,
-      GrpReplayDataset's label; 255 for the kyokus of a log that did not parse), log_of [K] i32, kyoku_offsets [M + 1] i64.
-    num_players defaults to the source's.  Asynchronous on torch's current stream; nothing is read back."""
-    import torch
-
-    n = int(source.n_players if num_players is None else num_players)
-    dev = source.device
-    K, M = int(getattr(source, "n_kyokus", 0) or 0), int(source.M)
-    out = {"x": torch.empty((K, n, 4 * n + 4), dtype=torch.float32, device=dev), "meta": torch.zeros((K, 4), dtype=torch.int32, device=dev),
-           "rank": torch.full((K, n), 255, dtype=torch.uint8, device=dev), "log_of": torch.zeros((K,), dtype=torch.int32, device=dev),
-           "kyoku_offsets": torch.as_tensor(np.asarray(source.kyoku_offsets, dtype=np.int64), device=dev)}
-    if not K or not M or not source.set:
-        return out
-    if source._d_start is not None:
-        start = end = None                     # the set's own tables
-    else:
-        start = torch.as_tensor(np.ascontiguousarray(source.start_scores, dtype=np.int32), device=dev)
-        end = torch.as_tensor(np.ascontiguousarray(source.end_scores, dtype=np.int32), device=dev)
-    o = abi.GrpOut(out["meta"].data_ptr(), out["x"].data_ptr(), out["rank"].data_ptr(), out["log_of"].data_ptr())
-    stream = torch.cuda.current_stream(dev)
-    vecenv._chk(vecenv.load_lib().rmj_logset_grp_device(source.set, n, None if start is None else C.c_void_p(start.data_ptr()),
-                                                        None if end is None else C.c_void_p(end.data_ptr()), C.byref(o), C.c_void_p(stream.cuda_stream)))
-    if start is not None:
-        start.record_stream(stream)
-        end.record_stream(stream)
-    return out
+    """LogSet.grp_rows of `source` - a LogSet, or the set of a LogSampleBuilder or a GrpDataset: the GRP rows of every kyoku as device
+    tensors.  num_players defaults to the set's.  Asynchronous on torch's current stream; nothing is read back."""
+    return (source if isinstance(source, LogSet) else source.logset).grp_rows(num_players)
 
 
 class GrpDataset:
@@ -82,132 +68,56 @@ class GrpDataset:
     the log - built on the device, without its file shuffling: batches() draws one permutation over all rows.  logs: lists of MJAI event
     dicts, MjaiReplay or MjSoulReplay objects; from_text / from_jsonl / from_device_text parse MJAI JSONL text on the device and take the
     arguments of LogSampleBuilder's constructors of those names (the replay-only ones - features, capacity, gamma, ... - are accepted
-    and unused: no game is replayed).  on_error: "raise" - a ValueError naming the first log that does not parse; "drop" - its rows are
-    left out (`dropped` lists (log, line, status); the `log` field of tensors() keeps the caller's numbering)."""
+    and unused: no game is replayed); from_logset takes a LogSet the caller made (and keeps).  on_error: "raise" - a ValueError naming the
+    first log that does not parse; "drop" - its rows are left out (`dropped` lists (log, line, status); the `log` field of tensors()
+    keeps the caller's numbering)."""
 
     def __init__(self, logs, game_mode=2, device=0, masked_ok=False, **kw):
-        self._configure(game_mode, device, kw)
-        t0 = time.perf_counter()
-        logs = [_events_of(l) for l in logs]
-        self.M = len(logs)
-        self.dropped = []
-        self._h_start, self._h_end = kyoku_tables(logs, self.n_players)
-        self.kyoku_offsets, self.n_kyokus = np.zeros(self.M + 1, dtype=np.uint32), 0
-        if self.M:
-            recs, offsets = pack_logs(logs, self.n_players, masked_ok)
-            self.set = C.c_void_p()
-            vecenv._chk(self.L.rmj_logset_create(self._device_index, C.addressof(recs), offsets.ctypes.data, self.M, C.byref(self.set)))
-            self._info()
-            assert self.n_kyokus == len(self._h_end), "the stream's start_kyoku records and the parsed rounds disagree"
-        self.host_seconds = {"ingest": time.perf_counter() - t0}
-
-    def _configure(self, game_mode, device, kw):
-        import torch
-
-        unknown = set(kw) - set(_BUILDER_ONLY)
-        if unknown:
-            raise TypeError(f"unexpected arguments {sorted(unknown)}")
-        self.torch, self.L = torch, vecenv.load_lib()
-        self.game_mode = vecenv._mode_id(game_mode)
-        self.n_players = 3 if self.game_mode >= 3 else 4
-        self._device_index = int(device)
-        self.device = torch.device("cuda", self._device_index)
-        self.set, self._d_start, self._d_end, self._h_start, self._h_end = None, None, None, None, None
-        self._rows = self._tensors = None
-
-    def _info(self):
-        info = abi.LogsetInfo()
-        self.kyoku_offsets = np.zeros(self.M + 1, dtype=np.uint32)
-        vecenv._chk(self.L.rmj_logset_info(self.set, C.byref(info), self.kyoku_offsets.ctypes.data))
-        self.n_kyokus = int(info.n_kyokus)
-
-    @property
-    def start_scores(self):
-        return self._h_start
-
-    @property
-    def end_scores(self):
-        return self._h_end
+        self._adopt(LogSet.from_logs(logs, _players(game_mode, kw), masked_ok, device), True, game_mode)
 
     @classmethod
-    def _from_set(cls, make_set, n_logs, game_mode, device, kw, on_error, t0):
-        if on_error not in ("raise", "drop"):
-            raise ValueError("on_error is 'raise' or 'drop'")
-        self = cls.__new__(cls)
-        self._configure(game_mode, device, kw)
-        self.M, self.dropped = int(n_logs), []
-        self.kyoku_offsets, self.n_kyokus = np.zeros(self.M + 1, dtype=np.uint32), 0
-        if self.M:
-            self.set = make_set(self.n_players)
-            status, line = np.zeros(self.M, np.uint8), np.zeros(self.M, np.uint32)
-            vecenv._chk(self.L.rmj_logset_status(self.set, status.ctypes.data, line.ctypes.data, None, None))
-            self.dropped = [(int(i), int(line[i]), abi.LOGTEXT_STATUS_NAMES[int(status[i])]) for i in np.flatnonzero(status)]
-            if self.dropped and on_error == "raise":
-                i, ln, st = self.dropped[0]
-                self.close()
-                raise ValueError(f"log {i}: line {ln}: {st} ({len(self.dropped)} of {n_logs} logs do not parse; on_error='drop' skips them)")
-            self._info()
-            self._d_start = True      # the set holds its own tables
-        self.host_seconds = {"ingest": time.perf_counter() - t0}
-        return self
+    def from_logset(cls, logset, **kw):
+        """over a LogSet the caller made: close() leaves the set open"""
+        _players(2, kw)
+        return cls.__new__(cls)._adopt(logset, False)
 
     @classmethod
     def from_text(cls, text, ranges=None, game_mode=2, device=0, masked_ok=False, on_error="raise", **kw):
-        """MJAI JSONL text parsed on the device: text / ranges as LogSampleBuilder.from_text takes them"""
-        t0 = time.perf_counter()
-        buf, rng = _text_and_ranges(text, ranges)
-        flags = abi.LOGTEXT_MASKED_OK if masked_ok else 0
-
-        def make_set(n_players):
-            h = C.c_void_p()
-            vecenv._chk(vecenv.load_lib().rmj_logset_create_from_text(int(device), buf.ctypes.data, rng.ctypes.data, len(rng), n_players, flags, C.byref(h)))
-            return h
-
-        return cls._from_set(make_set, len(rng), game_mode, device, kw, on_error, t0)
+        """MJAI JSONL text parsed on the device: text / ranges as LogSet.from_text takes them"""
+        n = _players(game_mode, kw, on_error)
+        return cls.__new__(cls)._adopt(LogSet.from_text(text, ranges, n, masked_ok, device, _KEEP[on_error]), True, game_mode)
 
     @classmethod
-    def from_jsonl(cls, paths, **kw):
+    def from_jsonl(cls, paths, game_mode=2, device=0, masked_ok=False, on_error="raise", **kw):
         """from_text over JSONL files read on the host: one log per path, gzip detected by its magic bytes"""
-        return cls.from_text([_read_log_file(p) for p in paths], **kw)
+        n = _players(game_mode, kw, on_error)
+        return cls.__new__(cls)._adopt(LogSet.from_jsonl(paths, num_players=n, masked_ok=masked_ok, device=device, on_error=_KEEP[on_error]), True, game_mode)
 
     @classmethod
     def from_device_text(cls, text, offsets, game_mode=2, device=None, masked_ok=False, on_error="raise", **kw):
         """over the (text uint8, offsets int64 [M + 1]) device tensors of TorchVecEnv.drain_text; the text is only read during this call"""
-        import torch
+        n = _players(game_mode, kw, on_error)
+        return cls.__new__(cls)._adopt(LogSet.from_device_text(text, offsets, n, masked_ok, device, _KEEP[on_error]), True, game_mode)
 
-        t0 = time.perf_counter()
-        if not (text.is_cuda and offsets.is_cuda) or text.dtype != torch.uint8:
-            raise ValueError("from_device_text takes a uint8 text tensor and an offsets tensor on the GPU")
-        dev = text.device.index if device is None else int(device)
-        text = text.contiguous()
-        o = offsets.to(torch.int64)
-        rng = torch.stack([o[:-1], o[1:]], dim=1).contiguous()
-        flags = abi.LOGTEXT_ON_DEVICE | (abi.LOGTEXT_MASKED_OK if masked_ok else 0)
+    def _adopt(self, logset, owned, game_mode=None):
+        self.logset, self._owned, self.torch = logset, owned, logset.torch
+        self.game_mode, self.n_players = None if game_mode is None else vecenv._mode_id(game_mode), logset.num_players
+        self.M, self.device, self.kyoku_offsets, self.n_kyokus, self.dropped = logset.M, logset.device, logset.kyoku_offsets, logset.n_kyokus, logset.dropped
+        self.host_seconds = dict(logset.host_seconds)
+        self._rows = self._tensors = None
+        return self
 
-        def make_set(n_players):
-            torch.cuda.current_stream(text.device).synchronize()
-            h = C.c_void_p()
-            vecenv._chk(vecenv.load_lib().rmj_logset_create_from_text(dev, C.c_void_p(text.data_ptr() if text.numel() else 0), C.c_void_p(rng.data_ptr() if rng.numel() else 0),
-                                                                      int(rng.shape[0]), n_players, flags, C.byref(h)))
-            return h
-
-        return cls._from_set(make_set, int(rng.shape[0]), game_mode, dev, kw, on_error, t0)
+    start_scores = property(lambda self: self.logset.start_scores)
+    end_scores = property(lambda self: self.logset.end_scores)
 
     def close(self):
-        if getattr(self, "set", None):
-            self.L.rmj_logset_destroy(self.set)
-        self.set = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        if self._owned:
+            self.logset.close()
 
     def grp_rows(self):
-        """grp_rows(self), computed once"""
+        """the set's grp_rows(), computed once"""
         if self._rows is None:
-            self._rows = grp_rows(self)
+            self._rows = self.logset.grp_rows()
         return self._rows
 
     def tensors(self):

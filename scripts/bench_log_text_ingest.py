@@ -43,6 +43,14 @@ def make_text(n, seed=1):
     return out
 
 
+def text_buffer(texts):
+    """(uint8 buffer, [M, 2] uint64 byte ranges) of per-log byte strings laid end to end: what the timed create calls take"""
+    import numpy as np
+
+    ends = np.cumsum([len(t) for t in texts], dtype=np.uint64)
+    return np.frombuffer(b"".join(texts), np.uint8), np.ascontiguousarray(np.stack([ends - np.array([len(t) for t in texts], np.uint64), ends], axis=1))
+
+
 def best_of(fn, reps=3):
     fn()
     best = None
@@ -87,9 +95,7 @@ def host_ingest(texts):
 def trace_child(n_logs):
     import torch
 
-    from riichienv_amd import datasets
-
-    buf, rng = datasets._text_and_ranges(make_text(n_logs), None)
+    buf, rng = text_buffer(make_text(n_logs))
     create_from_text(buf, rng)
     torch.cuda.synchronize()
     print("TRACE_CHILD " + json.dumps(dict(logs=n_logs, bytes=int(buf.size))))
@@ -139,7 +145,7 @@ def main():
     from riichienv_amd import datasets
 
     texts = make_text(args.logs)
-    buf, rng = datasets._text_and_ranges(texts, None)
+    buf, rng = text_buffer(texts)
     host_ingest(texts[:64])
     runs = [host_ingest(texts) for _ in range(3)]
     a = min(runs, key=lambda r: r["total"])

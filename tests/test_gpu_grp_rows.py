@@ -154,8 +154,8 @@ def test_refused_arguments():
     meta = torch.zeros((K, 4), dtype=torch.int32, device=dev)
     x = torch.zeros((K, 4, 20), dtype=torch.float32, device=dev)
     o = abi.GrpOut(meta.data_ptr(), x.data_ptr(), None, None)
-    assert L.rmj_logset_grp_device(ds.set, 4, None, None, C.byref(o), None) == -1          # a host-packed set has no score tables
-    assert L.rmj_logset_grp_device(ds.set, 5, meta.data_ptr(), meta.data_ptr(), C.byref(o), None) == -1
+    assert L.rmj_logset_grp_device(ds.logset.handle, 4, None, None, C.byref(o), None) == -1          # a host-packed set has no score tables
+    assert L.rmj_logset_grp_device(ds.logset.handle, 5, meta.data_ptr(), meta.data_ptr(), C.byref(o), None) == -1
     assert L.rmj_logset_grp_device(None, 4, None, None, C.byref(o), None) == -1
     assert L.rmj_grp_rows_device(0, meta.data_ptr(), meta.data_ptr(), meta.data_ptr(), K, 2, x.data_ptr(), None) == -1
     assert L.rmj_grp_rows_device(0, None, meta.data_ptr(), meta.data_ptr(), K, 4, x.data_ptr(), None) == -1

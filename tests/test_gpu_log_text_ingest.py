@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from riichienv_amd import abi, datasets, vecenv
+from riichienv_amd.logset import LogSet
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -60,18 +61,15 @@ def _shuffled_text(logs, seed):
 
 def _reference_set(logs, n_players):
     """what pack_logs + rmj_logset_create hold for the dict logs: events bytes, offsets, kyoku_offsets, n_kyokus, longest_log"""
-    L = vecenv.load_lib()
     recs, off = datasets.pack_logs(logs, n_players)
-    h = C.c_void_p()
-    vecenv._chk(L.rmj_logset_create(0, C.addressof(recs), off.ctypes.data, len(logs), C.byref(h)))
-    info, koff = abi.LogsetInfo(), np.zeros(len(logs) + 1, np.uint32)
-    vecenv._chk(L.rmj_logset_info(h, C.byref(info), koff.ctypes.data))
+    s = LogSet.from_logs(logs, n_players)
     v = abi.LogsetViews()
-    vecenv._chk(L.rmj_logset_views(h, C.byref(v)))
+    vecenv._chk(vecenv.load_lib().rmj_logset_views(s.handle, C.byref(v)))
     assert not v.start_scores and not v.end_scores and not v.status and not v.error_line and not v.decisions and v.events and v.offsets
-    L.rmj_logset_destroy(h)
+    s.close()
     n = int(off[-1])
-    return np.frombuffer(bytes(recs), dtype=np.uint8)[: n * 96].reshape(n, 3, 32), off.astype(np.int64), koff.astype(np.int64), int(info.n_kyokus), int(info.longest_log)
+    assert (s.M, s.n_events) == (len(logs), n)
+    return np.frombuffer(bytes(recs), dtype=np.uint8)[: n * 96].reshape(n, 3, 32), off.astype(np.int64), s.kyoku_offsets.astype(np.int64), s.n_kyokus, s.longest_log
 
 
 def _check_parse(texts, logs, n_players, what):
@@ -92,14 +90,9 @@ def _check_parse(texts, logs, n_players, what):
     assert got["end_scores"].cpu().numpy().tolist() == end.tolist(), what
     assert got["decisions"].cpu().tolist() == dec, what
     # n_kyokus and longest_log of the set itself
-    L = vecenv.load_lib()
-    buf, rng = datasets._text_and_ranges(texts, None)
-    h = C.c_void_p()
-    vecenv._chk(L.rmj_logset_create_from_text(0, buf.ctypes.data, rng.ctypes.data, len(rng), n_players, 0, C.byref(h)))
-    info = abi.LogsetInfo()
-    vecenv._chk(L.rmj_logset_info(h, C.byref(info), None))
-    L.rmj_logset_destroy(h)
-    assert (int(info.n_logs), int(info.n_events), int(info.n_kyokus), int(info.longest_log)) == (len(logs), int(off[-1]), K, longest), what
+    s = LogSet.from_text(texts, num_players=n_players)
+    s.close()
+    assert (s.M, s.n_events, s.n_kyokus, s.longest_log) == (len(logs), int(off[-1]), K, longest), what
 
 
 @pytest.mark.parametrize("mode", [2, 5])
@@ -147,7 +140,7 @@ def test_samples_equal_the_dict_builder(mode, features, n):
     assert a.default_rewards().is_cuda                      # no host round trip
     assert np.array_equal(a.default_rewards().cpu().numpy(), b.default_rewards())
     _assert_same_samples(a, b, (mode, features))
-    assert a._h_end is None                                  # finalize() took the device table
+    assert a.logset._h_end is None                           # finalize() took the device table
     assert a.start_scores.tolist() == b.start_scores.tolist() and a.end_scores.tolist() == b.end_scores.tolist()
     a.close()
     b.close()
