@@ -1,4 +1,4 @@
-// Kernels + C-ABI (include/riichi_mi355x.h) of the MI355X-native batched Riichi step path.
+// C-ABI (include/riichi_mi355x.h) of the MI355X-native batched Riichi step path.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -shared -fPIC rmj_api.hip -o libriichi_mi355x.so
 //
 // Launch geometry: 256-thread workgroups = 4 wavefronts = 4 games; grid = ceil(B/4) (16 384
@@ -26,143 +26,8 @@
 
 using namespace rmj;
 
-#define WPB 4
-#define STEP_F_RANDOM 1u
-#define STEP_F_AUTORESET 2u
-#define STEP_F_IDS 4u /* `actions` holds int32 action ids [n][4] (Observation.find_action semantics) */
-#define STEP_F_QUIET 0x10000u   /* fused rollouts, every step but the last: no mask rows, no nlegal / waits / status words (nobody can read them) */
-#define STEP_F_ALLROWS 0x20000u /* fused rollouts, last step: all four mask rows are rewritten (the quiet steps left them stale) */
-#define STEP_F_CONT_RYU 0x40000u /* ol_step_full: continue at the exhaustive draw on the record k_step4's tier 0 left in LDS (no reload, no replay of the discard) */
-#define STEP_F_CONT_FIN 0x80000u /* ol_step_full: the step is complete on the record in LDS, only the observation outputs are produced */
-#define STEP_F_CONT_CLAIMS 0x400000u /* ol_step_full: continue behind the dahai event of the discard made on the record in LDS (claim generation, then the rest of _resolve_discard) */
-#define STEP_F_GREEDY 8u /* with STEP_F_RANDOM: the greedy policy (rmj_step_greedy, r4_policy_greedy) instead of the RandomAgent; bits 8..15 = call rate / 256 */
-
-template <int N>
-struct BlockSharedT {
-    GState st[N];
-    WaveScratch x[N];
-};
-typedef BlockSharedT<WPB> BlockShared;
-#define RMJ_STEP_WPB 1 /* games (= waves) per block of the step kernel: single-wave blocks release their LDS as soon as the game is done (a block of four waited for its slowest game) */
-static inline dim3 step_grid(uint32_t n) { return dim3((n + RMJ_STEP_WPB - 1) / RMJ_STEP_WPB); }
-// smallest batch that a multi-step device rollout splits over several streams of a handle (rmj_step_random)
-#define RMJ_SPLIT_MIN_GAMES 16384u
-#define RMJ_SPLIT_MIN_PART 8192u   // games per part at least
-#define RMJ_MAX_ROLLOUT_STREAMS 8
-// games per wave by batch size (STEP_F_ROWS_SHIFT; profiles/r04_rows_sweep.txt, fused 4p-red-single rollouts, M env.step/s at 4 | 2 | 1 games
-// per wave: 2 048 games 226 | 254 | 278, 4 096: 435 | 478 | 456, 8 192: 814 | 770 | 522, 16 384: 1 288 | 882 | 599; round 5, profiles/r05_rows_sweep.txt:
-// 2 048: 236 | 272 | 301, 3 072: 345 | 373 | 416, 4 096: 455 | 505 | 492, 6 144: 632 | 692 | 589, 8 192: 845 | 823 | 567)
-#define RMJ_ROWS1_MAX_GAMES 3584u
-#define RMJ_ROWS2_MAX_GAMES 7168u
-
-__device__ __forceinline__ void load_state(GState& S, const GState* src, int lane) {
-    if (lane < (int)(sizeof(GState) / 16)) reinterpret_cast<uint4*>(&S)[lane] = reinterpret_cast<const uint4*>(src)[lane];
-    wave_sync();
-}
-__device__ __forceinline__ void store_state(const GState& S, GState* dst, int lane) {
-    wave_sync();
-    if (lane < (int)(sizeof(GState) / 16)) reinterpret_cast<uint4*>(dst)[lane] = reinterpret_cast<const uint4*>(&S)[lane];
-}
-
-// fast path of k_step: the 128 B of globals and the PState quarters named by `dirty` (bit = seat)
-__device__ __forceinline__ void store_state_partial(const GState& S, GState* dst, int lane, uint32_t dirty) {
-    wave_sync();
-    if (lane < (int)(sizeof(GState) / 16) && (lane >= 32 || ((dirty >> (lane >> 3)) & 1u)))
-        reinterpret_cast<uint4*>(dst)[lane] = reinterpret_cast<const uint4*>(&S)[lane];
-}
-
-// Device policy without stepping (rmj_random_actions)
-__global__ void k_random_actions(Env E, uint64_t policy_seed, uint64_t* out) {
-    uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= E.n_games) return;
-    const GState& S = E.core[g];
-    uint64_t gs = sm64(policy_seed + E.game_offset + g);
-    for (int p = 0; p < 4; p++) {
-        uint64_t a = RMJ_NO_ACTION;
-        int n = E.nlegal[(size_t)g * 4 + p];
-        if (((S.active_mask >> p) & 1u) && n > 0 && !S.is_done) {
-            const uint32_t ch = policy_pick(policy_key32(gs, S.step_count, (uint32_t)p), (uint32_t)n);
-            a = E.legal[((size_t)g * 4 + p) * RMJ_MAX_LEGAL + ch];
-        }
-        out[(size_t)g * 4 + p] = a;
-    }
-}
-
-// Trainer-side masked categorical sampler (rmj_sample_ids_device): one wave per game; for every seat that is to act the
-// lanes hold ids lane and lane + 64 of the seat's mask row, add Gumbel noise to the policy's logits (Gumbel-max = a draw
-// from softmax(logits) restricted to the legal ids; no logits = uniform over the legal ids) and a wave arg-max picks the id.
-// The noise is counter-based: splitmix64(seed, global game, the game's step count, seat, id).
-// Round 5: four games per wave (one 16-lane row each; lane r of a row judges the ids r, r + 16, ...), like the step kernels - the keyed Gumbel
-// draw of an id costs the same wherever it runs, but a wave per game left 64 lanes to 82 ids of (mostly) one seat.  The same keys, the same
-// arg-max rule (ties to the lower id) as the wave-per-game kernel of rounds 3-4: identical ids.
-// One id per acting seat of the row's game g (in: the row has a game): lane p of the row returns seat p's id, -1 where nobody acts.
-// Non-finite logits: a -inf or NaN logit is never drawn while a finite one is legal; if every legal id is -inf or NaN the lowest legal
-// id is drawn; among several +inf logits the lowest id wins.  tests/sampler_ref.py restates the draw in float64.
-__device__ __forceinline__ int32_t sample_ids_row(const uint32_t* status, const GState* core, const uint8_t* nlegal, const uint8_t* mask, uint64_t game_offset,
-                                                  int game_mode, uint32_t g, bool in, const float* __restrict__ logits, uint32_t stride, uint64_t seed, int lane,
-                                                  uint32_t seats = 0xFu) {   // seats: the seats that draw (k_select_ids draws for one)
-    const int r = lane & 15;
-    const uint32_t gi = in ? g : 0u;
-    const uint32_t st = in ? status[gi] : 0x10000u;
-    const uint32_t am = ((st >> 16) & 0xFFu ? 0u : (st & 0xFu)) & seats;   // done games have nobody to act
-    const int A = game_mode >= 3 ? RMJ_ACTION_SPACE_3P : RMJ_ACTION_SPACE_4P;
-    const uint64_t base = sm64(seed ^ sm64(game_offset + gi)) + ((uint64_t)core[gi].step_count << 10);
-    const uint32_t nl4 = in ? *reinterpret_cast<const uint32_t*>(nlegal + (size_t)gi * 4) : 0u;   // the four list lengths of the game
-    int32_t res = -1;
-    for (int p = 0; p < 4; p++) {
-        const bool act = ((am >> p) & 1u) && ((nl4 >> (8 * p)) & 0xFFu) != 0u;   // (row-uniform)
-        if (!__ballot(act)) continue;
-        const uint8_t* m = mask + ((size_t)gi * 4 + p) * 82;
-        const float* lg = logits ? logits + ((size_t)gi * 4 + p) * stride : nullptr;
-        float best = -INFINITY;
-        int bid = -1;
-        if (act) {
-            for (int id = r; id < A; id += 16) {
-                if (m[id]) {
-                    const uint64_t h = sm64(base + ((uint64_t)p << 8) + (uint64_t)id);
-                    // u in (0, 1), 24 bits: 0xFFFFFF + 0.5f rounds to 2^24 (u = 1, a +inf key whatever the logit), so the top value is
-                    // clamped to the largest float below 1 - the only hash value whose u this changes
-                    const float u = fminf(((float)(uint32_t)(h >> 40) + 0.5f) * (1.0f / 16777216.0f), 0x1.fffffep-1f);
-                    const float k = (lg ? lg[id] : 0.0f) - __logf(-__logf(u));
-                    const float key = __builtin_isnan(k) ? -INFINITY : k;   // a NaN logit is drawn like -inf (the arg-max stays a function of the keys)
-                    if (key > best || bid < 0) { best = key; bid = id; }
-                }
-            }
-        }
-        // row arg-max (ties to the lower id)
-#pragma unroll
-        for (int off = 8; off >= 1; off >>= 1) {
-            const float ob = __shfl_xor(best, off, 64);
-            const int oi = __shfl_xor(bid, off, 64);
-            if (oi >= 0 && (bid < 0 || ob > best || (ob == best && oi < bid))) { best = ob; bid = oi; }
-        }
-        if (act && r == p) res = bid;
-    }
-    return res;
-}
-__global__ __launch_bounds__(256) void k_sample_ids(Env E, const float* __restrict__ logits, uint32_t stride, uint64_t seed,
-                                                    int32_t* __restrict__ out) {
-    const int lane = threadIdx.x & 63, r = lane & 15;
-    const uint32_t g = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 4 + (uint32_t)(lane >> 4);
-    const bool in = g < E.n_games;
-    const int32_t res = sample_ids_row(E.status, E.core, E.nlegal, E.mask, E.game_offset, E.game_mode, g, in, logits, stride, seed, lane);
-    if (in && r < 4) out[(size_t)g * 4 + r] = res;
-}
-
-struct ResetArgs {
-    const uint8_t* select;
-    const uint8_t* walls;       // [n][136] reference orientation (draw order)
-    const uint8_t* oya;
-    const uint8_t* round_wind;
-    const int32_t* scores;      // [n][4]
-    const uint8_t* honba;
-    const uint32_t* kyotaku;
-    const uint64_t* seeds;      // ctor only
-    uint64_t base_seed;
-    uint32_t is_ctor;
-};
-
-
+// the device code, by subsystem, in the order the code object keeps its kernels
+#include "rmj_policy.hip.h"
 #define RMJ_NS rmj4
 #define RMJ_SANMA 0
 #include "rmj_step.hip.h"
@@ -177,860 +42,26 @@ struct ResetArgs {
 #include "rmj_step4.hip.h"
 #undef RMJ_NS
 #undef RMJ_SANMA
-
-// largest raw HW_REG_XCC_ID[3:0] over the waves of the launch (rmj_create: is the per-XCD queue assumption of k_step4_queue valid?)
-__global__ void k_probe_xcc(unsigned long long* out) {
-    const unsigned long long id = (unsigned long long)((uint32_t)__builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u);
-    if ((threadIdx.x & 63u) == 0u) atomicMax(out, id);
-}
-__global__ void k_sum_steps(const GState* core, uint32_t n, unsigned long long* out) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    unsigned long long v = 0;
-    for (; i < n; i += gridDim.x * blockDim.x) v += core[i].step_count;
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    if ((threadIdx.x & 63) == 0 && v) atomicAdd(out, v);
-}
-__global__ void k_sum_full(const GState* core, uint32_t n, unsigned long long* out) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    unsigned long long v = 0;
-    for (; i < n; i += gridDim.x * blockDim.x) v += core[i].full_count;
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    if ((threadIdx.x & 63) == 0 && v) atomicAdd(out, v);
-}
-__global__ void k_gather_steps(const GState* core, uint32_t n, uint64_t* out) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = core[i].step_count;
-}
-// ---- compact legal lists for a host agent loop (rmj_get_legal_compact): rows = the seats that are to act, in (game, seat) order,
-// entries = their lists one after the other.  Pass 1: per game the rows / entries it contributes, block prefix sums; pass 2: the
-// block totals scanned by one block; pass 3: every game writes its rows.  Deterministic order, no atomics.
-#define LC_BLOCK 256
-__device__ __forceinline__ uint32_t lc_rows_of(uint32_t status, const uint8_t* nl, uint32_t& entries) {
-    const uint32_t am = (status >> 16) & 1u ? 0u : (status & 0xFu);
-    uint32_t rows = 0;
-    entries = 0;
-    for (int p = 0; p < 4; p++)
-        if (((am >> p) & 1u) && nl[p]) { rows++; entries += nl[p]; }
-    return rows;
-}
-__global__ __launch_bounds__(LC_BLOCK) void k_lc_count(const uint32_t* __restrict__ status, const uint8_t* __restrict__ nlegal, uint32_t n, uint32_t* __restrict__ pre /*[n][2]*/,
-                                                       uint32_t* __restrict__ blk /*[blocks][2]*/) {
-    __shared__ uint32_t sr[LC_BLOCK], se[LC_BLOCK];
-    const uint32_t g = blockIdx.x * LC_BLOCK + threadIdx.x;
-    uint32_t e = 0, r = 0;
-    if (g < n) r = lc_rows_of(status[g], nlegal + (size_t)g * 4, e);
-    sr[threadIdx.x] = r; se[threadIdx.x] = e;
-    __syncthreads();
-    for (int off = 1; off < LC_BLOCK; off <<= 1) {     // inclusive Hillis-Steele scan
-        uint32_t ar = 0, ae = 0;
-        if ((int)threadIdx.x >= off) { ar = sr[threadIdx.x - off]; ae = se[threadIdx.x - off]; }
-        __syncthreads();
-        sr[threadIdx.x] += ar; se[threadIdx.x] += ae;
-        __syncthreads();
-    }
-    if (g < n) { pre[2 * (size_t)g] = sr[threadIdx.x] - r; pre[2 * (size_t)g + 1] = se[threadIdx.x] - e; }
-    if (threadIdx.x == LC_BLOCK - 1) { blk[2 * blockIdx.x] = sr[threadIdx.x]; blk[2 * blockIdx.x + 1] = se[threadIdx.x]; }
-}
-__global__ void k_lc_scan(uint32_t* blk, uint32_t blocks, uint32_t* totals /*[2]*/) {   // one thread: a few thousand blocks at most
-    if (blockIdx.x || threadIdx.x) return;
-    uint32_t r = 0, e = 0;
-    for (uint32_t b = 0; b < blocks; b++) {
-        const uint32_t cr = blk[2 * b], ce = blk[2 * b + 1];
-        blk[2 * b] = r; blk[2 * b + 1] = e;
-        r += cr; e += ce;
-    }
-    totals[0] = r; totals[1] = e;
-}
-__global__ __launch_bounds__(LC_BLOCK) void k_lc_gather(const uint32_t* __restrict__ status, const uint8_t* __restrict__ nlegal, const uint64_t* __restrict__ legal, uint32_t n,
-                                                        const uint32_t* __restrict__ pre, const uint32_t* __restrict__ blk, uint32_t cap_rows, uint32_t cap_entries,
-                                                        uint32_t* __restrict__ index, uint32_t* __restrict__ offs, uint64_t* __restrict__ entries) {
-    const uint32_t g = blockIdx.x * LC_BLOCK + threadIdx.x;
-    if (g >= n) return;
-    const uint32_t st = status[g];
-    const uint32_t am = (st >> 16) & 1u ? 0u : (st & 0xFu);
-    uint32_t row = blk[2 * blockIdx.x] + pre[2 * (size_t)g], ent = blk[2 * blockIdx.x + 1] + pre[2 * (size_t)g + 1];
-    for (int p = 0; p < 4; p++) {
-        const uint32_t k = nlegal[(size_t)g * 4 + p];
-        if (!((am >> p) & 1u) || !k) continue;
-        if (row < cap_rows) { index[row] = g * 4u + (uint32_t)p; offs[row] = ent; offs[row + 1] = ent + k; }   // (the next row writes the same value at row + 1)
-        for (uint32_t j = 0; j < k; j++)
-            if (ent + j < cap_entries) entries[ent + j] = legal[((size_t)g * 4 + p) * RMJ_MAX_LEGAL + j];
-        row++;
-        ent += k;
-    }
-}
-// RiichiEnv.points (env.rs:691-727) with ranks (env.rs:673-689: by score, ties by seat) for every game: f64 like the reference
-__global__ void k_points(const GState* core, uint32_t n, int np, double weight, double base, double u0, double u1, double u2, double u3, double* out) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    int32_t sc[4];
-    for (int p = 0; p < 4; p++) sc[p] = core[i].p[p].score;
-    for (int p = 0; p < 4; p++) {
-        double v = 0.0;
-        if (p < np) {
-            int rank = 0;   // seats ahead: a higher score, or the same score and a lower seat index
-            for (int o = 0; o < np; o++) rank += (sc[o] > sc[p]) || (sc[o] == sc[p] && o < p);
-            const double uma = rank == 0 ? u0 : (rank == 1 ? u1 : (rank == 2 ? u2 : u3));
-            v = ((double)sc[p] - base) / 1000.0 * weight + uma;
-        }
-        out[(size_t)i * 4 + p] = v;
-    }
-}
-__global__ void k_gather_scores(const GState* core, uint32_t n, int32_t* out, uint32_t* evc) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) {
-        for (int p = 0; p < 4; p++) out[(size_t)i * 4 + p] = core[i].p[p].score;
-        if (evc) evc[i] = core[i].ev_count - core[i].ev_base;   // len(mjai_log) of the current game
-    }
-}
-__global__ void k_track_mark(uint8_t* mark, const uint8_t* __restrict__ select, uint32_t first, uint32_t n) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && (!select || select[first + i])) mark[first + i] = 1;
-}
-__global__ void k_log_positions(const GState* core, uint32_t n, uint32_t* base, uint32_t* pos) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) { base[i] = core[i].ev_base; pos[i] = core[i].ev_count; }
-}
-
-// WallState.salt / wall_digest (state/wall.rs:15-16, 48-55) of games [first, first + n): out[i] = {valid, salt (u64), SHA-256 (8 x u32, big
-// endian words)} as 11 dwords; one lane per game.  valid = GState::wall_meta (RMJ_RULE_REFERENCE_RNG shuffles only).
-__global__ __launch_bounds__(64) void k_wall_digest(const GState* __restrict__ core, const uint8_t* __restrict__ wall, const uint32_t* __restrict__ frozen,
-                                                    uint32_t first, uint32_t n, int tiles, uint32_t* __restrict__ out) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t g = first + i;
-    const uint8_t* W = wall + (size_t)g * RMJ_WALL_STRIDE;
-    uint32_t* o = out + (size_t)i * 11;
-    const uint32_t valid = core[g].wall_meta;
-    uint64_t salt = 0;
-    uint32_t dg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (valid) {
-        for (int k = 0; k < 8; k++) salt |= (uint64_t)W[136 + k] << (8 * k);
-        if (valid == 2) { for (int k = 0; k < 8; k++) dg[k] = frozen[(size_t)g * 8 + k]; }   // the wall it belonged to is gone
-        else sha256_wall(W, tiles, salt, dg);
-    }
-    o[0] = valid; o[1] = (uint32_t)salt; o[2] = (uint32_t)(salt >> 32);
-    for (int k = 0; k < 8; k++) o[3 + k] = dg[k];
-}
-
-// ---------------------------------------------------------------- batched hand math kernels (one wave per case)
-__device__ inline MeldAgg agg_from_views(const RmjHandCase& hc) {
-    MeldAgg m;
-    m.n = hc.n_melds > 4 ? 4 : hc.n_melds;
-    m.n_kan = m.n_ankan = m.n_nonchi = 0;
-    m.menzen = true;
-    m.types = 0;
-    m.fu = 0;
-    m.aka = 0;
-    for (int i = 0; i < 4; i++) {
-        m.mtypes[i] = 0;
-        m.mtype[i] = 0;
-        m.t0[i] = 0;
-        if (i < m.n) {
-            const RmjMeldView& v = hc.melds[i];
-            int nt = v.n_tiles > 4 ? 4 : v.n_tiles;
-            uint64_t mm = 0;
-            int tmin = 99;
-            for (int k = 0; k < nt; k++) {
-                int t = v.tiles[k];
-                mm |= 1ull << (t >> 2);
-                m.aka += is_aka(t);
-                tmin = min(tmin, t >> 2);
-            }
-            m.mtypes[i] = mm;
-            m.types |= mm;
-            m.mtype[i] = v.meld_type;
-            int t0 = (v.meld_type == RMJ_MELD_CHI) ? tmin : (v.tiles[0] >> 2);  // chi tiles are sorted (hand_evaluator.rs:63-65)
-            m.t0[i] = (uint8_t)t0;
-            if (v.opened) m.menzen = false;
-            bool kan = v.meld_type >= RMJ_MELD_DAIMINKAN;
-            m.n_kan += kan;
-            m.n_ankan += (v.meld_type == RMJ_MELD_ANKAN);
-            m.n_nonchi += (v.meld_type != RMJ_MELD_CHI);
-            bool trip = nt >= 3 && v.meld_type != RMJ_MELD_CHI && (v.tiles[0] >> 2) == (v.tiles[1] >> 2);
-            if (v.meld_type == RMJ_MELD_CHI && nt >= 3) {  // sorted types: equal first two only for degenerate input
-                int a = 99, b = 99;
-                for (int k = 0; k < nt; k++) {
-                    int t = v.tiles[k] >> 2;
-                    if (t < a) { b = a; a = t; } else if (t < b) b = t;
-                }
-                trip = a == b;
-            }
-            if (trip) {
-                int f = v.opened ? 2 : 4;
-                if (t_is_terminal(t0)) f *= 2;
-                if (kan) f *= 4;
-                m.fu += f;
-            }
-        }
-    }
-    return m;
-}
-
-// Round 4: HandEvaluator::calc + waits for FOUR hands per wave, one 16-lane row per hand (e4_calc, rmj_eval4.hip.h).  The wave's four
-// 88-byte cases arrive as one contiguous 352-byte block (coalesced dword loads into LDS), lane r of a row is tile r / meld r / dora
-// indicator r while the case is parsed, the 64-byte results leave as one dword per lane (256 contiguous bytes per wave).  Round 3's
-// kernel - one wave per hand, lane = candidate head walking every division x winning group serially, 236 registers squeezed into 80
-// with 576 B of scratch per lane - ran at 71 M hands/s.
-struct EvalShared {
-    alignas(16) uint32_t in[4 * sizeof(RmjHandCase) / 4];
-    alignas(16) uint32_t out[4][16];
-};
-static_assert(sizeof(RmjHandCase) == 88 && sizeof(RmjHandResult) == 64, "k_eval_hands stages cases / results by these sizes");
-#define RMJ_EVAL_WAVES 6   /* 129 VGPR left alone = three waves per SIMD: 0.72 G hands/s; four 0.84, five 0.906, six 0.91-0.92, seven 0.905, eight 0.84 */
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RMJ_EVAL_WAVES, RMJ_EVAL_WAVES))) void k_eval_hands(const RmjHandCase* cases, uint32_t n, RmjHandResult* out) {
-    __shared__ EvalShared shw[WPB];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, rb = lane & 48, row = lane >> 4;
-    const uint32_t k0 = (blockIdx.x * WPB + wave) * 4u;   // first hand of the wave
-    if (k0 >= n) return;
-    EvalShared& sh = shw[wave];
-    const uint32_t k = k0 + (uint32_t)row;
-    const bool live = k < n;
-    {
-        const uint32_t words = (n - k0 < 4u ? n - k0 : 4u) * (uint32_t)(sizeof(RmjHandCase) / 4);
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(cases + k0);
-        for (uint32_t i = lane; i < words; i += 64) sh.in[i] = src[i];
-    }
-    wave_sync();
-    const RmjHandCase& hc = *reinterpret_cast<const RmjHandCase*>(reinterpret_cast<const uint8_t*>(sh.in) + (size_t)row * sizeof(RmjHandCase));
-    const int nt = live ? (hc.n_tiles > 14 ? 14 : hc.n_tiles) : 0;
-    const int nm = live ? (hc.n_melds > 4 ? 4 : hc.n_melds) : 0;
-    const bool sanma = hc.is_sanma != 0;
-    // ---- lane = concealed tile: histogram of the given tiles, red fives
-    uint32_t ca = 0, cb = 0, cc = 0, cd = 0;
-    const int tile = r < nt ? (int)hc.tiles[r] : 0;
-    if (r < nt) {
-        const int t = tile >> 2, s = t_suit(t);
-        const uint32_t one = 1u << (3 * (t - 9 * s));
-        ca = s == 0 ? one : 0u; cb = s == 1 ? one : 0u; cc = s == 2 ? one : 0u; cd = s == 3 ? one : 0u;
-    }
-    PH conc;
-    conc.a = e4_rsum(ca, rb); conc.b = e4_rsum(cb, rb); conc.c = e4_rsum(cc, rb); conc.d = e4_rsum(cd, rb);
-    int aka = __popc(e4_ballot(r < nt && is_aka(tile), rb));
-    // ---- lane = meld: the packed aggregate (agg_from_views), the tiles it adds to the dora histogram, HandEvaluator::new's kan fix
-    //      (hand_evaluator.rs:43-62: a concealed hand that still lists all four tiles of a kan loses one)
-    E4Meld mp;
-    uint32_t ma_ = 0, mb_ = 0, mc_ = 0, md_ = 0;   // meld tiles (one-hot sums)
-    uint32_t fa_ = 0, fb_ = 0, fc_ = 0, fd_ = 0;   // kan fix
-    {
-        const bool mv = r < nm;
-        const RmjMeldView& v = hc.melds[r & 3];
-        const int ntm = mv ? (v.n_tiles > 4 ? 4 : v.n_tiles) : 0;
-        const uint32_t t0id = v.tiles[0], t1id = v.tiles[1], t2id = v.tiles[2], t3id = v.tiles[3];
-        const bool chi = v.meld_type == RMJ_MELD_CHI;
-        int lo1 = 99, lo2 = 99;   // the two lowest types among the meld's tiles
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const int t = (int)(q == 0 ? t0id : (q == 1 ? t1id : (q == 2 ? t2id : t3id))) >> 2;
-            if (q < ntm) {
-                if (t < lo1) { lo2 = lo1; lo1 = t; } else if (t < lo2) lo2 = t;
-                const int s = t_suit(t);
-                const uint32_t one = 1u << (3 * (t - 9 * s));
-                ma_ += s == 0 ? one : 0u; mb_ += s == 1 ? one : 0u; mc_ += s == 2 ? one : 0u; md_ += s == 3 ? one : 0u;
-            }
-        }
-        const int t0 = chi ? lo1 : (int)(t0id >> 2);
-        const bool trip = ntm >= 3 && (chi ? lo1 == lo2 : (t0id >> 2) == (t1id >> 2));
-        mp = e4_meld_lane(mv, v.meld_type, ntm, t0id, t1id, t2id, t3id, t0, trip, v.opened != 0);
-        if (mv && v.meld_type >= RMJ_MELD_DAIMINKAN) {
-            const int t = (int)(t0id >> 2);
-            if (t < 34 && ph_cnt(conc, t) == 4) {
-                const int s = t_suit(t);
-                const uint32_t one = 1u << (3 * (t - 9 * s));
-                fa_ = s == 0 ? one : 0u; fb_ = s == 1 ? one : 0u; fc_ = s == 2 ? one : 0u; fd_ = s == 3 ? one : 0u;
-            }
-        }
-    }
-    const E4Meld ma = e4_meld_reduce(mp, rb);
-    aka += e4m_aka(ma);
-    PH hand = conc, full = conc;
-    hand.a -= e4_rsum(fa_, rb); hand.b -= e4_rsum(fb_, rb); hand.c -= e4_rsum(fc_, rb); hand.d -= e4_rsum(fd_, rb);
-    full.a += e4_rsum(ma_, rb); full.b += e4_rsum(mb_, rb); full.c += e4_rsum(mc_, rb); full.d += e4_rsum(md_, rb);
-    const int total = ph_total(hand) + 3 * nm;
-    uint64_t waits = 0ull;
-    if (__ballot(live && total == 13)) {
-        if (live && total == 13) waits = rmj4::r4_waits_probe(hand.a, hand.b, hand.c, hand.d);
-    }
-    const int win34 = (hc.win_tile >> 2) < 34 ? (hc.win_tile >> 2) : 33;
-    PH h14 = hand, f14 = full;
-    if (total == 13) {
-        ph_add(h14, win34);
-        ph_add(f14, win34);
-        aka += is_aka(hc.win_tile);
-    }
-    // ---- lane = indicator: dora (lanes 0..4) and ura (lanes 8..12) counts over the full histogram
-    int dora, ura;
-    {
-        const bool is_d = r < 5 && r < hc.n_dora, is_u = r >= 8 && r < 13 && r - 8 < hc.n_ura;
-        int cnt = 0;
-        if (is_d || is_u) {
-            const int ind = is_d ? hc.dora[r & 7] : hc.ura[(r - 8) & 7];
-            const int nt34 = next_dora34((ind >> 2) < 34 ? (ind >> 2) : 33, sanma);
-            cnt = ph_cnt(f14, nt34);
-            if (sanma && nt34 == 30) cnt += hc.kita_count;
-        }
-        dora = (int)e4_rsum(is_d ? (uint32_t)cnt : 0u, rb);
-        ura = (int)e4_rsum(is_u ? (uint32_t)cnt : 0u, rb);
-    }
-    E4In in;
-    in.on = live;
-    in.hand14 = h14;
-    in.ma = ma;
-    in.win34 = win34;
-    uint32_t cf = 0;
-    if (hc.tsumo) cf |= CF_TSUMO;
-    if (hc.riichi) cf |= CF_RIICHI;
-    if (hc.double_riichi) cf |= CF_DOUBLE_RIICHI;
-    if (hc.ippatsu) cf |= CF_IPPATSU;
-    if (hc.haitei) cf |= CF_HAITEI;
-    if (hc.houtei) cf |= CF_HOUTEI;
-    if (hc.rinshan) cf |= CF_RINSHAN;
-    if (hc.chankan) cf |= CF_CHANKAN;
-    if (hc.tsumo_first_turn) cf |= CF_FIRST_TURN;
-    in.cf = cf;
-    in.dora = dora & 0xFF; in.aka = aka & 0xFF; in.ura = ura & 0xFF;
-    in.nuki = sanma ? hc.kita_count : 0;
-    in.round_wind34 = 27 + (hc.round_wind & 3);
-    in.seat_wind34 = 27 + (hc.player_wind & 3);
-    in.sanma = sanma;
-    in.honba = hc.honba;
-    const E4Out o = e4_calc(in, r, rb);
-    // ---- the 64-byte result: dword r by lane r, the ordered yaku list through LDS bytes
-    uint32_t w = 0u;
-    if (r == 6) w = o.shape ? (uint32_t)o.han : 0u;
-    if (r == 7) w = o.shape ? (uint32_t)o.fu : 0u;
-    if (r == 8) w = o.ron;
-    if (r == 9) w = o.tsumo_oya;
-    if (r == 10) w = o.tsumo_ko;
-    if (r == 12) w = (uint32_t)waits;
-    if (r == 13) w = (uint32_t)(waits >> 32);
-    if (r == 14) w = (uint32_t)(waits != 0ull) | ((uint32_t)o.shape << 8);
-    sh.out[row][r] = w;
-    wave_sync();
-    int ny = 0;
-    if (__ballot(live && o.shape)) {
-        if (live && o.shape) ny = e4_yaku_list(o.kind, o.ym, reinterpret_cast<uint8_t*>(&sh.out[row][1]), r, rb);
-    }
-    if (r == 0) sh.out[row][0] = (uint32_t)o.is_win | ((uint32_t)o.yakuman << 8) | ((uint32_t)o.shape << 16) | ((uint32_t)ny << 24);
-    wave_sync();
-    if (live) reinterpret_cast<uint32_t*>(out + k)[r] = sh.out[row][r];
-}
-
-// agari.rs:65-73 + hand_evaluator.rs:178-213 over raw histograms.  Round 3: FOUR hands per wave - one 16-lane row per hand like
-// the step kernel's tier 0: the hand's 34 counts arrive as three coalesced byte loads per row (round 2: one hand per wave, every lane
-// walked the same 34 bytes one by one), the row OR-reduces them into the packed histogram, is_agari is closed-form per row and the
-// waits come from the row-form probe of the step kernel (r4_waits_probe).
-__global__ __launch_bounds__(256) void k_agari_counts(const uint8_t* counts, uint32_t n, uint8_t* agari, uint8_t* tenpai, uint64_t* waits) {
-    const int lane = threadIdx.x & 63, r = lane & 15, rb = lane & 48;
-    const uint32_t k = (blockIdx.x * 4u + (threadIdx.x >> 6)) * 4u + (uint32_t)(lane >> 4);
-    const bool live = k < n;
-    PH h = {0, 0, 0, 0};
-    {
-        uint32_t w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            const int t = r + 16 * j;
-            if (live && t < 34) {
-                const int s = t_suit(t);
-                const uint32_t f = ((uint32_t)counts[(size_t)k * 34 + t] & 7u) << (3 * (t - 9 * s));
-                w[0] |= s == 0 ? f : 0u; w[1] |= s == 1 ? f : 0u; w[2] |= s == 2 ? f : 0u; w[3] |= s == 3 ? f : 0u;
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < 4; q++) w[q] = (uint32_t)rmj4::rbc((int)rmj4::row_or16(w[q]), rb + 15);
-        h.a = w[0]; h.b = w[1]; h.c = w[2]; h.d = w[3];
-    }
-    const bool ag = is_agari(h);
-    uint64_t w = 0ull;
-    if (__ballot(live && ph_total(h) == 13)) {
-        if (live && ph_total(h) == 13) w = rmj4::r4_waits_probe(h.a, h.b, h.c, h.d);
-    }
-    if (live && r == 0) {
-        agari[k] = ag;
-        tenpai[k] = w != 0ull;
-        waits[k] = w;
-    }
-}
-
-// Observation.encode() / encode_extended() for every (game, seat): one wave (= one block) per (game, seat).
-// out[g][seat][C][W] f32, C = 74 or 215.  The tensor is assembled in an 84-channel LDS staging buffer (11 KB: 13 blocks per
-// CU) and streamed out group by group: base channels, then the two extended groups (rmj_encode.hip.h).
-// only_active: 0 = every seat, 1 = acting seats (other rows zeroed), 2 = acting seats (other rows untouched).
-template <int W>
-__device__ __forceinline__ void enc_stream_out(float* dst, const float* buf, int n_floats, int lane) {
-    // both even: 16-byte rows are not guaranteed (215 x 27 is odd), 8-byte pairs are when the offset and count are even
-    if ((n_floats & 1) == 0 && ((reinterpret_cast<uintptr_t>(dst) & 7u) == 0)) {
-        for (int i = lane; i < n_floats / 2; i += 64) reinterpret_cast<float2*>(dst)[i] = reinterpret_cast<const float2*>(buf)[i];
-    } else {
-        for (int i = lane; i < n_floats; i += 64) dst[i] = buf[i];
-    }
-}
-// n_floats floats from LDS to global memory in 16-byte stores: `dst` is 8-byte aligned (every row of the tensors is an even
-// number of floats from a 16-byte aligned base), so at most two floats precede the first 16-byte boundary and at most
-// three follow the last; the body goes out as dwordx4 (the epilogue of a wave is store-issue bound: half the instructions
-// of the 8-byte version).  The LDS side is read as two 8-byte halves (its offset is only 8-byte aligned after the head).
-__device__ __forceinline__ void enc_stream_out16(float* dst, const float* buf, int n_floats, int lane) {
-    const int head = (int)(((16u - (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u) >> 2);  // 0 or 2
-    const int body = (n_floats - head) >> 2, tail0 = head + 4 * body;
-    if (lane < head) dst[lane] = buf[lane];
-    float4* d4 = reinterpret_cast<float4*>(dst + head);
-    for (int i = lane; i < body; i += 64) {
-        const float2 lo = *reinterpret_cast<const float2*>(buf + head + 4 * i), hi = *reinterpret_cast<const float2*>(buf + head + 4 * i + 2);
-        d4[i] = make_float4(lo.x, lo.y, hi.x, hi.y);
-    }
-    if (lane < n_floats - tail0) dst[tail0 + lane] = buf[tail0 + lane];
-}
-__device__ __forceinline__ void enc_zero16(float* dst, int n_floats, int lane) {
-    const int head = (int)(((16u - (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u) >> 2);
-    const int body = (n_floats - head) >> 2, tail0 = head + 4 * body;
-    if (lane < head) dst[lane] = 0.0f;
-    float4* d4 = reinterpret_cast<float4*>(dst + head);
-    for (int i = lane; i < body; i += 64) d4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (lane < n_floats - tail0) dst[tail0 + lane] = 0.0f;
-}
-// Slots of the compact observation batch, level one: a block of 1024 threads scans the acting-seat counts of its 1024 games
-// (finished games have none): offs[g] = acting seats in the block's games before g, totals[block] = the block's sum.  The
-// encoder adds the totals of the blocks before its game's block (at most 512 numbers, one wave reduction).
-#define OBS_SCAN_BLOCK 1024
-__global__ __launch_bounds__(OBS_SCAN_BLOCK) void k_obs_offsets(const uint32_t* __restrict__ status, uint32_t n, uint32_t* __restrict__ offs,
-                                                               uint32_t* __restrict__ totals) {
-    __shared__ uint32_t wsum[OBS_SCAN_BLOCK / 64];
-    const uint32_t t = threadIdx.x, g = blockIdx.x * OBS_SCAN_BLOCK + t, lane = t & 63u, wv = t >> 6;
-    uint32_t c = 0u;
-    if (g < n) {
-        const uint32_t w = status[g];
-        c = ((w >> 16) & 0xFFu) ? 0u : (uint32_t)__popc(w & 0xFu);
-    }
-    uint32_t inc = c;   // inclusive scan inside the wave
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t v = (uint32_t)__shfl_up((int)inc, d, 64);
-        if ((int)lane >= d) inc += v;
-    }
-    if (lane == 63u) wsum[wv] = inc;
-    __syncthreads();
-    uint32_t before = 0u;
-    for (uint32_t k = 0; k < wv; k++) before += wsum[k];
-    if (g < n) offs[g] = before + inc - c;
-    if (t == OBS_SCAN_BLOCK - 1) totals[blockIdx.x] = before + inc;
-}
-// sum of totals[0 .. nb) by one wave (nb <= 512 for 524 288 games)
-__device__ __forceinline__ uint32_t obs_block_prefix(const uint32_t* __restrict__ totals, uint32_t nb, int lane) {
-    uint32_t s = 0u;
-    for (uint32_t k = (uint32_t)lane; k < nb; k += 64u) s += totals[k];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) s += (uint32_t)__shfl_xor((int)s, d, 64);
-    return s;
-}
+#include "rmj_readout.hip.h"
+#include "rmj_handapi.hip.h"
+#include "rmj_obs.hip.h"
 #include "rmj_ppo.hip.h"
-// Observation.encode() of the games [g0, g0 + gridDim.x): ONE block (= one wave) per game, which walks the seats it has to
-// encode - with only_active that is the acting seat (one, rarely two or three), so the launch has a quarter of the blocks of
-// a (game, seat) grid and no early-exit blocks.  The tensor of a seat is staged as one byte per cell (EncByteSink: 2.5 KB,
-// 4.9 KB of LDS per block with the record, the histograms and the value table) and leaves as a stream of 16-byte stores.
-// Round 6: four waves per SIMD.  Left alone the kernel takes 100 VGPR (four waves) under the default flags and 60 (seven) under -disable-machine-licm; alone
-// it runs the same either way (3P 0.1347 -> 0.1378 ms, occupancy 5 -> 8 changed nothing in round 5), but next to step and sampler kernels of other
-// shards on other streams the seven-wave form crowds them out: the trainer loop as 4 shards on 4 streams 304 -> 345 M env.step/s, 2 shards 290 -> 315 M,
-// compact batch 305 -> 334 M with the cap (five waves: 336 / 292 / 320; round-5 binary: 340-350 / 312-320 / 311-316).
-#define RMJ_ENC_WAVES 4
-// `offs` != nullptr: compact output (rmj_encode_compact_device) - the observations of the acting seats, one after the other in
-// (game, seat) order: observation offs[g] + j is the j-th acting seat of game g, `index` receives game * 4 + seat.
-template <bool SANMA, bool COMPACT>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RMJ_ENC_WAVES, RMJ_ENC_WAVES))) void k_encode_base(Env E, int only_active, float* __restrict__ out, uint32_t g0,
-                                                               const uint32_t* __restrict__ offs, int32_t* __restrict__ index, uint32_t capacity,
-                                                               const uint32_t* __restrict__ totals, uint32_t* __restrict__ count) {
-    constexpr int W = SANMA ? ENC_W3 : ENC_W4, NPP = SANMA ? 3 : 4;
-    __shared__ GState st;
-    __shared__ __attribute__((aligned(16))) uint8_t raw[(ENC_CH * W + 4 + 15) / 16 * 16];
-    __shared__ float lut[ENC_LUT];
-    __shared__ uint32_t hist[ENC_HIST_WORDS];
-    const int lane = threadIdx.x & 63;
-    const uint32_t g = g0 + blockIdx.x;
-    // the record is requested together with the status word (nearly every game has a seat to act): one memory round trip
-    uint4 rec = make_uint4(0u, 0u, 0u, 0u);
-    if (lane < (int)(sizeof(GState) / 16)) rec = reinterpret_cast<const uint4*>(E.core + g)[lane];
-    const uint32_t stw = E.status[g];
-    const uint32_t am = ((stw >> 16) & 0xFFu) ? 0u : (stw & 0xFu);
-    const size_t RS = E.enc_stride;   // row stride in floats (>= 74 x W; rows padded to a multiple of 256 B leave at 1.3-1.4 x the rate)
-    float* base = out + (size_t)g * 4 * RS;
-    uint32_t slot = 0u;
-    if (COMPACT) {
-        if (blockIdx.x == 0) {   // the size of the batch: all block totals
-            const uint32_t all = obs_block_prefix(totals, (E.n_games + OBS_SCAN_BLOCK - 1) / OBS_SCAN_BLOCK, lane);
-            if (lane == 0) *count = all;
-        }
-        if (am == 0u) return;
-        slot = offs[g] + obs_block_prefix(totals, g / OBS_SCAN_BLOCK, lane);
-    } else if (only_active && am == 0u) {
-        if (only_active == 1)
-            for (int z = 0; z < 4; z++) enc_zero16(base + (size_t)z * RS, ENC_CH * W, lane);
-        return;
-    }
-    enc_lut_init(lut, lane);
-    if (lane < (int)(sizeof(GState) / 16)) reinterpret_cast<uint4*>(&st)[lane] = rec;
-    wave_sync();
-    const GState& S = st;
-    for (int seat = 0; seat < 4; seat++) {
-        float* dst = base + (size_t)seat * RS;
-        const bool acts = (am >> seat) & 1u;
-        if (COMPACT) {
-            if (seat >= NPP || !acts) continue;
-            if (slot >= capacity) return;                  // (the count tells the caller that the buffer was too small)
-            dst = out + (size_t)slot * RS;
-            if (lane == 0) index[slot] = (int32_t)(g * 4u + (uint32_t)seat);
-            slot += 1u;
-        } else if (seat >= NPP || (only_active && !acts)) {
-            if (only_active != 2) enc_zero16(dst, ENC_CH * W, lane);
-            continue;
-        }
-        const int head = (int)(((16u - (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u) >> 2);  // 0 or 2 floats
-        EncByteSink<W> o{raw + ((4 - head) & 3), lut, lane, -1.0f};
-        encode_seat_to<SANMA>(S, seat, lane, hist, o, true);
-        enc_emit_bytes<W>(dst, o.cells, lut, lane, head, o.big);
-        wave_sync();
-    }
-}
-// n floats computed per element into 16-byte stores (4-byte aligned dst: up to three floats before the first boundary)
-template <class F>
-__device__ __forceinline__ void enc_emit_fn(float* dst, int n_floats, int lane, F f) {
-    int head = (int)(((16u - (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u) >> 2);
-    if (head > n_floats) head = n_floats;
-    const int body = (n_floats - head) >> 2, tail0 = head + 4 * body;
-    if (lane < head) dst[lane] = f(lane);
-    float4* d4 = reinterpret_cast<float4*>(dst + head);
-    for (int i = lane; i < body; i += 64) {
-        const int e = head + 4 * i;
-        d4[i] = make_float4(f(e), f(e + 1), f(e + 2), f(e + 3));
-    }
-    if (lane < n_floats - tail0) dst[tail0 + lane] = f(tail0 + lane);
-}
-// encode_extended() of every (game, seat): one wave per seat.  The 215 x W tensor leaves in three groups that share one
-// staging area of bytes: the 74 base channels (EncByteSink), the extended scalars (four per-column channels as floats and a
-// table of the 53 channels that are one value per row) and the 84 meld-overview channels (a 0/1 pattern).  6 KB of LDS per
-// block instead of 12 KB: the kernel waits on table lookups (the ukeire walk), and its duration is inversely proportional to
-// the resident waves (measured by capping them: 13 / 8 / 5 / 3 blocks per CU -> 1.05 / 1.63 / 2.24 / 3.67 ms).
-#define RMJ_ENCX_WAVES 6   /* 3P (85 VGPR left alone = five waves): six waves 691 -> 661 us, seven 667, eight 755; 4P (63 VGPR) the same at any */
-template <bool SANMA>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RMJ_ENCX_WAVES, RMJ_ENCX_WAVES))) void k_encode_ext(Env E, int only_active, const float* __restrict__ decay, float* __restrict__ out) {
-    constexpr int W = SANMA ? ENC_W3 : ENC_W4;
-    constexpr int CH = ENC_EXT_CH;
-    __shared__ GState st;
-    __shared__ __attribute__((aligned(16))) uint8_t raw[(ENC_EXT_C_SLOTS * W + 4 + 15) / 16 * 16];
-    __shared__ float lut[ENC_LUT];
-    __shared__ float tab[ENC_EXT_B_SLOTS];
-    __shared__ float col4[4 * W];
-    __shared__ uint32_t hist[ENC_HIST_WORDS];
-    const int lane = threadIdx.x & 63;
-    const uint32_t g = blockIdx.x >> 2;
-    const int seat = blockIdx.x & 3;
-    float* dst = out + ((size_t)g * 4 + seat) * CH * W;
-    if (only_active) {  // cheap early-out from the 4-byte status word, before the record is fetched
-        const uint32_t stw = E.status[g];
-        const bool acts = ((stw >> seat) & 1u) && !((stw >> 16) & 0xFFu);
-        if (!acts || seat >= (SANMA ? 3 : 4)) {
-            if (only_active == 1)
-                for (int i = lane; i < CH * W; i += 64) dst[i] = 0.0f;
-            return;
-        }
-    }
-    if (lane < (int)(sizeof(GState) / 16)) reinterpret_cast<uint4*>(&st)[lane] = reinterpret_cast<const uint4*>(E.core + g)[lane];
-    enc_lut_init(lut, lane);
-    wave_sync();
-    const GState& S = st;
-    if (seat >= (SANMA ? 3 : 4)) {
-        for (int i = lane; i < CH * W; i += 64) dst[i] = 0.0f;
-        return;
-    }
-    auto head_of = [](const float* p) { return (int)(((16u - (uint32_t)(reinterpret_cast<uintptr_t>(p) & 15u)) & 15u) >> 2); };
-    {   // channels 0..73 (encode_base_into: its own tiles-left count, see encode_seat_to)
-        const int head = head_of(dst);
-        EncByteSink<W> o{raw + ((4 - head) & 3), lut, lane, -1.0f};
-        encode_seat_to<SANMA>(S, seat, lane, hist, o, true, true);
-        enc_emit_bytes<W>(dst, o.cells, lut, lane, head, o.big);
-        wave_sync();
-    }
-    {   // channels 74..93 and 178..214
-        const int n_legal = (((S.active_mask >> seat) & 1u) && !S.is_done) ? (int)E.nlegal[(size_t)g * 4 + seat] : 0;
-        encode_ext_scalars<SANMA>(S, seat, tab, col4, lane, E.sh, decay, E.legal + ((size_t)g * 4 + seat) * RMJ_MAX_LEGAL, n_legal);
-        enc_emit_fn(dst + 74 * W, 20 * W, lane, [&](int e) { return e < 4 * W ? col4[e] : tab[e / W]; });
-        enc_emit_fn(dst + 178 * W, 37 * W, lane, [&](int e) { return tab[20 + e / W]; });
-        wave_sync();
-    }
-    {   // channels 94..177
-        float* d = dst + 94 * W;
-        const int head = head_of(d);
-        uint8_t* cells = raw + ((4 - head) & 3);
-        for (int i = lane; i < (int)sizeof(raw) / 16; i += 64) reinterpret_cast<uint4*>(raw)[i] = make_uint4(0u, 0u, 0u, 0u);
-        wave_sync();
-        encode_ext_melds<SANMA>(S, seat, cells, lane);
-        enc_emit_bytes<W, ENC_EXT_C_SLOTS>(d, cells, lut, lane, head);
-    }
-}
-// Observation batches (rmj_encode_batch_device): the acting seats' rows of one feature set, FEAT = RMJ_FEATURES_*:
-//   BASE             encode()                                   74 x W  (channels 0..73, ext_base = false)
-//   DISCARD_SHANTEN  encode() + encode_extended()'s 74..93      94 x W  (riichienv-ml feat_v2; 4P only)
-//   EXTENDED         encode_extended()                          215 x W (k_encode_ext's rows, byte for byte)
-// in one of two layouts: dense out[n][4][RS] (rows of seats that do not act untouched) or, COMPACT, out[capacity][RS] in (game, seat)
-// order with index[slot] = game * 4 + seat and *count = the number of acting seats.  k_encode_ext's grid of one wave per (game, seat)
-// and its occupancy cap: the extended rows wait on the ukeire walk, and a wave per seat keeps the two or three claimants of a discard
-// in parallel.  A seat that does not act leaves on the 4-byte status word.  The compact slot is k_obs_offsets' offset of the game,
-// plus the totals of the scan blocks before it, plus the acting seats of the game below this one.
-// one row of a feature set: seat `seat` of game `g` into dst (4-byte aligned), by one wave that is a block of its own (the staging areas are the block's LDS)
-template <bool SANMA, int FEAT>
-__device__ __forceinline__ void encode_batch_row(const Env& E, uint32_t g, int seat, const float* __restrict__ decay, float* __restrict__ dst, int lane) {
-    constexpr int W = SANMA ? ENC_W3 : ENC_W4;
-    constexpr bool EXT = FEAT == RMJ_FEATURES_EXTENDED;
-    constexpr int SLOTS = EXT ? ENC_EXT_C_SLOTS : ENC_CH;
-    __shared__ GState st;
-    __shared__ __attribute__((aligned(16))) uint8_t raw[(SLOTS * W + 4 + 15) / 16 * 16];
-    __shared__ float lut[ENC_LUT];
-    __shared__ float tab[ENC_EXT_B_SLOTS];
-    __shared__ float col4[4 * W];
-    __shared__ uint32_t hist[ENC_HIST_WORDS];
-    if (lane < (int)(sizeof(GState) / 16)) reinterpret_cast<uint4*>(&st)[lane] = reinterpret_cast<const uint4*>(E.core + g)[lane];
-    enc_lut_init(lut, lane);
-    wave_sync();
-    const GState& S = st;
-    auto head_of = [](const float* p) { return (int)(((16u - (uint32_t)(reinterpret_cast<uintptr_t>(p) & 15u)) & 15u) >> 2); };
-    {   // channels 0..73: encode() (channel 30 counts every meld tile) or encode_extended()'s base block
-        const int head = head_of(dst);
-        EncByteSink<W> o{raw + ((4 - head) & 3), lut, lane, -1.0f};
-        encode_seat_to<SANMA>(S, seat, lane, hist, o, true, EXT);
-        enc_emit_bytes<W>(dst, o.cells, lut, lane, head, o.big);
-        wave_sync();
-    }
-    if constexpr (FEAT != RMJ_FEATURES_BASE) {   // channels 74..93 (and 178..214 for EXTENDED)
-        const int n_legal = EXT && ((S.active_mask >> seat) & 1u) && !S.is_done ? (int)E.nlegal[(size_t)g * 4 + seat] : 0;
-        encode_ext_scalars<SANMA, EXT>(S, seat, tab, col4, lane, E.sh, decay, E.legal + ((size_t)g * 4 + seat) * RMJ_MAX_LEGAL, n_legal);
-        enc_emit_fn(dst + 74 * W, 20 * W, lane, [&](int e) { return e < 4 * W ? col4[e] : tab[e / W]; });
-        if (EXT) enc_emit_fn(dst + 178 * W, 37 * W, lane, [&](int e) { return tab[20 + e / W]; });
-        wave_sync();
-    }
-    if constexpr (EXT) {   // channels 94..177
-        float* d = dst + 94 * W;
-        const int head = head_of(d);
-        uint8_t* cells = raw + ((4 - head) & 3);
-        for (int i = lane; i < (int)sizeof(raw) / 16; i += 64) reinterpret_cast<uint4*>(raw)[i] = make_uint4(0u, 0u, 0u, 0u);
-        wave_sync();
-        encode_ext_melds<SANMA>(S, seat, cells, lane);
-        enc_emit_bytes<W, ENC_EXT_C_SLOTS>(d, cells, lut, lane, head);
-    }
-}
-template <bool SANMA, int FEAT, bool COMPACT>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RMJ_ENCX_WAVES, RMJ_ENCX_WAVES))) void k_encode_batch(Env E, const float* __restrict__ decay, float* __restrict__ out, uint32_t RS,
-                                                                  const uint32_t* __restrict__ offs, const uint32_t* __restrict__ totals,
-                                                                  int32_t* __restrict__ index, uint32_t capacity, uint32_t* __restrict__ count) {
-    constexpr int NPP = SANMA ? 3 : 4;
-    const int lane = threadIdx.x & 63;
-    const uint32_t g = blockIdx.x >> 2;
-    const int seat = blockIdx.x & 3;
-    if (COMPACT && blockIdx.x == 0) {   // the size of the batch: all block totals
-        const uint32_t all = obs_block_prefix(totals, (E.n_games + OBS_SCAN_BLOCK - 1) / OBS_SCAN_BLOCK, lane);
-        if (lane == 0) *count = all;
-    }
-    const uint32_t stw = E.status[g];
-    const uint32_t am = ((stw >> 16) & 0xFFu) ? 0u : (stw & 0xFu);   // the seats k_obs_offsets counts
-    if (seat >= NPP || !((am >> seat) & 1u)) return;
-    float* dst;
-    if (COMPACT) {
-        const uint32_t slot = offs[g] + obs_block_prefix(totals, g / OBS_SCAN_BLOCK, lane) + (uint32_t)__popc(am & ((1u << seat) - 1u));
-        if (slot >= capacity) return;                  // (the count tells the caller that the buffer was too small)
-        if (lane == 0) index[slot] = (int32_t)(g * 4u + (uint32_t)seat);
-        dst = out + (size_t)slot * RS;
-    } else {
-        dst = out + ((size_t)g * 4 + seat) * RS;
-    }
-    encode_batch_row<SANMA, FEAT>(E, g, seat, decay, dst, lane);
-}
 #include "rmj_logreplay.hip.h"
 #include "rmj_logtext.hip.h"
 #include "rmj_grp.hip.h"
+#include "rmj_handtab.hip.h"
+#include "rmj_events.hip.h"
 
-// ---- auxiliary encoders (row N3): kawa overview, yaku possibility, furiten-ron possibility ----------------------
-// One wave per game; absolute seat order, public information only (the same for every observing seat).
-//   which 0  Observation.encode_kawa_overview           (observation/python.rs:881-925, observation_3p/python.rs:759-810)
-//   which 1  Observation.encode_yaku_possibility        (observation/python.rs:327-455 over yaku_checker.rs:27-412)
-//   which 2  Observation.encode_furiten_ron_possibility (observation/python.rs:251-293)
-template <bool SANMA>
-__global__ __launch_bounds__(64) void k_encode_aux(Env E, int which, float* __restrict__ out) {
-    constexpr int W = SANMA ? ENC_W3 : ENC_W4, NP = SANMA ? 3 : 4;
-    __shared__ GState st;
-    const int lane = threadIdx.x & 63;
-    const uint32_t g = blockIdx.x;
-    if (which == 2) {  // tsumogiri_flags is never filled by the reference (observation/mod.rs:105): every row stays 1.0
-        for (int i = lane; i < NP * 21; i += 64) out[(size_t)g * NP * 21 + i] = 1.0f;
-        return;
-    }
-    if (lane < (int)(sizeof(GState) / 16)) reinterpret_cast<uint4*>(&st)[lane] = reinterpret_cast<const uint4*>(E.core + g)[lane];
-    wave_sync();
-    const GState& S = st;
-    if (which == 0) {
-        // lane = tile column.  Channel k (< 4) is set iff the seat has discarded more than k tiles of the type; channels 4..6 are
-        // the red-five flags with the reference's ids and columns (20 / 24 / 28; 4P column 5 + 9 i, 3P (5, 6) and (6, 15))
-        float* dst = out + (size_t)g * NP * 7 * W;
-        for (int p = 0; p < NP; p++) {
-            const PState& P = S.p[p];
-            int cnt = 0;
-            bool aka0 = false, aka1 = false, aka2 = false;
-            for (int k = 0; k < P.n_discards; k++) {
-                const int t = P.discards[k];
-                cnt += (lane < W && enc_col<SANMA>(t >> 2) == lane);
-                aka0 |= t == 20;
-                aka1 |= t == 24;
-                aka2 |= t == 28;
-            }
-            if (lane < W) {
-                for (int k = 0; k < 4; k++) dst[(p * 7 + k) * W + lane] = cnt > k ? 1.0f : 0.0f;
-                if (!SANMA) {
-                    dst[(p * 7 + 4) * W + lane] = (aka0 && lane == 5) ? 1.0f : 0.0f;
-                    dst[(p * 7 + 5) * W + lane] = (aka1 && lane == 14) ? 1.0f : 0.0f;
-                    dst[(p * 7 + 6) * W + lane] = (aka2 && lane == 23) ? 1.0f : 0.0f;
-                } else {
-                    dst[(p * 7 + 4) * W + lane] = 0.0f;
-                    dst[(p * 7 + 5) * W + lane] = (aka1 && lane == 6) ? 1.0f : 0.0f;
-                    dst[(p * 7 + 6) * W + lane] = (aka2 && lane == 15) ? 1.0f : 0.0f;
-                }
-            }
-        }
-        return;
-    }
-    // which == 1.  lane = tile type: visible[type] = own discards + dora indicators (yaku_checker.rs:42-58); the meld facts
-    // are wave-uniform loops over <= 4 melds x <= 4 tiles.
-    float* dst = out + (size_t)g * NP * 21 * 2;
-    for (int p = 0; p < NP; p++) {
-        const PState& P = S.p[p];
-        int vis = 0;
-        for (int k = 0; k < P.n_discards; k++) vis += (P.discards[k] >> 2) == lane;
-        for (int k = 0; k < S.n_dora; k++) vis += (S.dora[k] >> 2) == lane;
-        const uint64_t vis2 = __ballot(lane < 34 && vis >= 2), vis3 = __ballot(lane < 34 && vis >= 3), vis4 = __ballot(lane < 34 && vis >= 4);
-        uint64_t set_types = 0;  // types with a meld of >= 3 tiles starting with that type (yaku_checker.rs:68-75)
-        bool any_yaochu = false, simple_tile = false, any_number = false, any_honor = false, any_non_terminal = false;
-        bool suit0 = false, suit1 = false, suit2 = false, has_run = false, no_yaochu_meld = false, junchan_bad = false;
-        const int nm = P.n_melds;
-        for (int m = 0; m < nm; m++) {
-            const int len = (P.meld_type[m] == RMJ_MELD_CHI || P.meld_type[m] == RMJ_MELD_PON) ? 3 : 4;
-            const int t0 = P.meld_tiles[m][0] >> 2, t1 = P.meld_tiles[m][1] >> 2, t2 = P.meld_tiles[m][2] >> 2;
-            set_types |= 1ull << t0;
-            if (len == 3 && t0 + 1 == t1 && t1 + 1 == t2 && t0 < 27) has_run = true;
-            bool m_yaochu = false, m_terminal = false, m_honor = false;
-            for (int k = 0; k < len; k++) {
-                const int tt = P.meld_tiles[m][k] >> 2;
-                const bool honor = tt >= 27, terminal = !honor && (tt % 9 == 0 || tt % 9 == 8);
-                m_yaochu |= honor || terminal;
-                m_terminal |= terminal;
-                m_honor |= honor;
-                any_number |= !honor;
-                any_non_terminal |= !terminal;
-                simple_tile |= !honor && !terminal;
-                if (!honor) { suit0 |= tt < 9; suit1 |= tt >= 9 && tt < 18; suit2 |= tt >= 18; }
-            }
-            any_yaochu |= m_yaochu;
-            any_honor |= m_honor;
-            if (!m_yaochu) no_yaochu_meld = true;
-            if (m_honor || !m_terminal) junchan_bad = true;
-        }
-        const int ns = (int)suit0 + (int)suit1 + (int)suit2;
-        const int round_t = 27 + S.round_wind, seat_t = 27 + (p + NP - S.oya) % NP;
-        auto yakuhai_imp = [&](int tt) { return !((set_types >> tt) & 1ull) && ((vis3 >> tt) & 1ull); };
-        const uint64_t koku_req = 0x101ull | (0x101ull << 9) | (0x101ull << 18) | (0x7Full << 27);
-        bool imp = false;
-        switch (lane) {
-            case 0: imp = any_yaochu; break;
-            case 1: imp = yakuhai_imp(31); break;
-            case 2: imp = yakuhai_imp(32); break;
-            case 3: imp = yakuhai_imp(33); break;
-            case 4: imp = yakuhai_imp(round_t); break;
-            case 5: imp = yakuhai_imp(seat_t); break;
-            case 6: imp = nm > 0 && ns >= 2; break;
-            case 7: imp = nm > 0 && (ns >= 2 || (ns == 1 && any_honor)); break;
-            case 8: imp = has_run; break;
-            case 9: imp = nm > 0; break;
-            case 10: imp = ((vis4 >> 31) & 7ull) != 0ull; break;
-            case 11: imp = (((vis2 & ~set_types) >> 31) & 7ull) != 0ull; break;
-            case 12: imp = any_number; break;
-            case 13: imp = any_non_terminal; break;
-            case 14: imp = simple_tile; break;
-            case 15: imp = nm > 0 || (vis4 & koku_req) != 0ull; break;
-            case 16: imp = no_yaochu_meld; break;
-            case 17: imp = junchan_bad; break;
-            case 19: imp = nm > 0; break;
-            default: break;  // 18 sanshoku, 20 ittsu: never impossible
-        }
-        if (lane < 21) {
-            const float v = imp ? 0.0f : 1.0f;
-            reinterpret_cast<float2*>(dst)[p * 21 + lane] = make_float2(v, v);
-        }
-    }
-}
-
-
-// shanten.rs:244-261 / :470-484 (calculate_shanten / calculate_shanten_3p over raw histograms): one thread per hand
-// one thread per hand; the block's 256 hands (8 704 contiguous bytes) are fetched as coalesced 16-byte loads into LDS first
-// (round 2: every thread read its own 34 bytes at a 34-byte stride)
-__global__ __launch_bounds__(256) void k_shanten(ShantenTables T, const uint8_t* counts, uint32_t n, int sanma, int8_t* out) {
-    __shared__ __attribute__((aligned(16))) uint8_t tile[256 * 34 + 16];
-    const uint32_t base = blockIdx.x * 256u;
-    const uint32_t here = n - base < 256u ? n - base : 256u;
-    const size_t off0 = (size_t)base * 34;                       // 8 704 * block: 16-byte aligned when `counts` is
-    const uint32_t bytes = here * 34u;
-    if ((reinterpret_cast<uintptr_t>(counts) & 15u) == 0u) {
-        for (uint32_t i = threadIdx.x; i * 16u < bytes; i += 256u) {
-            if (i * 16u + 16u <= bytes) reinterpret_cast<uint4*>(tile)[i] = reinterpret_cast<const uint4*>(counts + off0)[i];
-            else for (uint32_t b = i * 16u; b < bytes; b++) tile[b] = counts[off0 + b];
-        }
-    } else {
-        for (uint32_t b = threadIdx.x; b < bytes; b += 256u) tile[b] = counts[off0 + b];
-    }
-    __syncthreads();
-    const uint32_t i = base + threadIdx.x;
-    if (i >= n) return;
-    PH h = {0, 0, 0, 0};
-    int total = 0;
-    const uint8_t* mine = tile + threadIdx.x * 34;
-#pragma unroll
-    for (int t = 0; t < 34; t++) {
-        const uint32_t c = mine[t];
-        total += (int)c;
-        const int s = t_suit(t);
-        ph_addv(h, s, (c & 7u) << (3 * (t - 9 * s)));
-    }
-    out[i] = (int8_t)sh_shanten(h, total / 3, sanma != 0, T);
-}
-// (round 4's walk: 82 VGPRs = five waves per SIMD left alone; compiled for six: +5 %, eight: the same.  Round 5's pair-dense walk, 74 VGPRs left alone:
-//  five waves 0.388, six 0.412, seven 0.425, eight 0.430 G hands/s of best ukeire on random hands)
-#define RMJ_UKE_WAVES 8
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RMJ_UKE_WAVES, RMJ_UKE_WAVES))) void k_ukeire(ShantenTables T, const uint8_t* counts, const uint8_t* visible, uint32_t n, int sanma,
-                                                int mode, uint32_t* out) {
-    const int lane = threadIdx.x & 63;
-    const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= n) return;
-    const bool sm = sanma != 0;
-    const int t = lane;                                       // tile type of this lane
-    const uint32_t my_cnt = t < 34 ? counts[(size_t)i * 34 + t] : 0u;
-    const uint32_t my_vis = (t < 34 && visible) ? visible[(size_t)i * 34 + t] : 0u;
-    // wave-uniform histogram: lane t contributes its field, the four words are OR-reduced over the wave
-    PH h = {0, 0, 0, 0};
-    {
-        const int s = t < 34 ? t_suit(t) : 0;
-        uint32_t f = t < 34 ? (my_cnt & 7u) << (3 * (t - 9 * s)) : 0u;
-        uint32_t w[4] = {s == 0 ? f : 0u, s == 1 ? f : 0u, s == 2 ? f : 0u, s == 3 ? f : 0u};
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) w[k] |= (uint32_t)__shfl_xor((int)w[k], off, 64);
-        }
-        h.a = w[0]; h.b = w[1]; h.c = w[2]; h.d = w[3];
-    }
-    const uint32_t res = sh_ukeire_wave(T, h, my_cnt, my_vis, sm, mode, lane);
-    if (lane == 0) out[i] = res;
-}
-
-__global__ void k_score(const uint8_t* han, const uint8_t* fu, const uint8_t* oya, const uint8_t* tsumo, const uint32_t* honba,
-                        const uint8_t* np, uint32_t n, uint32_t* out) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    ScoreOut s = calc_score(han[i], fu[i], oya[i] != 0, tsumo[i] != 0, honba[i], np[i]);
-    out[4 * i] = s.total; out[4 * i + 1] = s.ron; out[4 * i + 2] = s.tsumo_oya; out[4 * i + 3] = s.tsumo_ko;
-}
+static inline dim3 step_grid(uint32_t n) { return dim3((n + RMJ_STEP_WPB - 1) / RMJ_STEP_WPB); }
+// smallest batch that a multi-step device rollout splits over several streams of a handle (rmj_step_random)
+#define RMJ_SPLIT_MIN_GAMES 16384u
+#define RMJ_SPLIT_MIN_PART 8192u   // games per part at least
+#define RMJ_MAX_ROLLOUT_STREAMS 8
+// games per wave by batch size (STEP_F_ROWS_SHIFT; profiles/r04_rows_sweep.txt, fused 4p-red-single rollouts, M env.step/s at 4 | 2 | 1 games
+// per wave: 2 048 games 226 | 254 | 278, 4 096: 435 | 478 | 456, 8 192: 814 | 770 | 522, 16 384: 1 288 | 882 | 599; round 5, profiles/r05_rows_sweep.txt:
+// 2 048: 236 | 272 | 301, 3 072: 345 | 373 | 416, 4 096: 455 | 505 | 492, 6 144: 632 | 692 | 589, 8 192: 845 | 823 | 567)
+#define RMJ_ROWS1_MAX_GAMES 3584u
+#define RMJ_ROWS2_MAX_GAMES 7168u
 
 // ================================================================= host side
 static thread_local std::string g_err;
@@ -1159,7 +190,67 @@ struct DevTmp {
         if (r == hipSuccess) events.push_back(*e);
         return r;
     }
+    void release(void* p) {   // the buffer has an owner that outlives the call: no longer freed here
+        for (void*& q : bufs) if (q == p) q = nullptr;
+    }
 };
+// Host-copy twin of a `_device` entry point: `fill` (the twin) writes `bytes` bytes into the handle's scratch, which are waited for and copied to `out`
+template <class Fill>
+static int fill_and_fetch(rmj_env* h, void* out, size_t bytes, Fill fill) {
+    HIPCHK(hipSetDevice(h->cfg.device));
+    void* sp;
+    int rc = scratch_for(h, bytes, &sp);
+    if (rc) return rc;
+    if ((rc = fill(sp))) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(out, sp, bytes, hipMemcpyDeviceToHost));
+    return RMJ_OK;
+}
+// The same for the two sequence encoders: the seven arrays of `Buffers` (sz: their bytes) at 256-byte steps of the handle's scratch
+template <class Buffers, class Twin>
+static int encode_seq_host(rmj_env* h, int game_style, const Buffers* out, const size_t (&sz)[7], Twin twin) {
+    HIPCHK(hipSetDevice(h->cfg.device));
+    size_t off[8] = {0};
+    for (int i = 0; i < 7; i++) off[i + 1] = off[i] + ((sz[i] + 255) & ~(size_t)255);
+    void* sp;
+    int rc = scratch_for(h, off[7], &sp);
+    if (rc) return rc;
+    char* b = (char*)sp;
+    Buffers d{(uint16_t*)(b + off[0]), (uint8_t*)(b + off[1]), (float*)(b + off[2]), (uint16_t*)(b + off[3]), (uint16_t*)(b + off[4]),
+              (uint16_t*)(b + off[5]), (uint8_t*)(b + off[6])};
+    if ((rc = twin(h, game_style, &d))) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    void* dst[7] = {out->sparse, out->n_sparse, out->numeric, out->progression, out->n_progression, out->candidates, out->n_candidates};
+    for (int i = 0; i < 7; i++) {
+        if (!dst[i]) return fail(RMJ_ERR_ARG, "null output array");
+        HIPCHK(hipMemcpy(dst[i], b + off[i], sz[i], hipMemcpyDeviceToHost));
+    }
+    return RMJ_OK;
+}
+// Average ms of one `launch` (returns an RMJ code): a warm-up, then `reps` launches between two events on `st`; settle: the warm-up is waited for
+template <class Launch>
+static int time_launches(hipStream_t st, uint32_t reps, bool settle, double* avg_ms, Launch launch) {
+    DevTmp tmp;
+    hipEvent_t e0, e1;
+    HIPCHK(tmp.event(&e0));
+    HIPCHK(tmp.event(&e1));
+    int rc;
+    if ((rc = launch())) return rc;  // warm-up
+    if (settle) {
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipDeviceSynchronize());
+    }
+    HIPCHK(hipEventRecord(e0, st));
+    for (uint32_t i = 0; i < reps; i++)
+        if ((rc = launch())) return rc;
+    HIPCHK(hipEventRecord(e1, st));
+    HIPCHK(hipEventSynchronize(e1));
+    HIPCHK(hipGetLastError());
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+    *avg_ms = (double)ms / reps;
+    return RMJ_OK;
+}
 
 // a PPO transition collector bound to a handle (rmj_ppo_create): its pool is one device allocation
 struct rmj_ppo {
@@ -1193,7 +284,39 @@ struct rmj_logreplay {
     uint32_t steps = 0, step = 0;      // steps of a whole replay (the longest slot's events), steps taken
     std::vector<uint32_t> slot_first, slot_logs;
 };
-static int shanten_tables_for(int device, ShantenTables* out);
+// the shanten tables on a device, uploaded once (rmj_create: the handle's Env; the hand API)
+static int shanten_tables_for(int device, ShantenTables* out) {
+    static ShantenTables cache[64];
+    static bool have[64] = {false};
+    static std::mutex mu;   // handles are created from several host threads (MultiGpuVecEnv: one per shard, shards may share a device)
+    if (device < 0 || device >= 64) return fail(RMJ_ERR_ARG, "device ordinal");
+    std::lock_guard<std::mutex> lock(mu);
+    if (!have[device]) {
+        const ShantenHostTables& H = shanten_host_tables();
+        uint64_t *ds, *dh;
+        uint32_t *r9, *r7;
+        HIPCHK(hipMalloc(&ds, H.suit.size() * 8));
+        HIPCHK(hipMalloc(&dh, H.honor.size() * 8));
+        HIPCHK(hipMalloc(&r9, H.rank9.size() * 4));
+        HIPCHK(hipMalloc(&r7, H.rank7.size() * 4));
+        HIPCHK(hipMemcpy(ds, H.suit.data(), H.suit.size() * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(dh, H.honor.data(), H.honor.size() * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(r9, H.rank9.data(), H.rank9.size() * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(r7, H.rank7.data(), H.rank7.size() * 4, hipMemcpyHostToDevice));
+        uint32_t* r2;
+        uint64_t* v6;
+        HIPCHK(hipMalloc(&r2, H.r2.size() * 4));
+        HIPCHK(hipMalloc(&v6, H.v6.size() * 8));
+        HIPCHK(hipMemcpy(r2, H.r2.data(), H.r2.size() * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(v6, H.v6.data(), H.v6.size() * 8, hipMemcpyHostToDevice));
+        cache[device].suit = ds; cache[device].honor = dh; cache[device].rank9 = r9; cache[device].rank7 = r7;
+        cache[device].r2 = r2; cache[device].v6 = v6;
+        have[device] = true;
+    }
+    *out = cache[device];
+    return RMJ_OK;
+}
+// (defined in its section: ahead of rmj_step_random_encode it would put k_encode_base before the fused step kernels in the code object)
 static void launch_encode_base_range(rmj_env* h, hipStream_t st, int only_active, float* d_out, uint32_t g0, uint32_t g1);
 
 extern "C" {
@@ -2150,122 +1273,7 @@ int rmj_format_events(const RmjEvent* ev, const uint32_t* offsets, uint32_t n_ga
     return (buf && *needed <= cap) ? RMJ_OK : RMJ_ERR_RANGE;
 }
 
-// ---- per-round rewards for a trainer on the same GPU -------------------------------------------
-// What riichienv-ml's PPO worker derives on the host between steps (trainers/_ppo_worker.py:100-116, 240-266, 283-291): when a
-// round has ended, the seats' score deltas over that round and the round's opening facts (the GRP features chang / ju / ben /
-// liqibang); when the game has ended, its final scores (rank rewards).  A tracker per handle remembers where every game's current
-// round began; one small launch after a step compares: the wall's hand index moves with every deal (state/wall.rs:36-40), is_done
-// with the end of the game.  ended: 0 = the round goes on, 1 = a round ended and the next one was dealt, 2 = the round and the game
-// ended; a finished game that was restarted (auto-reset, rmj_reset) re-opens silently.
-struct RoundTrack {            // device arrays of the tracker (rmj_env::d_track)
-    uint32_t* hand_index;      // [n] hand index when the game's current round was dealt
-    uint8_t* was_done;         // [n]
-    int32_t* start_scores;     // [n][4]
-    int32_t* start_meta;       // [n][4] round_wind, oya, honba, riichi_sticks at the deal
-    uint8_t* mark;             // [n] set by rmj_reset / rmj_poke_state for the games they touch: the tracker takes the new state as its baseline
-};
-
-__global__ void k_round_track(const GState* __restrict__ core, uint32_t n, RoundTrack T, int baseline, uint8_t* __restrict__ ended, int32_t* __restrict__ delta,
-                              int32_t* __restrict__ meta, uint8_t* __restrict__ kyoku_idx) {
-    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= n) return;
-    const GState& S = core[g];
-    const uint32_t hi = S.hand_index;
-    const bool done = S.is_done != 0;
-    int32_t sc[4];
-    for (int p = 0; p < 4; p++) sc[p] = S.p[p].score;
-    uint8_t e = 0;
-    bool rebase = baseline != 0;
-    const bool marked = T.mark[g] != 0;   // rmj_reset / rmj_poke_state touched the game since the last call: no round of THIS game ended
-    if (marked) { T.mark[g] = 0; rebase = true; }
-    if (!baseline && !marked) {
-        const bool wd = T.was_done[g] != 0;
-        if (wd && !done) rebase = true;                                  // restarted: a new game opens
-        else if (done && !wd) e = 2;                                     // the round that ended the game
-        else if (!done && hi != T.hand_index[g]) { e = 1; rebase = true; }
-    }
-    if (ended) ended[g] = e;
-    if (kyoku_idx) kyoku_idx[g] = S.kyoku_idx;
-    for (int p = 0; p < 4; p++) {
-        if (delta) delta[(size_t)g * 4 + p] = e ? sc[p] - T.start_scores[(size_t)g * 4 + p] : 0;
-        if (meta) meta[(size_t)g * 4 + p] = e ? T.start_meta[(size_t)g * 4 + p] : 0;
-    }
-    if (rebase) {
-        T.hand_index[g] = hi;
-        for (int p = 0; p < 4; p++) T.start_scores[(size_t)g * 4 + p] = sc[p];
-        T.start_meta[(size_t)g * 4 + 0] = S.round_wind; T.start_meta[(size_t)g * 4 + 1] = S.oya;
-        T.start_meta[(size_t)g * 4 + 2] = S.honba; T.start_meta[(size_t)g * 4 + 3] = (int32_t)S.riichi_sticks;
-    }
-    T.was_done[g] = done ? 1 : 0;
-}
-static int round_track_impl(rmj_env* h, int baseline, uint8_t* d_ended, int32_t* d_delta, int32_t* d_meta, uint8_t* d_kyoku_idx);
-
-// ---- bulk drain of the event rings ----------------------------------------------------------
-// RiichiEnv.mjai_log / per-seat logs of EVERY game (riichienv-python/src/env.rs:729-739, state/mod.rs:2094-2148): the records each
-// game slot wrote since the caller's cursor, gathered on the device into one dense buffer (two-level scan of the counts, one wave per
-// game copies its window of the ring) and brought down with one copy.  Cursors are positions in the slot's record stream
-// (GState::ev_count never goes back: a restart moves ev_base), so a window may hold the end of one game and the start of the next.
-// A slot whose ring was lapped since its cursor lost its oldest records: the window starts at the oldest record still there; the loss is
-// booked per slot (RmjEventViews.lost, cumulative) by the drain that hands the window over, not by peeks or failed calls.
-__global__ __launch_bounds__(LC_BLOCK) void k_ev_count(const GState* __restrict__ core, uint32_t n, uint32_t ring, const uint32_t* __restrict__ cursor,
-                                                       uint32_t* __restrict__ first, uint32_t* __restrict__ pre, uint32_t* __restrict__ blk) {
-    __shared__ uint32_t sc[LC_BLOCK];
-    const uint32_t g = blockIdx.x * LC_BLOCK + threadIdx.x;
-    uint32_t c = 0;
-    if (g < n) {
-        const uint32_t total = core[g].ev_count;
-        uint32_t behind = total - cursor[g];           // wrap-safe distance; a cursor "ahead" of the stream (not this slot's) reads as nothing new
-        if (behind > 0x80000000u) behind = 0u;
-        const uint32_t take = behind > ring ? ring : behind;
-        first[g] = total - take;
-        c = take;
-    }
-    sc[threadIdx.x] = c;
-    __syncthreads();
-    for (int off = 1; off < LC_BLOCK; off <<= 1) {
-        uint32_t a = 0;
-        if ((int)threadIdx.x >= off) a = sc[threadIdx.x - off];
-        __syncthreads();
-        sc[threadIdx.x] += a;
-        __syncthreads();
-    }
-    if (g < n) pre[g] = sc[threadIdx.x] - c;
-    if (threadIdx.x == LC_BLOCK - 1) blk[blockIdx.x] = sc[threadIdx.x];
-}
-__global__ void k_ev_scan(uint32_t* blk, uint32_t blocks, uint32_t* total) {
-    if (blockIdx.x || threadIdx.x) return;
-    uint32_t r = 0;
-    for (uint32_t b = 0; b < blocks; b++) { const uint32_t c = blk[b]; blk[b] = r; r += c; }
-    total[0] = r;
-}
-// one wave per game: lane = (record, half) - 16 bytes per lane, 32 records per pass.  newcur[g] = the position behind the window
-// (the window = [first[g], ev_count): the size call of rmj_drain_format keeps what it gathered staged, so no second gather needs a stop position)
-__global__ __launch_bounds__(256) void k_ev_gather(const GState* __restrict__ core, const RmjEvent* __restrict__ events, uint32_t n, uint32_t ring,
-                                                   const uint32_t* __restrict__ first, const uint32_t* __restrict__ pre, const uint32_t* __restrict__ blk,
-                                                   uint32_t cap, RmjEvent* __restrict__ out, uint32_t* __restrict__ offs, uint32_t* __restrict__ newcur) {
-    const uint32_t g = blockIdx.x * 4u + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (g >= n) return;
-    const uint32_t total = core[g].ev_count, lo = first[g], base = blk[g / LC_BLOCK] + pre[g], cnt = total - lo;
-    const uint4* src = reinterpret_cast<const uint4*>(events + (size_t)g * ring);
-    uint4* dst = reinterpret_cast<uint4*>(out);
-    for (uint32_t k = (uint32_t)(lane >> 1); k < cnt; k += 32u) {
-        const uint32_t o = base + k;
-        if (o < cap) dst[2 * (size_t)o + (lane & 1)] = src[2 * (size_t)((lo + k) & (ring - 1u)) + (lane & 1)];
-    }
-    if (lane == 0) {
-        offs[g] = base;
-        if (g == n - 1u) offs[n] = base + cnt;
-        newcur[g] = total;
-    }
-}
-// the drain is handed over: what its windows skipped is lost
-__global__ void k_ev_book(const uint32_t* __restrict__ cursor, const uint32_t* __restrict__ first, uint32_t n, uint32_t* __restrict__ lost) {
-    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= n) return;
-    const uint32_t skipped = first[g] - cursor[g];
-    if (skipped && skipped <= 0x80000000u) lost[g] += skipped;
-}
+// ---- bulk drain of the event rings (k_ev_*: rmj_events.hip.h) ---------------------------------------------
 // the device part of a drain: the handle's scratch holds [cursor | first | pre | blk | total | offsets | new cursor | records]
 struct DrainPlan { uint32_t *d_cur, *d_first, *d_pre, *d_blk, *d_tot, *d_off, *d_new; RmjEvent* d_ev; uint32_t cap; };
 static int drain_device(rmj_env* h, const uint32_t* cursor, uint32_t cap_events, DrainPlan* P, uint32_t* n_events) {
@@ -2423,188 +1431,7 @@ int rmj_drain_format(rmj_handle h, uint32_t* cursor, int seat, char* buf, uint64
     }
     return RMJ_OK;
 }
-// ---- MJAI text on the device (rmj_drain_text / rmj_format_events_device) -------------------------
-// The host formatter's text (rmjh::format_events), byte for byte, written by the GPU with the per-record functions of rmj_evtext.h (the
-// host test holds them to the host formatter).  A game's window is either a run of its ring - stream positions [first[g], ev_count), as
-// k_ev_count computes them, read in place: no dense gather - or a run of caller records ev[offsets[g] .. offsets[g + 1]).
-//   k_text_size   one wave per game, a record per lane: evt_len; the game's stop = the min over its failing indices (the first set bit
-//                 of the first failing chunk's ballot); the game's bytes; the position behind the window (the new cursor).
-//   k_text_scan1 / k_text_scan2   the games' bytes to uint64 bases: an exclusive scan inside blocks of 256 games, then the block sums
-//                 by one workgroup of 1 024 (any number of blocks - 524 288 games are 2 048).
-//   k_text_write  one wave per game: chunks of up to 64 records - as many as fit the wave's LDS staging - are sized again and scanned in
-//                 the wave, each lane writes its record's text into the staging, and the staging goes out as aligned 16-byte stores;
-//                 only the unaligned head and tail bytes of the game's span are stored narrow.
-// The per-record rule (rmj_evtext.h): a TEHAI record gives 0 bytes, a START_KYOKU is a head iff the next two records of the window are
-// TEHAI, the log ends before the first other record that cannot be formatted.  A head in front of the stop has its two TEHAI records in
-// front of it too (the stop is not a TEHAI), so the write pass bounds the window by the stop.
-struct TextSrc {
-    const RmjEvent* ev;     // ring mode: the rings [n][ring]; records mode: the caller's records
-    uint32_t ring;          // ring size (a power of two); 0 = records mode
-    uint32_t rec_bytes;     // sizeof(RmjEvent), as an argument: record addresses are 32 x 32 -> 64-bit multiplies, not 64-bit shifts
-    const uint32_t* lo;     // ring mode: first[g] (a stream position); records mode: offsets [n + 1]
-    const GState* core;     // ring mode: core[g].ev_count ends the window
-};
-__device__ inline uint32_t text_end(const TextSrc& s, uint32_t g) { return s.ring ? s.core[g].ev_count : s.lo[g + 1]; }
-__device__ inline const RmjEvent* text_rec(const TextSrc& s, uint32_t g, uint32_t pos) {
-    const char* b = reinterpret_cast<const char*>(s.ev);
-    if (s.ring) return reinterpret_cast<const RmjEvent*>(b + (uint64_t)g * (s.ring * s.rec_bytes) + (pos & (s.ring - 1u)) * s.rec_bytes);
-    return reinterpret_cast<const RmjEvent*>(b + (uint64_t)pos * s.rec_bytes);
-}
-__device__ inline RmjEvent text_load(const RmjEvent* p) {   // one record in two 16-byte loads
-    union { uint4 q[2]; RmjEvent e; } u;
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    u.q[0] = q[0];
-    u.q[1] = q[1];
-    return u.e;
-}
-__device__ inline uint32_t text_incl_scan(uint32_t v, int lane) {
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t u = (uint32_t)__shfl_up((int)v, d, 64);
-        if (lane >= d) v += u;
-    }
-    return v;
-}
-__global__ __launch_bounds__(256) void k_text_size(TextSrc s, uint32_t n, int seat, uint32_t* __restrict__ nrec, uint32_t* __restrict__ bytes,
-                                                   uint32_t* __restrict__ newcur) {
-    const uint32_t g = blockIdx.x * 4u + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (g >= n) return;
-    const uint32_t lo = s.lo[g], cnt = text_end(s, g) - lo;
-    uint32_t total = 0, stop = cnt;
-    for (uint32_t k0 = 0; k0 < cnt; k0 += 64u) {
-        const uint32_t k = k0 + (uint32_t)lane;
-        int32_t len = 0;
-        if (k < cnt) {
-            const RmjEvent e = text_load(text_rec(s, g, lo + k));
-            len = rmjt::evt_len(e, k + 1u < cnt ? text_rec(s, g, lo + k + 1u) : nullptr, k + 2u < cnt ? text_rec(s, g, lo + k + 2u) : nullptr, seat);
-        }
-        const unsigned long long bad = __ballot(len < 0);
-        if (bad) {
-            const uint32_t f = (uint32_t)__ffsll(bad) - 1u;
-            stop = k0 + f;
-            if ((uint32_t)lane >= f) len = 0;
-        }
-        total += (uint32_t)__shfl((int)text_incl_scan((uint32_t)len, lane), 63, 64);
-        if (bad) break;
-    }
-    if (lane == 0) {
-        nrec[g] = stop;
-        bytes[g] = total;
-        if (newcur) newcur[g] = lo + cnt;
-    }
-}
-__global__ __launch_bounds__(256) void k_text_scan1(const uint32_t* __restrict__ bytes, uint32_t n, uint64_t* __restrict__ pre, uint64_t* __restrict__ blk) {
-    __shared__ uint64_t sc[256];
-    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
-    const uint64_t c = g < n ? bytes[g] : 0u;
-    sc[threadIdx.x] = c;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {
-        uint64_t a = 0;
-        if ((int)threadIdx.x >= off) a = sc[threadIdx.x - off];
-        __syncthreads();
-        sc[threadIdx.x] += a;
-        __syncthreads();
-    }
-    if (g < n) pre[g] = sc[threadIdx.x] - c;
-    if (threadIdx.x == 255) blk[blockIdx.x] = sc[255];
-}
-// blk[0 .. blocks) -> exclusive bases; the total -> offs[n]
-__global__ __launch_bounds__(1024) void k_text_scan2(uint64_t* __restrict__ blk, uint32_t blocks, uint64_t* __restrict__ offs, uint32_t n,
-                                                     uint64_t* __restrict__ total) {
-    __shared__ uint64_t sc[1024];
-    const uint32_t per = (blocks + 1023u) / 1024u, b0 = threadIdx.x * per;
-    uint64_t c = 0;
-    for (uint32_t i = 0; i < per; i++)
-        if (b0 + i < blocks) c += blk[b0 + i];
-    sc[threadIdx.x] = c;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        uint64_t a = 0;
-        if ((int)threadIdx.x >= off) a = sc[threadIdx.x - off];
-        __syncthreads();
-        sc[threadIdx.x] += a;
-        __syncthreads();
-    }
-    uint64_t r = sc[threadIdx.x] - c;
-    for (uint32_t i = 0; i < per; i++)
-        if (b0 + i < blocks) {
-            const uint64_t v = blk[b0 + i];
-            blk[b0 + i] = r;
-            r += v;
-        }
-    if (threadIdx.x == 1023) {
-        offs[n] = sc[1023];
-        total[0] = sc[1023];
-    }
-}
-#define TEXT_STAGE 4096u   // bytes of LDS staging per wave: 64 records of the longest kind do not fit, so a chunk takes what does (>= 1)
-static_assert(TEXT_STAGE >= 16u + rmjt::RMJT_MAX_EVENT_BYTES, "a record must fit behind a partial block");
-struct LdsSink {
-    char* p;
-    __device__ void put(char c) { *p++ = c; }
-};
-__global__ __launch_bounds__(64) void k_text_write(TextSrc s, uint32_t n, int seat, const uint32_t* __restrict__ nrec, const uint32_t* __restrict__ bytes,
-                                                   const uint64_t* __restrict__ pre, const uint64_t* __restrict__ blk, uint64_t* __restrict__ offs,
-                                                   char* __restrict__ text) {
-    __shared__ uint4 stage4[TEXT_STAGE / 16u];
-    char* const stage = reinterpret_cast<char*>(stage4);
-    const uint32_t g = blockIdx.x;
-    const int lane = threadIdx.x;
-    const uint64_t base = blk[g >> 8] + pre[g];
-    if (lane == 0) offs[g] = base;
-    const uint32_t lo = s.lo[g], m = nrec[g], span = bytes[g];
-    char* gp = text + (base & ~(uint64_t)15);    // the global address of stage[0]: 16-byte aligned
-    uint32_t fill = (uint32_t)base & 15u;        // bytes staged (the first `skip` of them are not this game's)
-    uint32_t skip = fill, done = 0;              // done: bytes of the span staged so far (never more than the size pass gave)
-    for (uint32_t k0 = 0; k0 < m;) {
-        const uint32_t k = k0 + (uint32_t)lane;
-        uint32_t len = 0;
-        RmjEvent e;
-        const RmjEvent *t1 = nullptr, *t2 = nullptr;
-        if (k < m) {
-            e = text_load(text_rec(s, g, lo + k));
-            if (e.type == RMJ_EV_START_KYOKU) {
-                t1 = k + 1u < m ? text_rec(s, g, lo + k + 1u) : nullptr;
-                t2 = k + 2u < m ? text_rec(s, g, lo + k + 2u) : nullptr;
-            }
-            const int32_t l = rmjt::evt_len(e, t1, t2, seat);
-            len = l > 0 ? (uint32_t)l : 0u;
-        }
-        const uint32_t incl = text_incl_scan(len, lane);
-        const bool fits = k < m && fill + incl <= TEXT_STAGE && done + incl <= span;
-        const uint32_t take = (uint32_t)__popcll(__ballot(fits));   // the lanes that fit are a prefix of the chunk
-        if (take == 0) break;                                         // (only if the records changed since the size pass)
-        if (fits && len) {
-            LdsSink o{stage + fill + incl - len};
-            rmjt::evt_write(o, e, t1, t2, seat);
-        }
-        const uint32_t chunk = (uint32_t)__shfl((int)incl, (int)take - 1, 64);
-        fill += chunk;
-        done += chunk;
-        k0 += take;
-        __syncthreads();
-        const uint32_t nb = fill >> 4;
-        for (uint32_t b = (uint32_t)lane; b < nb; b += 64u) {
-            if (b == 0 && skip) {   // the span's unaligned head: the block's first bytes belong to the game before
-                for (uint32_t j = skip; j < 16u; j++) gp[j] = stage[j];
-            } else {
-                *reinterpret_cast<uint4*>(gp + b * 16u) = stage4[b];
-            }
-        }
-        const uint32_t rem = fill & 15u;
-        if (nb) {   // the partial block moves to the front of the staging
-            const char c = (uint32_t)lane < rem ? stage[nb * 16u + lane] : 0;
-            __syncthreads();
-            if ((uint32_t)lane < rem) stage[lane] = c;
-            __syncthreads();
-            gp += nb * 16u;
-            fill = rem;
-            skip = 0;
-        }
-    }
-    if ((uint32_t)lane < fill && (uint32_t)lane >= skip) gp[lane] = stage[lane];   // the unaligned tail
-}
+// ---- MJAI text on the device (rmj_drain_text / rmj_format_events_device; k_text_*: rmj_events.hip.h) ------
 // handle-owned buffers of the text calls: device text / offsets / work, pinned text / offsets + cursors; grown on demand
 static int text_device_room(rmj_env* h, uint32_t n_games) {
     const uint32_t blocks = (n_games + 255u) / 256u;
@@ -2737,6 +1564,7 @@ int rmj_format_events_device(rmj_handle h, const RmjEvent* d_ev, const uint32_t*
     out->n_events = ends[1] - ends[0];
     return RMJ_OK;
 }
+// ---- per-round rewards for a trainer on the same GPU (k_round_track: rmj_events.hip.h) --------------------
 static int round_track_impl(rmj_env* h, int baseline, uint8_t* d_ended, int32_t* d_delta, int32_t* d_meta, uint8_t* d_kyoku_idx) {
     const uint32_t n = h->cfg.n_games;
     if (!h->d_track) {
@@ -2851,8 +1679,11 @@ int rmj_calculate_score(int device, const uint8_t* han, const uint8_t* fu, const
 // for 65 536 4P games - the kernel is bound by its own instruction stream and the store epilogue, not by occupancy.
 static void launch_encode_base_range(rmj_env* h, hipStream_t st, int only_active, float* d_out, uint32_t g0, uint32_t g1) {
     const dim3 grid(g1 - g0), block(64);
-    if (h->cfg.game_mode >= 3) hipLaunchKernelGGL((k_encode_base<true, false>), grid, block, 0, st, h->d, only_active, d_out, g0, (const uint32_t*)nullptr, (int32_t*)nullptr, 0u, (const uint32_t*)nullptr, (uint32_t*)nullptr);
-    else hipLaunchKernelGGL((k_encode_base<false, false>), grid, block, 0, st, h->d, only_active, d_out, g0, (const uint32_t*)nullptr, (int32_t*)nullptr, 0u, (const uint32_t*)nullptr, (uint32_t*)nullptr);
+#define RMJ_LAUNCH_BASE(SM) \
+    hipLaunchKernelGGL((k_encode_base<SM, false>), grid, block, 0, st, h->d, only_active, d_out, g0, (const uint32_t*)nullptr, (int32_t*)nullptr, 0u, (const uint32_t*)nullptr, (uint32_t*)nullptr)
+    if (h->cfg.game_mode >= 3) RMJ_LAUNCH_BASE(true);
+    else RMJ_LAUNCH_BASE(false);
+#undef RMJ_LAUNCH_BASE
 }
 static int launch_encode(rmj_handle h, int only_active, float* d_out, bool ext) {
     if (!h || !d_out) return fail(RMJ_ERR_ARG, "null argument");
@@ -2871,8 +1702,11 @@ static void launch_encode_compact(rmj_env* h, float* d_out, int32_t* d_index, ui
     const uint32_t n = h->cfg.n_games, nb = (n + OBS_SCAN_BLOCK - 1) / OBS_SCAN_BLOCK;
     uint32_t* totals = h->d_obs_offs + n;
     hipLaunchKernelGGL(k_obs_offsets, dim3(nb), dim3(OBS_SCAN_BLOCK), 0, h->stream, (const uint32_t*)h->d.status, n, h->d_obs_offs, totals);
-    if (h->cfg.game_mode >= 3) hipLaunchKernelGGL((k_encode_base<true, true>), dim3(n), dim3(64), 0, h->stream, h->d, 2, d_out, 0u, (const uint32_t*)h->d_obs_offs, d_index, capacity, (const uint32_t*)totals, d_count);
-    else hipLaunchKernelGGL((k_encode_base<false, true>), dim3(n), dim3(64), 0, h->stream, h->d, 2, d_out, 0u, (const uint32_t*)h->d_obs_offs, d_index, capacity, (const uint32_t*)totals, d_count);
+#define RMJ_LAUNCH_COMPACT(SM) \
+    hipLaunchKernelGGL((k_encode_base<SM, true>), dim3(n), dim3(64), 0, h->stream, h->d, 2, d_out, 0u, (const uint32_t*)h->d_obs_offs, d_index, capacity, (const uint32_t*)totals, d_count)
+    if (h->cfg.game_mode >= 3) RMJ_LAUNCH_COMPACT(true);
+    else RMJ_LAUNCH_COMPACT(false);
+#undef RMJ_LAUNCH_COMPACT
 }
 int rmj_encode_compact_device(rmj_handle h, float* d_out, int32_t* d_index, uint32_t capacity, uint32_t* d_count) {
     if (!h || !d_out || !d_index || !d_count) return fail(RMJ_ERR_ARG, "null argument");
@@ -2894,35 +1728,14 @@ int rmj_step_random_encode_compact(rmj_handle h, uint64_t policy_seed, uint32_t 
     return RMJ_OK;
 }
 int rmj_bench_encode_compact(rmj_handle h, float* d_out, int32_t* d_index, uint32_t capacity, uint32_t* d_count, uint32_t reps, double* avg_ms) {
-    DevTmp tmp;
     if (!h || !d_out || !d_index || !d_count || !avg_ms || reps == 0) return fail(RMJ_ERR_ARG, "bad argument");
     HIPCHK(hipSetDevice(h->cfg.device));
-    hipEvent_t e0, e1;
-    HIPCHK(tmp.event(&e0));
-    HIPCHK(tmp.event(&e1));
-    launch_encode_compact(h, d_out, d_index, capacity, d_count);  // warm-up
-    HIPCHK(hipEventRecord(e0, h->stream));
-    for (uint32_t i = 0; i < reps; i++) launch_encode_compact(h, d_out, d_index, capacity, d_count);
-    HIPCHK(hipEventRecord(e1, h->stream));
-    HIPCHK(hipEventSynchronize(e1));
-    HIPCHK(hipGetLastError());
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    *avg_ms = (double)ms / reps;
-    return RMJ_OK;
+    return time_launches(h->stream, reps, false, avg_ms, [&] { launch_encode_compact(h, d_out, d_index, capacity, d_count); return RMJ_OK; });
 }
 int rmj_encode(rmj_handle h, int only_active, float* out) {
     if (!h || !out) return fail(RMJ_ERR_ARG, "null argument");
-    HIPCHK(hipSetDevice(h->cfg.device));
-    size_t bytes = (size_t)h->cfg.n_games * 4 * (size_t)h->d.enc_stride * sizeof(float);
-    void* sp;
-    int rc = scratch_for(h, bytes, &sp);
-    if (rc) return rc;
-    float* d = (float*)sp;
-    if ((rc = rmj_encode_device(h, only_active, d))) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(out, d, bytes, hipMemcpyDeviceToHost));
-    return RMJ_OK;
+    const size_t bytes = (size_t)h->cfg.n_games * 4 * (size_t)h->d.enc_stride * sizeof(float);
+    return fill_and_fetch(h, out, bytes, [&](void* d) { return rmj_encode_device(h, only_active, (float*)d); });
 }
 
 static size_t aux_floats(const rmj_env* h, int which) {
@@ -2941,15 +1754,8 @@ int rmj_encode_aux_device(rmj_handle h, int which, float* d_out) {
 int rmj_encode_aux(rmj_handle h, int which, float* out) {
     if (!h || !out) return fail(RMJ_ERR_ARG, "null argument");
     if (which < 0 || which > 2) return fail(RMJ_ERR_ARG, "unknown auxiliary encoder");
-    HIPCHK(hipSetDevice(h->cfg.device));
     const size_t bytes = (size_t)h->cfg.n_games * aux_floats(h, which) * sizeof(float);
-    void* sp;
-    int rc = scratch_for(h, bytes, &sp);
-    if (rc) return rc;
-    if ((rc = rmj_encode_aux_device(h, which, (float*)sp))) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(out, sp, bytes, hipMemcpyDeviceToHost));
-    return RMJ_OK;
+    return fill_and_fetch(h, out, bytes, [&](void* d) { return rmj_encode_aux_device(h, which, (float*)d); });
 }
 
 // sequence features (row N3, 4P only like the reference): see rmj_seq.hip.h
@@ -2965,25 +1771,9 @@ int rmj_encode_seq_device(rmj_handle h, int game_style, const RmjSeqBuffers* d) 
 }
 int rmj_encode_seq(rmj_handle h, int game_style, const RmjSeqBuffers* out) {
     if (!h || !out) return fail(RMJ_ERR_ARG, "null argument");
-    HIPCHK(hipSetDevice(h->cfg.device));
     const size_t n = h->cfg.n_games;
     const size_t sz[7] = {n * 4 * RMJ_SEQ_SPARSE * 2, n * 4, n * 4 * 12 * 4, n * RMJ_SEQ_PROG * 5 * 2, n * 2, n * 4 * RMJ_SEQ_CAND * 4 * 2, n * 4};
-    size_t off[8] = {0};
-    for (int i = 0; i < 7; i++) off[i + 1] = off[i] + ((sz[i] + 255) & ~(size_t)255);
-    void* sp;
-    int rc = scratch_for(h, off[7], &sp);
-    if (rc) return rc;
-    char* b = (char*)sp;
-    RmjSeqBuffers d{(uint16_t*)(b + off[0]), (uint8_t*)(b + off[1]), (float*)(b + off[2]), (uint16_t*)(b + off[3]), (uint16_t*)(b + off[4]),
-                    (uint16_t*)(b + off[5]), (uint8_t*)(b + off[6])};
-    if ((rc = rmj_encode_seq_device(h, game_style, &d))) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    void* dst[7] = {out->sparse, out->n_sparse, out->numeric, out->progression, out->n_progression, out->candidates, out->n_candidates};
-    for (int i = 0; i < 7; i++) {
-        if (!dst[i]) return fail(RMJ_ERR_ARG, "null output array");
-        HIPCHK(hipMemcpy(dst[i], b + off[i], sz[i], hipMemcpyDeviceToHost));
-    }
-    return RMJ_OK;
+    return encode_seq_host(h, game_style, out, sz, rmj_encode_seq_device);
 }
 
 int rmj_encode_seq_delta_device(rmj_handle h, int game_style, const RmjSeqDeltaBuffers* d) {
@@ -2998,41 +1788,17 @@ int rmj_encode_seq_delta_device(rmj_handle h, int game_style, const RmjSeqDeltaB
 }
 int rmj_encode_seq_delta(rmj_handle h, int game_style, const RmjSeqDeltaBuffers* out) {
     if (!h || !out) return fail(RMJ_ERR_ARG, "null argument");
-    HIPCHK(hipSetDevice(h->cfg.device));
     const size_t n = h->cfg.n_games;
     const size_t sz[7] = {n * 4 * RMJ_SEQ_SPARSE * 2, n * 4, n * 4 * 12 * 4, n * 4 * RMJ_SEQ_DELTA_PROG * 5 * 2, n * 4 * 2,
                           n * 4 * RMJ_SEQ_CAND * 4 * 2, n * 4};
-    size_t off[8] = {0};
-    for (int i = 0; i < 7; i++) off[i + 1] = off[i] + ((sz[i] + 255) & ~(size_t)255);
-    void* sp;
-    int rc = scratch_for(h, off[7], &sp);
-    if (rc) return rc;
-    char* b = (char*)sp;
-    RmjSeqDeltaBuffers d{(uint16_t*)(b + off[0]), (uint8_t*)(b + off[1]), (float*)(b + off[2]), (uint16_t*)(b + off[3]), (uint16_t*)(b + off[4]),
-                         (uint16_t*)(b + off[5]), (uint8_t*)(b + off[6])};
-    if ((rc = rmj_encode_seq_delta_device(h, game_style, &d))) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    void* dst[7] = {out->sparse, out->n_sparse, out->numeric, out->progression, out->n_progression, out->candidates, out->n_candidates};
-    for (int i = 0; i < 7; i++) {
-        if (!dst[i]) return fail(RMJ_ERR_ARG, "null output array");
-        HIPCHK(hipMemcpy(dst[i], b + off[i], sz[i], hipMemcpyDeviceToHost));
-    }
-    return RMJ_OK;
+    return encode_seq_host(h, game_style, out, sz, rmj_encode_seq_delta_device);
 }
 
 int rmj_encode_extended_device(rmj_handle h, int only_active, float* d_out) { return launch_encode(h, only_active, d_out, true); }
 int rmj_encode_extended(rmj_handle h, int only_active, float* out) {
     if (!h || !out) return fail(RMJ_ERR_ARG, "null argument");
-    HIPCHK(hipSetDevice(h->cfg.device));
-    size_t bytes = (size_t)h->cfg.n_games * 4 * ENC_EXT_CH * (h->cfg.game_mode >= 3 ? ENC_W3 : ENC_W4) * sizeof(float);
-    void* sp;
-    int rc = scratch_for(h, bytes, &sp);
-    if (rc) return rc;
-    float* d = (float*)sp;
-    if ((rc = rmj_encode_extended_device(h, only_active, d))) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(out, d, bytes, hipMemcpyDeviceToHost));
-    return RMJ_OK;
+    const size_t bytes = (size_t)h->cfg.n_games * 4 * ENC_EXT_CH * (h->cfg.game_mode >= 3 ? ENC_W3 : ENC_W4) * sizeof(float);
+    return fill_and_fetch(h, out, bytes, [&](void* d) { return rmj_encode_extended_device(h, only_active, (float*)d); });
 }
 
 // ---- observation batches (k_encode_batch) ------------------------------------------------------------------
@@ -3334,18 +2100,20 @@ int rmj_logset_info(rmj_logset_handle s, RmjLogsetInfo* out, uint32_t* kyoku_off
     if (kyoku_offsets) memcpy(kyoku_offsets, s->koff.data(), (size_t)(s->M + 1) * 4);
     return RMJ_OK;
 }
-// body of rmj_logset_create_from_text: everything in `tmp` is freed by the caller, whatever happens
-static int logset_from_text_impl(rmj_logset* s, const uint8_t* text, const uint64_t* ranges, uint32_t num_players, uint32_t flags, std::vector<void*>& tmp) {
+// body of rmj_logset_create_from_text: the buffers in `tmp` are freed by the caller, whatever happens; the set's own by rmj_logset_destroy
+static int logset_from_text_impl(rmj_logset* s, const uint8_t* text, const uint64_t* ranges, uint32_t num_players, uint32_t flags, DevTmp& tmp) {
     using namespace rmjlt;
     const uint32_t M = s->M;
     const bool on_device = (flags & RMJ_LOGTEXT_ON_DEVICE) != 0u;
-    auto dalloc = [&](void** p, size_t bytes, bool keep) -> bool {
-        if (hipMalloc(p, bytes ? bytes : 16u) != hipSuccess) { *p = nullptr; (void)hipGetLastError(); return false; }
-        if (!keep) tmp.push_back(*p);
-        return true;
+    auto dalloc = [&](void* pp, size_t bytes, bool keep) -> int {   // pp: the address of a device pointer of any type; keep: the buffer belongs to the set
+        uint8_t* q;
+        const hipError_t e = tmp.alloc(&q, bytes ? bytes : 16u);
+        *(void**)pp = q;
+        if (e != hipSuccess) { (void)hipGetLastError(); return fail(RMJ_ERR_HIP, "rmj_logset_create_from_text: no device memory"); }
+        if (keep) tmp.release(q);
+        return RMJ_OK;
     };
-#define LT_ALLOC(ptr, bytes, keep) \
-    if (!dalloc((void**)&(ptr), (bytes), (keep))) return fail(RMJ_ERR_HIP, "rmj_logset_create_from_text: no device memory")
+    int rc;
     // the ranges on the host: O(n_logs) words, checked before a kernel trusts them
     std::vector<uint64_t> hr((size_t)2 * M);
     if (M) {
@@ -3366,8 +2134,8 @@ static int logset_from_text_impl(rmj_logset* s, const uint8_t* text, const uint6
     if (!on_device) {   // one upload of the bytes the ranges span, the ranges rebased on it
         uint8_t* t = nullptr;
         uint64_t* r = nullptr;
-        LT_ALLOC(t, (size_t)(hi - lo), false);
-        LT_ALLOC(r, hr.size() * 8, false);
+        if ((rc = dalloc(&t, (size_t)(hi - lo), false))) return rc;
+        if ((rc = dalloc(&r, hr.size() * 8, false))) return rc;
         if (hi > lo) HIPCHK(hipMemcpy(t, text + lo, (size_t)(hi - lo), hipMemcpyHostToDevice));
         for (uint32_t l = 0; l < M; l++) {
             if (hr[2 * (size_t)l + 1] == hr[2 * (size_t)l]) hr[2 * (size_t)l] = hr[2 * (size_t)l + 1] = lo;   // an empty range may lie anywhere
@@ -3381,17 +2149,17 @@ static int logset_from_text_impl(rmj_logset* s, const uint8_t* text, const uint6
     uint32_t *d_cnt = nullptr, *d_choff = nullptr, *d_max = nullptr, *d_kcnt = nullptr;
     unsigned long long *d_tot = nullptr, *d_ferr = nullptr;
     const size_t ob = (size_t)(M + 1) * 4;
-    LT_ALLOC(d_cnt, (size_t)M * 4, false);
-    LT_ALLOC(d_choff, ob, false);
-    LT_ALLOC(d_max, 4, false);
-    LT_ALLOC(d_kcnt, (size_t)M * 4, false);
-    LT_ALLOC(d_tot, 3 * 8, false);
-    LT_ALLOC(d_ferr, (size_t)M * 8, false);
-    LT_ALLOC(s->d_off, ob, true);
-    LT_ALLOC(s->d_koff, ob, true);
-    LT_ALLOC(s->d_status, M, true);
-    LT_ALLOC(s->d_errline, (size_t)M * 4, true);
-    LT_ALLOC(s->d_dec, (size_t)M * 4, true);
+    if ((rc = dalloc(&d_cnt, (size_t)M * 4, false))) return rc;
+    if ((rc = dalloc(&d_choff, ob, false))) return rc;
+    if ((rc = dalloc(&d_max, 4, false))) return rc;
+    if ((rc = dalloc(&d_kcnt, (size_t)M * 4, false))) return rc;
+    if ((rc = dalloc(&d_tot, 3 * 8, false))) return rc;
+    if ((rc = dalloc(&d_ferr, (size_t)M * 8, false))) return rc;
+    if ((rc = dalloc(&s->d_off, ob, true))) return rc;
+    if ((rc = dalloc(&s->d_koff, ob, true))) return rc;
+    if ((rc = dalloc(&s->d_status, M, true))) return rc;
+    if ((rc = dalloc(&s->d_errline, (size_t)M * 4, true))) return rc;
+    if ((rc = dalloc(&s->d_dec, (size_t)M * 4, true))) return rc;
     HIPCHK(hipMemset(d_max, 0, 4));
     HIPCHK(hipMemset(d_kcnt, 0, (size_t)M * 4 + (M ? 0 : 16)));
     HIPCHK(hipMemset(s->d_dec, 0, (size_t)M * 4 + (M ? 0 : 16)));
@@ -3409,11 +2177,11 @@ static int logset_from_text_impl(rmj_logset* s, const uint8_t* text, const uint6
     s->total = total;
     uint32_t *d_es = nullptr, *d_ee = nullptr, *d_el = nullptr;
     rmjp::Side* d_side = nullptr;
-    LT_ALLOC(d_es, (size_t)total * 4, false);
-    LT_ALLOC(d_ee, (size_t)total * 4, false);
-    LT_ALLOC(d_el, (size_t)total * 4, false);
-    LT_ALLOC(d_side, (size_t)total * sizeof(rmjp::Side), false);
-    LT_ALLOC(s->d_ev, (size_t)total * 3 * sizeof(RmjEvent), true);
+    if ((rc = dalloc(&d_es, (size_t)total * 4, false))) return rc;
+    if ((rc = dalloc(&d_ee, (size_t)total * 4, false))) return rc;
+    if ((rc = dalloc(&d_el, (size_t)total * 4, false))) return rc;
+    if ((rc = dalloc(&d_side, (size_t)total * sizeof(rmjp::Side), false))) return rc;
+    if ((rc = dalloc(&s->d_ev, (size_t)total * 3 * sizeof(RmjEvent), true))) return rc;
     if (total) {
         // line index, then the records
         hipLaunchKernelGGL(k_lt_lines<true>, per_log, b256, 0, 0, d_text, d_ranges, M, (uint32_t*)nullptr, (const uint32_t*)s->d_off, d_es, d_ee, d_el);
@@ -3429,13 +2197,12 @@ static int logset_from_text_impl(rmj_logset* s, const uint8_t* text, const uint6
     HIPCHK(hipMemcpy(s->koff.data(), s->d_koff, ob, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(&s->max_len, d_max, 4, hipMemcpyDeviceToHost));
     s->K = s->koff[M];
-    LT_ALLOC(s->d_start, (size_t)s->K * 16, true);
-    LT_ALLOC(s->d_end, (size_t)s->K * 16, true);
+    if ((rc = dalloc(&s->d_start, (size_t)s->K * 16, true))) return rc;
+    if ((rc = dalloc(&s->d_end, (size_t)s->K * 16, true))) return rc;
     if (M) hipLaunchKernelGGL(k_lt_tables, per_log, b256, 0, 0, (const rmjp::Side*)d_side, (const uint32_t*)s->d_off, (const uint32_t*)s->d_koff, M,
                               (const unsigned long long*)d_ferr, s->d_start, s->d_end, s->d_status, s->d_errline);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
-#undef LT_ALLOC
     return RMJ_OK;
 }
 int rmj_logset_create_from_text(int device, const uint8_t* text, const uint64_t* ranges, uint32_t n_logs, uint32_t num_players, uint32_t flags, rmj_logset_handle* out) {
@@ -3448,10 +2215,11 @@ int rmj_logset_create_from_text(int device, const uint8_t* text, const uint64_t*
     rmj_logset* s = new rmj_logset();
     s->device = device;
     s->M = n_logs;
-    std::vector<void*> tmp;
-    rc = logset_from_text_impl(s, text, ranges, num_players, flags, tmp);
-    if (rc) (void)hipDeviceSynchronize();
-    for (void* p : tmp) hipFree(p);
+    {
+        DevTmp tmp;
+        rc = logset_from_text_impl(s, text, ranges, num_players, flags, tmp);
+        if (rc) (void)hipDeviceSynchronize();
+    }
     if (rc) {
         (void)hipGetLastError();
         rmj_logset_destroy(s);
@@ -3707,37 +2475,6 @@ int rmj_logreplay_counts(rmj_logreplay_handle r, RmjLogReplayCounts* out) {
 }
 
 // ---- shanten (row A7) -------------------------------------------------------------------------------
-static int shanten_tables_for(int device, ShantenTables* out) {
-    static ShantenTables cache[64];
-    static bool have[64] = {false};
-    static std::mutex mu;   // handles are created from several host threads (MultiGpuVecEnv: one per shard, shards may share a device)
-    if (device < 0 || device >= 64) return fail(RMJ_ERR_ARG, "device ordinal");
-    std::lock_guard<std::mutex> lock(mu);
-    if (!have[device]) {
-        const ShantenHostTables& H = shanten_host_tables();
-        uint64_t *ds, *dh;
-        uint32_t *r9, *r7;
-        HIPCHK(hipMalloc(&ds, H.suit.size() * 8));
-        HIPCHK(hipMalloc(&dh, H.honor.size() * 8));
-        HIPCHK(hipMalloc(&r9, H.rank9.size() * 4));
-        HIPCHK(hipMalloc(&r7, H.rank7.size() * 4));
-        HIPCHK(hipMemcpy(ds, H.suit.data(), H.suit.size() * 8, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dh, H.honor.data(), H.honor.size() * 8, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(r9, H.rank9.data(), H.rank9.size() * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(r7, H.rank7.data(), H.rank7.size() * 4, hipMemcpyHostToDevice));
-        uint32_t* r2;
-        uint64_t* v6;
-        HIPCHK(hipMalloc(&r2, H.r2.size() * 4));
-        HIPCHK(hipMalloc(&v6, H.v6.size() * 8));
-        HIPCHK(hipMemcpy(r2, H.r2.data(), H.r2.size() * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(v6, H.v6.data(), H.v6.size() * 8, hipMemcpyHostToDevice));
-        cache[device].suit = ds; cache[device].honor = dh; cache[device].rank9 = r9; cache[device].rank7 = r7;
-        cache[device].r2 = r2; cache[device].v6 = v6;
-        have[device] = true;
-    }
-    *out = cache[device];
-    return RMJ_OK;
-}
 int rmj_shanten(int device, const uint8_t* counts, uint32_t n, int sanma, int8_t* out) {
     DevTmp tmp;
     if (!counts || !out) return fail(RMJ_ERR_ARG, "null argument");
@@ -3966,23 +2703,9 @@ int rmj_bench_rollout_validated(rmj_handle h, uint64_t policy_seed, uint32_t war
 // Average duration of one encoder launch over `reps` back-to-back launches (HIP events on the handle's stream): the
 // roofline figure of BASELINE's feature-output configuration.  d_out like rmj_encode_device / rmj_encode_extended_device.
 int rmj_bench_encode(rmj_handle h, int extended, int only_active, float* d_out, uint32_t reps, double* avg_ms) {
-    DevTmp tmp;
     if (!h || !d_out || !avg_ms || reps == 0) return fail(RMJ_ERR_ARG, "bad argument");
     HIPCHK(hipSetDevice(h->cfg.device));
-    hipEvent_t e0, e1;
-    HIPCHK(tmp.event(&e0));
-    HIPCHK(tmp.event(&e1));
-    int rc;
-    if ((rc = launch_encode(h, only_active, d_out, extended != 0))) return rc;  // warm-up
-    HIPCHK(hipEventRecord(e0, h->stream));
-    for (uint32_t i = 0; i < reps; i++)
-        if ((rc = launch_encode(h, only_active, d_out, extended != 0))) return rc;
-    HIPCHK(hipEventRecord(e1, h->stream));
-    HIPCHK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    *avg_ms = (double)ms / reps;
-    return RMJ_OK;
+    return time_launches(h->stream, reps, false, avg_ms, [&] { return launch_encode(h, only_active, d_out, extended != 0); });
 }
 // Kernel-gate benchmark (the groups of riichienv-core/benches/agari_bench.rs:142-376): average duration of
 // ONE launch of a hand-math kernel over `n` device-resident inputs, HIP events around `reps` back-to-back launches after a warm-up
@@ -4006,10 +2729,7 @@ int rmj_bench_hand_kernel(int device, int which, const void* a, const void* b, u
         HIPCHK(hipMemcpy(d_b, b, in_b, hipMemcpyHostToDevice));
     }
     HIPCHK(tmp.alloc(&d_o, (size_t)n * (which == 0 ? sizeof(RmjHandResult) : 16)));
-    hipEvent_t e0, e1;
-    HIPCHK(tmp.event(&e0));
-    HIPCHK(tmp.event(&e1));
-    auto launch = [&]() {
+    return time_launches(0, reps, true, avg_ms, [&] {
         switch (which) {
             case 0: hipLaunchKernelGGL(k_eval_hands, dim3((n + 15u) / 16u), dim3(256), 0, 0, (const RmjHandCase*)d_a, n, (RmjHandResult*)d_o); break;
             case 1: hipLaunchKernelGGL(k_agari_counts, dim3((n + 15) / 16), dim3(256), 0, 0, (const uint8_t*)d_a, n, d_o, d_o + n, (uint64_t*)(d_o + 8 * (size_t)n)); break;
@@ -4019,19 +2739,8 @@ int rmj_bench_hand_kernel(int device, int which, const void* a, const void* b, u
             default: hipLaunchKernelGGL(k_score, dim3((n + 255) / 256), dim3(256), 0, 0, (const uint8_t*)d_a, (const uint8_t*)d_a + n, (const uint8_t*)d_a + 2 * (size_t)n,
                                         (const uint8_t*)d_a + 3 * (size_t)n, (const uint32_t*)d_b, (const uint8_t*)d_a + 4 * (size_t)n, n, (uint32_t*)d_o); break;
         }
-    };
-    launch();
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipEventRecord(e0, 0));
-    for (uint32_t i = 0; i < reps; i++) launch();
-    HIPCHK(hipEventRecord(e1, 0));
-    HIPCHK(hipEventSynchronize(e1));
-    HIPCHK(hipGetLastError());
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    *avg_ms = (double)ms / reps;
-    return RMJ_OK;
+        return RMJ_OK;
+    });
 }
 // Observation outputs of ONE game (sampled parity checks at batch sizes where fetching every game's lists is wasteful)
 int rmj_peek_outputs(rmj_handle h, uint32_t game, rmj_action_t* legal /*[4][64]*/, uint8_t* counts /*[4]*/, uint8_t* mask /*[4][82]*/,

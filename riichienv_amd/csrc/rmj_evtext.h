@@ -1,5 +1,5 @@
 // One MJAI event record -> its JSON text, as scalar functions that the host and the device share: the device formatter of the logs of
-// every game (k_text_size / k_text_write in rmj_api.hip: rmj_drain_text, rmj_format_events_device) and the host test that holds them to
+// every game (k_text_size / k_text_write in rmj_events.hip.h: rmj_drain_text, rmj_format_events_device) and the host test that holds them to
 // rmjh::format_event / format_events (rmj_host.h), which stay the definition.  Plain C++17 under g++; __host__ __device__ under hipcc.
 // No HIP intrinsics in this file.
 //

@@ -1,6 +1,6 @@
 // Log sample builder (riichienv-ml datasets/mjai_logs.py:62-129 MCDataset) on the device: many MJAI logs replayed in lock-step from one
 // resident event stream, and what the dataset yields per decision - feature row, mask, action id, return, rank - left in a pool.
-// Included from rmj_api.hip behind the batch encoder (encode_batch_row, obs_block_prefix, ppo_block_scan come from there).
+// Included from rmj_api.hip behind rmj_ppo.hip.h (encode_batch_row, obs_block_prefix come from rmj_obs.hip.h, ppo_block_scan from rmj_ppo.hip.h).
 //
 // Slots and logs.  The M logs of a log set are replayed in n <= M game slots.  Which slot replays which logs, in which order, is
 // fixed before the replay by lr_assign: the logs are handed out in log order, each to the slot that becomes free first when every

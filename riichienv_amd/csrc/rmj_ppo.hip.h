@@ -1,6 +1,6 @@
 // PPO transition collector (riichienv-ml trainers/_ppo_worker.py:129-391 collect_episodes, :393-466 evaluate_episodes) on the device:
 // the hero / opponent action selector, the trajectory pool, the per-kyoku GAE and the flattening into the trainer's arrays.
-// Included from rmj_api.hip behind k_sample_ids (sample_ids_row, obs_block_prefix come from there).
+// Included from rmj_api.hip behind rmj_obs.hip.h (sample_ids_row comes from rmj_policy.hip.h, obs_block_prefix from rmj_obs.hip.h).
 //
 // The pool is a flat array of `capacity` transitions.  Slots are handed out in (call, game) order: a record call scans the games that
 // record (k_ppo_scan: block prefix counts, like k_obs_offsets), every recording game takes slot fill + its prefix (k_ppo_record) and

@@ -12,7 +12,7 @@
 // Reference semantics: riichienv-core/src/state/mod.rs (step, _resolve_discard, _resolve_kan,
 // _accept_riichi, _deal_next, _initialize_next_round, _initialize_round, _trigger_ryukyoku,
 // check_abortive_draw, _reveal_kan_dora), state/legal_actions.rs, riichienv-python/src/env.rs.
-// NOTE: this file is included ONCE PER VARIANT by rmj_api.hip with
+// NOTE: this file is included ONCE PER VARIANT by rmj_api.hip (behind rmj_policy.hip.h: step flags, state load / store) with
 //   RMJ_NS    = namespace of the instantiation (rmj4 / rmj3)
 //   RMJ_SANMA = 0 (state/, 4 seats, 136 tiles) or 1 (state_3p/, 3 seats, 108 tiles, kita, no chi)
 // so that the seat count and the sanma switches are compile-time constants on each variant's hot path.

@@ -1,6 +1,6 @@
 // Sanitizer harness of the HOST side of the C-ABI (riichienv_amd/csrc/rmj_host.h: state record <-> view, MJAI formatter) - built with
-// -fsanitize=address,undefined by scripts/run_sanitizers.sh.  GPU-side sanitizers do not exist on this pool; this covers the code of
-// rmj_api.hip that runs on the CPU and handles caller-supplied data.
+// -fsanitize=address,undefined by scripts/run_sanitizers.sh.  GPU-side sanitizers do not exist on this pool; this covers the code behind
+// rmj_api.hip's entry points that runs on the CPU and handles caller-supplied data.
 //   * random state views (in and out of range) through from_view / to_view: accepted views round-trip field by field
 //   * random and adversarial event records (every type byte, any counts) through the single and the batch formatter with
 //     buffers of every size: no out-of-bounds access, the sizes the two passes report agree

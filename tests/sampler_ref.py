@@ -1,4 +1,4 @@
-"""Float64 restatement of the trainer-side masked categorical sampler (sample_ids_row in riichienv_amd/csrc/rmj_api.hip: the
+"""Float64 restatement of the trainer-side masked categorical sampler (sample_ids_row in riichienv_amd/csrc/rmj_policy.hip.h: the
 kernel behind rmj_sample_ids_device / TorchVecEnv.sample_ids and the draw in front of rmj_step_sample_encode_device).  numpy only.
 
 For every seat that is to act (active bit set, game not done, nlegal > 0) and every id < A (82 in 4P, 60 in 3P) whose mask byte
