@@ -1,7 +1,10 @@
-"""ctypes mirror of include/riichi_mi355x.h (POD structs + packed-action helpers).
+"""ctypes mirror of include/riichi_mi355x.h and include/riichi_mi355x_bench.h: the POD structs, the packed-action helpers,
+PROTOTYPES - the one table of every function the two headers declare, which vecenv.load_lib() applies - and the wrapper
+that hands library-owned device memory to torch (device_tensor).  tests/test_abi.py holds the structs and the table to the
+headers: a new C entry is its header declaration plus one row here.
 
-Pure data-layout definitions: no compute.  Shared by the product binding
-(riichienv_amd.vecenv) and by the test-only oracle binding (oracle/oracle.py).
+Pure data-layout definitions: no compute, no torch import.  Shared by the product binding (riichienv_amd.vecenv) and by
+the test-only oracle binding (oracle/oracle.py).
 """
 from __future__ import annotations
 
@@ -223,6 +226,8 @@ class SeqBuffers(C.Structure):
                 ("n_progression", C.c_void_p), ("candidates", C.c_void_p), ("n_candidates", C.c_void_p)]
 
 
+SeqDeltaBuffers = SeqBuffers   # RmjSeqDeltaBuffers: the same fields (the arrays behind progression / n_progression are per seat)
+
 SEQ_SPARSE, SEQ_PROG, SEQ_CAND, SEQ_DELTA_PROG = 25, 256, 64, 64
 
 # feature sets of the observation batches (RMJ_FEATURES_*, rmj_encode_batch_device)
@@ -236,6 +241,11 @@ FEATURE_CHANNELS = {FEATURES_BASE: 74, FEATURES_DISCARD_SHANTEN: 94, FEATURES_EX
 class ObsBatch(C.Structure):   # RmjObsBatch
     _fields_ = [("features", C.c_int32), ("compact", C.c_int32), ("row_stride", C.c_uint32), ("capacity", C.c_uint32),
                 ("out", C.c_void_p), ("index", C.c_void_p), ("count", C.c_void_p)]
+
+
+class DeviceViews(C.Structure):   # RmjDeviceViews
+    _fields_ = [("n_games", C.c_uint32), ("reserved", C.c_uint32), ("status", C.c_void_p), ("nlegal", C.c_void_p),
+                ("legal", C.c_void_p), ("mask", C.c_void_p), ("waits", C.c_void_p), ("stream", C.c_void_p)]
 
 
 class PpoConfig(C.Structure):   # RmjPpoConfig
@@ -301,6 +311,158 @@ class BenchResult(C.Structure):
     _fields_ = [("total_ms", C.c_double), ("step_kernel_ms", C.c_double), ("env_steps", C.c_uint64),
                 ("launches", C.c_uint32), ("launches_in_flight", C.c_uint32), ("full_path_steps", C.c_uint64),
                 ("queued", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# "RmjX" -> the class that mirrors the header's struct RmjX: every Structure of this module, under the name it has here
+STRUCTS = {"Rmj" + k: v for k, v in list(globals().items()) if isinstance(v, type) and issubclass(v, C.Structure)}
+
+# Every function the two headers declare, in the headers' order: (name, argtypes[, restype when it is not int]).  Handles and
+# raw buffers are c_void_p.  Return codes stay plain ints: vecenv._chk is the one place that raises.
+P, vp, cint, u32, u64, f64 = C.POINTER, C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_double
+PROTOTYPES = [
+    # ======== include/riichi_mi355x.h
+    # ---- lifecycle
+    ("rmj_version", [], C.c_char_p),
+    ("rmj_last_error", [], C.c_char_p),
+    ("rmj_device_count", []),
+    ("rmj_create", [P(Config), P(vp)]),
+    ("rmj_destroy", [vp]),
+    ("rmj_reset", [vp] * 8),
+    ("rmj_clone", [vp, P(vp)]),
+    ("rmj_copy_games", [vp, vp, vp, vp, u32]),
+    ("rmj_copy_games_device", [vp, vp, vp, vp, u32]),
+    ("rmj_step", [vp, vp]),
+    ("rmj_step_device", [vp, vp]),
+    ("rmj_step_random", [vp, u64, u32, cint]),
+    ("rmj_step_greedy", [vp, u64, u32, cint, u32]),
+    ("rmj_random_actions", [vp, u64, vp]),
+    ("rmj_random_actions_device", [vp, u64, vp]),
+    # ---- observations
+    ("rmj_get_status", [vp, vp, vp, vp]),
+    ("rmj_get_legal", [vp, vp, vp]),
+    ("rmj_get_legal_compact", [vp, vp, vp, vp, u32, u32, P(u32), P(u32)]),
+    ("rmj_get_mask", [vp, vp]),
+    ("rmj_get_waits", [vp, vp]),
+    ("rmj_get_scores", [vp, vp]),
+    ("rmj_get_ranks", [vp, vp]),
+    ("rmj_get_step_counts", [vp, vp]),
+    ("rmj_total_steps", [vp, P(u64)]),
+    ("rmj_get_wall_digest", [vp, u32, C.c_char_p, C.c_char_p]),
+    ("rmj_get_wall_digests", [vp, u32, u32, vp, vp]),
+    ("rmj_peek_state", [vp, u32, P(StateView)]),
+    ("rmj_peek_outputs", [vp, u32, vp, vp, vp, vp, P(u32)]),
+    ("rmj_poke_state", [vp, u32, P(StateView)]),
+    ("rmj_get_win_results", [vp, u32, P(WinResult), P(C.c_uint8)]),
+    ("rmj_get_event_counts", [vp, vp]),
+    ("rmj_get_events", [vp, u32, u32, u32, P(Event), P(u32)]),
+    ("rmj_format_event", [P(Event), u32, cint, C.c_char_p, u32]),
+    ("rmj_get_log_positions", [vp, vp, vp]),
+    ("rmj_drain_events", [vp, vp, vp, u32, vp, P(u32), u32]),
+    ("rmj_format_events", [vp, vp, u32, cint, vp, u64, vp, P(u64)]),
+    ("rmj_drain_format", [vp, vp, cint, vp, u64, vp, P(u64), P(u32), vp, u32]),
+    ("rmj_event_views", [vp, P(EventViews)]),
+    ("rmj_get_events_lost", [vp, vp]),
+    ("rmj_drain_text", [vp, vp, cint, u32, P(TextView)]),
+    ("rmj_format_events_device", [vp, vp, vp, u32, cint, u32, P(TextView)]),
+    # ---- batched hand math (kernel gate)
+    ("rmj_eval_hands", [cint, P(HandCase), u32, P(HandResult)]),
+    ("rmj_agari_counts", [cint, vp, u32, vp, vp, vp]),
+    ("rmj_calculate_score", [cint] + [vp] * 6 + [u32, vp]),
+    ("rmj_encode", [vp, cint, vp]),
+    ("rmj_set_encode_row_stride", [vp, u32]),
+    ("rmj_encode_device", [vp, cint, vp]),
+    ("rmj_step_random_encode", [vp, u64, u32, cint, cint, vp]),
+    ("rmj_encode_compact_device", [vp, vp, vp, u32, vp]),
+    ("rmj_step_random_encode_compact", [vp, u64, u32, cint, vp, vp, u32, vp]),
+    ("rmj_encode_extended", [vp, cint, vp]),
+    ("rmj_encode_extended_device", [vp, cint, vp]),
+    ("rmj_encode_batch_device", [vp, P(ObsBatch)]),
+    ("rmj_encode_batch", [vp, P(ObsBatch)]),
+    ("rmj_step_ids_encode_batch_device", [vp, vp, cint, P(ObsBatch)]),
+    ("rmj_step_sample_encode_batch_device", [vp, vp, u32, u64, cint, vp, P(ObsBatch)]),
+    ("rmj_shanten", [cint, vp, u32, cint, vp]),
+    ("rmj_effective_tiles", [cint, vp, u32, cint, vp]),
+    ("rmj_best_ukeire", [cint, vp, vp, u32, cint, vp]),
+    # ---- trainer-side device interface
+    ("rmj_device_views", [vp, P(DeviceViews)]),
+    ("rmj_step_ids_device", [vp, vp, cint]),
+    ("rmj_step_ids_encode_device", [vp, vp, cint, vp]),
+    ("rmj_step_sample_encode_device", [vp, vp, u32, u64, cint, vp, vp]),
+    ("rmj_sample_ids_device", [vp, vp, u32, u64, vp]),
+    ("rmj_select_ids_device", [vp, vp, u32, u64, vp, vp]),
+    # ---- PPO transition collector
+    ("rmj_ppo_create", [vp, P(PpoConfig), P(vp)]),
+    ("rmj_ppo_destroy", [vp]),
+    ("rmj_ppo_record_device", [vp, P(ObsBatch), vp, vp, vp, u32, vp]),
+    ("rmj_ppo_close_device", [vp, vp, vp]),
+    ("rmj_ppo_emit_device", [vp, P(PpoBatch)]),
+    ("rmj_ppo_views", [vp, P(PpoViews)]),
+    ("rmj_ppo_counts", [vp, P(PpoCounts)]),
+    ("rmj_ppo_clear", [vp]),
+    # ---- log sample builder
+    ("rmj_logset_create", [cint, vp, vp, u32, P(vp)]),
+    ("rmj_logset_destroy", [vp]),
+    ("rmj_logset_info", [vp, P(LogsetInfo), vp]),
+    ("rmj_logset_create_from_text", [cint, vp, vp, u32, u32, u32, P(vp)]),
+    ("rmj_logset_views", [vp, P(LogsetViews)]),
+    ("rmj_logset_status", [vp, vp, vp, vp, vp]),
+    ("rmj_grp_rows_device", [cint, vp, vp, vp, u32, u32, vp, vp]),
+    ("rmj_logset_grp_device", [vp, u32, vp, vp, P(GrpOut), vp]),
+    ("rmj_logreplay_assign", [vp, u32, u32, vp, vp, vp, P(u32)]),
+    ("rmj_logreplay_create", [vp, vp, P(LogReplayConfig), P(vp)]),
+    ("rmj_logreplay_destroy", [vp]),
+    ("rmj_logreplay_run_device", [vp, u32, P(u32)]),
+    ("rmj_logreplay_finalize_device", [vp, vp, vp]),
+    ("rmj_logreplay_emit_device", [vp, P(LogBatch)]),
+    ("rmj_logreplay_views", [vp, P(LogReplayViews)]),
+    ("rmj_logreplay_counts", [vp, P(LogReplayCounts)]),
+    ("rmj_logreplay_clear", [vp]),
+    ("rmj_round_track_device", [vp, vp, vp, vp, vp]),
+    ("rmj_round_track_reset", [vp]),
+    ("rmj_scores_device", [vp, vp, vp]),
+    ("rmj_points_device", [vp, cint, vp]),
+    ("rmj_get_points", [vp, cint, vp]),
+    ("rmj_sync", [vp]),
+    ("rmj_set_stream", [vp, vp, cint]),
+    # ---- MJAI event ingestion
+    ("rmj_apply_events", [vp, vp]),
+    ("rmj_encode_aux", [vp, cint, vp]),
+    ("rmj_encode_aux_device", [vp, cint, vp]),
+    ("rmj_encode_seq_delta", [vp, cint, P(SeqDeltaBuffers)]),
+    ("rmj_encode_seq_delta_device", [vp, cint, P(SeqDeltaBuffers)]),
+    ("rmj_encode_seq", [vp, cint, P(SeqBuffers)]),
+    ("rmj_encode_seq_device", [vp, cint, P(SeqBuffers)]),
+    # ---- scheduling
+    ("rmj_set_rollout_streams", [vp, cint]),
+    # ======== include/riichi_mi355x_bench.h
+    ("rmj_bench_rollout", [vp, u64, u32, u32, P(BenchResult)]),
+    ("rmj_time_rollout", [vp, u64, u32, P(BenchResult)]),
+    ("rmj_time_rollout_encode", [vp, u64, u32, vp, P(BenchResult)]),
+    ("rmj_time_rollout_greedy", [vp, u64, u32, u32, P(BenchResult)]),
+    ("rmj_bench_rollout_validated", [vp, u64, u32, u32, P(BenchResult)]),
+    ("rmj_bench_hand_kernel", [cint, cint, vp, vp, u32, cint, u32, P(f64)]),
+    ("rmj_bench_encode", [vp, cint, cint, vp, u32, P(f64)]),
+    ("rmj_bench_encode_compact", [vp, vp, vp, u32, vp, u32, P(f64)]),
+    ("rmj_bench_device_alloc", [cint, u64, P(vp)]),
+    ("rmj_bench_device_free", [cint, vp]),
+    ("rmj_bench_device_sync", [cint]),
+    ("rmj_total_full_path", [vp, P(u64)]),
+]
+
+
+class _CudaArray:
+    """Minimal __cuda_array_interface__ carrier so that torch.as_tensor wraps library-owned device memory in place."""
+
+    def __init__(self, ptr, shape, typestr, owner):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 3,
+                                         "strides": None}
+        self._owner = owner   # keeps the owning object (and with it the allocation) alive
+
+
+def device_tensor(torch, owner, device, ptr, shape, typestr):
+    """A zero-copy torch tensor over library-owned device memory at `ptr`; the tensor keeps `owner` alive.  (torch is passed in: this
+    module imports none; functools.partial over the first three arguments gives a view struct's wrapper.)"""
+    return torch.as_tensor(_CudaArray(ptr, shape, typestr, owner), device=device)
 
 
 def hand_case_from_fixture(case: dict) -> HandCase:

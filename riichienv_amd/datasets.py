@@ -26,6 +26,7 @@ replay raises in MCDataset."""
 from __future__ import annotations
 
 import ctypes as C
+import functools
 
 import numpy as np
 
@@ -160,8 +161,6 @@ class LogSampleBuilder:
 
     def _attach(self, logset, owned):
         """the environment, the replay and the pool views over the log set; `owned`: close() closes the set too"""
-        from .torch_env import _CudaArray
-
         self.logset, self._owned = logset, owned
         try:
             assert self.n_players == logset.num_players, "the log set was made for another number of players"
@@ -186,7 +185,7 @@ class LogSampleBuilder:
             v = abi.LogReplayViews()
             vecenv._chk(L.rmj_logreplay_views(self.h, C.byref(v)))
             self.steps = int(v.steps)
-            wrap = lambda ptr, shape, ts: torch.as_tensor(_CudaArray(ptr, shape, ts, self), device=self.device)  # noqa: E731
+            wrap = functools.partial(abi.device_tensor, torch, self, self.device)
             cap, fl, K = self.capacity, self.channels * self.width, max(self.n_kyokus, 1)
             rows = wrap(v.features, (cap, v.row_stride), "<f4")
             self.pool = {"features": rows[:, :fl].unflatten(-1, (self.channels, self.width)), "mask": wrap(v.mask, (cap, self.A), "|u1"),

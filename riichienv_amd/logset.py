@@ -268,9 +268,7 @@ class LogSet:
         return v
 
     def _wrap(self, ptr, shape, typestr):
-        from .torch_env import _CudaArray
-
-        return self.torch.as_tensor(_CudaArray(ptr, shape, typestr, self), device=self.device)
+        return abi.device_tensor(self.torch, self, self.device, ptr, shape, typestr)
 
     def device_scores(self):
         """(start, end) int32 [K, 4] device tensors: views into a set that owns its tables (None for a set packed from dicts)"""
@@ -285,7 +283,9 @@ class LogSet:
         offsets / kyoku_offsets [M + 1] int64, start_scores / end_scores [K, 4] int32, status [M] uint8 (abi.LOGTEXT_*), error_line /
         decisions [M] int64."""
         t, dev, m, n, k, v = self.torch, self.device, self.M, self.n_events, self.n_kyokus, self._views()
-        get = lambda ptr, shape, ts: self._wrap(ptr, shape, ts).clone() if ptr and int(np.prod(shape)) else t.zeros(shape, dtype=t.uint8, device=dev)  # noqa: E731
+
+        def get(ptr, shape, ts):
+            return self._wrap(ptr, shape, ts).clone() if ptr and int(np.prod(shape)) else t.zeros(shape, dtype=t.uint8, device=dev)
         out = {"events": get(v.events, (n, 3, 32), "|u1"), "offsets": get(v.offsets, (m + 1,), "<i4").to(t.int64),
                "kyoku_offsets": get(v.kyoku_offsets, (m + 1,), "<i4").to(t.int64), "start_scores": get(v.start_scores, (k, 4), "<i4").to(t.int32),
                "end_scores": get(v.end_scores, (k, 4), "<i4").to(t.int32), "status": get(v.status, (m,), "|u1"),

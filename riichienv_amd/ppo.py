@@ -11,9 +11,9 @@ not fit is counted (`counts()["overflowed"]`), and a trajectory that lost a tran
 from __future__ import annotations
 
 import ctypes as C
+import functools
 
 from . import abi, vecenv
-from .torch_env import _CudaArray
 
 NO_HERO = 255   # hero value of a game in which every seat takes the arg-max and nothing is recorded (evaluate_episodes)
 
@@ -54,7 +54,7 @@ class PPOCollector:
         vecenv._chk(L.rmj_ppo_create(tenv.env.h, C.byref(cfg), C.byref(self.h)))
         v = abi.PpoViews()
         vecenv._chk(L.rmj_ppo_views(self.h, C.byref(v)))
-        wrap = lambda ptr, shape, ts: t.as_tensor(_CudaArray(ptr, shape, ts, self), device=dev)  # noqa: E731
+        wrap = functools.partial(abi.device_tensor, t, self, dev)
         cap, fl = self.capacity, tenv.channels * tenv.width
         self._pool_rows = wrap(v.features, (cap, v.row_stride), "<f4")
         self.pool = {"features": self._pool_rows[:, :fl].unflatten(-1, (tenv.channels, tenv.width)), "mask": wrap(v.mask, (cap, self.A), "|u1"),

@@ -9,24 +9,12 @@ torch is used for device memory and streams only; all game logic runs in the HIP
 from __future__ import annotations
 
 import ctypes as C
+import functools
 
 import numpy as np
 
 from . import abi, vecenv
-
-
-class DeviceViews(C.Structure):
-    _fields_ = [("n_games", C.c_uint32), ("reserved", C.c_uint32), ("status", C.c_void_p), ("nlegal", C.c_void_p),
-                ("legal", C.c_void_p), ("mask", C.c_void_p), ("waits", C.c_void_p), ("stream", C.c_void_p)]
-
-
-class _CudaArray:
-    """Minimal __cuda_array_interface__ carrier so that torch.as_tensor wraps library-owned device memory in place."""
-
-    def __init__(self, ptr, shape, typestr, owner):
-        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 3,
-                                         "strides": None}
-        self._owner = owner   # keeps the environment (and with it the allocation) alive
+from .abi import _CudaArray  # noqa: F401  (imported from here by tests and scripts)
 
 
 class TorchVecEnv:
@@ -59,10 +47,6 @@ class TorchVecEnv:
         self.env = vecenv.VecRiichiEnv(n_games, game_mode=game_mode, seed=seed, device=device,
                                        skip_mjai_logging=skip_mjai_logging, **kw)
         L = self.env.L
-        L.rmj_device_views.argtypes = [C.c_void_p, C.POINTER(DeviceViews)]
-        L.rmj_step_ids_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-        L.rmj_scores_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.rmj_sync.argtypes = [C.c_void_p]
         self.n = int(n_games)
         self.sanma = self.env.game_mode >= 3
         self.features = features
@@ -70,9 +54,9 @@ class TorchVecEnv:
         self.extended = features == "extended"
         self.channels = abi.FEATURE_CHANNELS[self._feat]
         self.width = 27 if self.sanma else 34
-        v = DeviceViews()
+        v = abi.DeviceViews()
         vecenv._chk(L.rmj_device_views(self.env.h, C.byref(v)))
-        wrap = lambda ptr, shape, ts: torch.as_tensor(_CudaArray(ptr, shape, ts, self), device=self.device)  # noqa: E731
+        wrap = functools.partial(abi.device_tensor, torch, self, self.device)
         self.status_raw = wrap(v.status, (self.n,), "<u4") if hasattr(torch, "uint32") else wrap(v.status, (self.n,), "<i4")
         self.nlegal = wrap(v.nlegal, (self.n, 4), "|u1")
         self.mask = wrap(v.mask, (self.n, 4, abi.ACTION_SPACE_4P), "|u1")      # zero-copy, rewritten by every step
@@ -361,7 +345,7 @@ class TorchVecEnv:
         v = self.env._text_call(seat, cursor, peek, True)
         if timings is not None:
             timings[:] = [v.ms[0], v.ms[1], v.ms[2]]
-        wrap = lambda ptr, shape, ts: self.torch.as_tensor(_CudaArray(ptr, shape, ts, self), device=self.device)  # noqa: E731
+        wrap = functools.partial(abi.device_tensor, self.torch, self, self.device)
         text = wrap(v.text, (int(v.bytes),), "|u1") if v.bytes else self.torch.zeros(0, dtype=self.torch.uint8, device=self.device)
         return text, wrap(v.text_offsets, (v.n_games + 1,), "<i8")
 

@@ -20,30 +20,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RMJ_LIB_PATH") or os.path.join(_HERE, "libriichi_mi355x.so")   # (the variable: experiment builds)
 _LIB = None
 
-# every symbol include/riichi_mi355x.h declares
-EXPORTS = [
-    "rmj_version", "rmj_last_error", "rmj_device_count", "rmj_create", "rmj_destroy", "rmj_reset", "rmj_step",
-    "rmj_step_device", "rmj_step_random", "rmj_random_actions", "rmj_get_status", "rmj_get_legal", "rmj_get_mask",
-    "rmj_get_waits", "rmj_get_scores", "rmj_get_ranks", "rmj_get_step_counts", "rmj_total_steps", "rmj_peek_state",
-    "rmj_poke_state", "rmj_get_event_counts", "rmj_get_events", "rmj_format_event", "rmj_eval_hands",
-    "rmj_agari_counts", "rmj_calculate_score", "rmj_shanten", "rmj_effective_tiles", "rmj_best_ukeire", "rmj_apply_events", "rmj_device_views", "rmj_step_ids_device", "rmj_clone", "rmj_copy_games", "rmj_copy_games_device",
-    "rmj_scores_device", "rmj_sync", "rmj_set_stream", "rmj_encode", "rmj_encode_device", "rmj_encode_extended", "rmj_encode_extended_device", "rmj_encode_aux", "rmj_encode_aux_device", "rmj_encode_seq", "rmj_encode_seq_device", "rmj_bench_rollout", "rmj_time_rollout", "rmj_step_greedy", "rmj_time_rollout_greedy", "rmj_time_rollout_encode", "rmj_step_ids_encode_device", "rmj_step_sample_encode_device", "rmj_set_encode_row_stride", "rmj_bench_hand_kernel", "rmj_points_device", "rmj_get_points", "rmj_get_legal_compact", "rmj_get_wall_digest", "rmj_get_wall_digests",
-    "rmj_bench_rollout_validated", "rmj_bench_encode", "rmj_set_rollout_streams", "rmj_total_full_path", "rmj_bench_device_alloc", "rmj_bench_device_free", "rmj_bench_device_sync",
-    "rmj_random_actions_device", "rmj_peek_outputs", "rmj_sample_ids_device",
-    "rmj_encode_seq_delta", "rmj_encode_seq_delta_device", "rmj_step_random_encode",
-    "rmj_encode_compact_device", "rmj_step_random_encode_compact", "rmj_bench_encode_compact",
-    "rmj_get_win_results",
-    "rmj_drain_events", "rmj_format_events", "rmj_drain_format", "rmj_event_views", "rmj_round_track_device", "rmj_round_track_reset", "rmj_get_events_lost", "rmj_get_log_positions",
-    "rmj_drain_text", "rmj_format_events_device",
-    "rmj_encode_batch_device", "rmj_encode_batch", "rmj_step_ids_encode_batch_device", "rmj_step_sample_encode_batch_device",
-    "rmj_select_ids_device", "rmj_ppo_create", "rmj_ppo_destroy", "rmj_ppo_record_device", "rmj_ppo_close_device", "rmj_ppo_emit_device",
-    "rmj_ppo_views", "rmj_ppo_counts", "rmj_ppo_clear",
-    "rmj_logset_create", "rmj_logset_destroy", "rmj_logset_info", "rmj_logreplay_assign", "rmj_logreplay_create", "rmj_logreplay_destroy",
-    "rmj_logreplay_run_device", "rmj_logreplay_finalize_device", "rmj_logreplay_emit_device", "rmj_logreplay_views", "rmj_logreplay_counts",
-    "rmj_logreplay_clear",
-    "rmj_logset_create_from_text", "rmj_logset_views", "rmj_logset_status",
-    "rmj_grp_rows_device", "rmj_logset_grp_device",
-]
+# every symbol include/riichi_mi355x.h and include/riichi_mi355x_bench.h declare
+EXPORTS = [row[0] for row in abi.PROTOTYPES]
 
 
 class RmjError(RuntimeError):
@@ -84,119 +62,11 @@ def load_lib():
                        "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     _share_torch_hip_runtime()
     L = C.CDLL(LIB_PATH)
-    L.rmj_version.restype = C.c_char_p
-    L.rmj_last_error.restype = C.c_char_p
-    vp = C.c_void_p
-    L.rmj_create.argtypes = [C.POINTER(abi.Config), C.POINTER(vp)]
-    L.rmj_destroy.argtypes = [vp]
-    L.rmj_get_wall_digest.argtypes = [vp, C.c_uint32, C.c_char_p, C.c_char_p]
-    L.rmj_get_wall_digests.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp]
-    L.rmj_reset.argtypes = [vp] * 8
-    L.rmj_step.argtypes = [vp, vp]
-    L.rmj_clone.argtypes = [vp, C.POINTER(vp)]
-    L.rmj_copy_games.argtypes = [vp, vp, vp, vp, C.c_uint32]
-    L.rmj_copy_games_device.argtypes = [vp, vp, vp, vp, C.c_uint32]
-    L.rmj_step_device.argtypes = [vp, vp]
-    L.rmj_step_random.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_int]
-    L.rmj_random_actions.argtypes = [vp, C.c_uint64, vp]
-    L.rmj_get_status.argtypes = [vp, vp, vp, vp]
-    L.rmj_get_legal.argtypes = [vp, vp, vp]
-    L.rmj_get_mask.argtypes = [vp, vp]
-    L.rmj_get_waits.argtypes = [vp, vp]
-    L.rmj_get_scores.argtypes = [vp, vp]
-    L.rmj_get_ranks.argtypes = [vp, vp]
-    L.rmj_get_step_counts.argtypes = [vp, vp]
-    L.rmj_total_steps.argtypes = [vp, C.POINTER(C.c_uint64)]
-    L.rmj_peek_state.argtypes = [vp, C.c_uint32, C.POINTER(abi.StateView)]
-    L.rmj_poke_state.argtypes = [vp, C.c_uint32, C.POINTER(abi.StateView)]
-    L.rmj_get_event_counts.argtypes = [vp, vp]
-    L.rmj_get_events.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(abi.Event), C.POINTER(C.c_uint32)]
-    L.rmj_format_event.argtypes = [C.POINTER(abi.Event), C.c_uint32, C.c_int, C.c_char_p, C.c_uint32]
-    L.rmj_eval_hands.argtypes = [C.c_int, C.POINTER(abi.HandCase), C.c_uint32, C.POINTER(abi.HandResult)]
-    L.rmj_agari_counts.argtypes = [C.c_int, vp, C.c_uint32, vp, vp, vp]
-    L.rmj_calculate_score.argtypes = [C.c_int] + [vp] * 6 + [C.c_uint32, vp]
-    L.rmj_encode.argtypes = [vp, C.c_int, vp]
-    L.rmj_encode_device.argtypes = [vp, C.c_int, vp]
-    L.rmj_encode_extended.argtypes = [vp, C.c_int, vp]
-    L.rmj_encode_extended_device.argtypes = [vp, C.c_int, vp]
-    L.rmj_set_stream.argtypes = [vp, vp, C.c_int]
-    L.rmj_encode_aux.argtypes = [vp, C.c_int, vp]
-    L.rmj_encode_aux_device.argtypes = [vp, C.c_int, vp]
-    L.rmj_encode_seq.argtypes = [vp, C.c_int, C.POINTER(abi.SeqBuffers)]
-    L.rmj_encode_seq_device.argtypes = [vp, C.c_int, C.POINTER(abi.SeqBuffers)]
-    L.rmj_effective_tiles.argtypes = [C.c_int, vp, C.c_uint32, C.c_int, vp]
-    L.rmj_best_ukeire.argtypes = [C.c_int, vp, vp, C.c_uint32, C.c_int, vp]
-    L.rmj_apply_events.argtypes = [vp, vp]
-    L.rmj_shanten.argtypes = [C.c_int, vp, C.c_uint32, C.c_int, vp]
-    L.rmj_bench_rollout.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(abi.BenchResult)]
-    L.rmj_bench_rollout_validated.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(abi.BenchResult)]
-    L.rmj_time_rollout.argtypes = [vp, C.c_uint64, C.c_uint32, C.POINTER(abi.BenchResult)]
-    L.rmj_step_greedy.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_int, C.c_uint32]
-    L.rmj_get_legal_compact.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-    L.rmj_points_device.argtypes = [vp, C.c_int, vp]
-    L.rmj_get_points.argtypes = [vp, C.c_int, vp]
-    L.rmj_bench_hand_kernel.argtypes = [C.c_int, C.c_int, vp, vp, C.c_uint32, C.c_int, C.c_uint32, C.POINTER(C.c_double)]
-    L.rmj_set_encode_row_stride.argtypes = [vp, C.c_uint32]
-    L.rmj_step_ids_encode_device.argtypes = [vp, vp, C.c_int, vp]
-    L.rmj_step_sample_encode_device.argtypes = [vp, vp, C.c_uint32, C.c_uint64, C.c_int, vp, vp]
-    L.rmj_time_rollout_encode.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.POINTER(abi.BenchResult)]
-    L.rmj_time_rollout_greedy.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(abi.BenchResult)]
-    L.rmj_bench_encode.argtypes = [vp, C.c_int, C.c_int, vp, C.c_uint32, C.POINTER(C.c_double)]
-    L.rmj_set_rollout_streams.argtypes = [vp, C.c_int]
-    L.rmj_total_full_path.argtypes = [vp, C.POINTER(C.c_uint64)]
-    L.rmj_bench_device_alloc.argtypes = [C.c_int, C.c_uint64, C.POINTER(vp)]
-    L.rmj_bench_device_free.argtypes = [C.c_int, vp]
-    L.rmj_bench_device_sync.argtypes = [C.c_int]
-    L.rmj_random_actions_device.argtypes = [vp, C.c_uint64, vp]
-    L.rmj_peek_outputs.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, C.POINTER(C.c_uint32)]
-    L.rmj_sample_ids_device.argtypes = [vp, vp, C.c_uint32, C.c_uint64, vp]
-    L.rmj_step_random_encode.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_int, C.c_int, vp]
-    L.rmj_encode_compact_device.argtypes = [vp, vp, vp, C.c_uint32, vp]
-    L.rmj_step_random_encode_compact.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_int, vp, vp, C.c_uint32, vp]
-    L.rmj_bench_encode_compact.argtypes = [vp, vp, vp, C.c_uint32, vp, C.c_uint32, C.POINTER(C.c_double)]
-    L.rmj_get_win_results.argtypes = [vp, C.c_uint32, C.POINTER(abi.WinResult), C.POINTER(C.c_uint8)]
-    L.rmj_encode_seq_delta.argtypes = [vp, C.c_int, C.POINTER(abi.SeqBuffers)]          # same field layout as RmjSeqBuffers
-    L.rmj_encode_seq_delta_device.argtypes = [vp, C.c_int, C.POINTER(abi.SeqBuffers)]
-    L.rmj_drain_events.argtypes = [vp, vp, vp, C.c_uint32, vp, C.POINTER(C.c_uint32), C.c_uint32]
-    L.rmj_get_log_positions.argtypes = [vp, vp, vp]
-    L.rmj_format_events.argtypes = [vp, vp, C.c_uint32, C.c_int, vp, C.c_uint64, vp, C.POINTER(C.c_uint64)]
-    L.rmj_drain_format.argtypes = [vp, vp, C.c_int, vp, C.c_uint64, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), vp, C.c_uint32]
-    L.rmj_event_views.argtypes = [vp, C.POINTER(abi.EventViews)]
-    L.rmj_get_events_lost.argtypes = [vp, vp]
-    L.rmj_round_track_device.argtypes = [vp, vp, vp, vp, vp]
-    L.rmj_round_track_reset.argtypes = [vp]
-    L.rmj_drain_text.argtypes = [vp, vp, C.c_int, C.c_uint32, C.POINTER(abi.TextView)]
-    L.rmj_format_events_device.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, C.c_uint32, C.POINTER(abi.TextView)]
-    L.rmj_encode_batch_device.argtypes = [vp, C.POINTER(abi.ObsBatch)]
-    L.rmj_encode_batch.argtypes = [vp, C.POINTER(abi.ObsBatch)]
-    L.rmj_step_ids_encode_batch_device.argtypes = [vp, vp, C.c_int, C.POINTER(abi.ObsBatch)]
-    L.rmj_step_sample_encode_batch_device.argtypes = [vp, vp, C.c_uint32, C.c_uint64, C.c_int, vp, C.POINTER(abi.ObsBatch)]
-    L.rmj_select_ids_device.argtypes = [vp, vp, C.c_uint32, C.c_uint64, vp, vp]
-    L.rmj_ppo_create.argtypes = [vp, C.POINTER(abi.PpoConfig), C.POINTER(vp)]
-    L.rmj_ppo_destroy.argtypes = [vp]
-    L.rmj_ppo_record_device.argtypes = [vp, C.POINTER(abi.ObsBatch), vp, vp, vp, C.c_uint32, vp]
-    L.rmj_ppo_close_device.argtypes = [vp, vp, vp]
-    L.rmj_ppo_emit_device.argtypes = [vp, C.POINTER(abi.PpoBatch)]
-    L.rmj_ppo_views.argtypes = [vp, C.POINTER(abi.PpoViews)]
-    L.rmj_ppo_counts.argtypes = [vp, C.POINTER(abi.PpoCounts)]
-    L.rmj_ppo_clear.argtypes = [vp]
-    L.rmj_logset_create.argtypes = [C.c_int, vp, vp, C.c_uint32, C.POINTER(vp)]
-    L.rmj_logset_destroy.argtypes = [vp]
-    L.rmj_logset_create_from_text.argtypes = [C.c_int, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(vp)]
-    L.rmj_logset_views.argtypes = [vp, C.POINTER(abi.LogsetViews)]
-    L.rmj_logset_status.argtypes = [vp, vp, vp, vp, vp]
-    L.rmj_logset_info.argtypes = [vp, C.POINTER(abi.LogsetInfo), vp]
-    L.rmj_logreplay_assign.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.POINTER(C.c_uint32)]
-    L.rmj_logreplay_create.argtypes = [vp, vp, C.POINTER(abi.LogReplayConfig), C.POINTER(vp)]
-    L.rmj_logreplay_destroy.argtypes = [vp]
-    L.rmj_logreplay_run_device.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32)]
-    L.rmj_logreplay_finalize_device.argtypes = [vp, vp, vp]
-    L.rmj_logreplay_emit_device.argtypes = [vp, C.POINTER(abi.LogBatch)]
-    L.rmj_logreplay_views.argtypes = [vp, C.POINTER(abi.LogReplayViews)]
-    L.rmj_logreplay_counts.argtypes = [vp, C.POINTER(abi.LogReplayCounts)]
-    L.rmj_logreplay_clear.argtypes = [vp]
-    L.rmj_grp_rows_device.argtypes = [C.c_int, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp]
-    L.rmj_logset_grp_device.argtypes = [vp, C.c_uint32, vp, vp, C.POINTER(abi.GrpOut), vp]
+    for name, argtypes, *restype in abi.PROTOTYPES:
+        fn = getattr(L, name)
+        fn.argtypes = argtypes
+        if restype:
+            fn.restype = restype[0]
     _LIB = L
     return L
 

@@ -102,9 +102,6 @@ def test_alternating_halves_driver_equals_the_whole_batch(mode):
     n, k = 4096, 120
     whole = [vecenv.VecRiichiEnv(n, game_mode=mode, seed=3, event_ring=64)]
     halves = [vecenv.VecRiichiEnv(n // 2, game_mode=mode, seed=3, game_offset=i * (n // 2), event_ring=64) for i in range(2)]
-    L = whole[0].L
-    L.rmj_sample_ids_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]
-    L.rmj_step_ids_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     for e in whole + halves:
         e.reset()
     ids_w = [torch.full((n, 4), -1, dtype=torch.int32, device="cuda:0")]
