@@ -688,6 +688,38 @@ typedef struct RmjGrpOut {
 } RmjGrpOut;
 int rmj_logset_grp_device(rmj_logset_handle s, uint32_t num_players, const int32_t* d_start_scores, const int32_t* d_end_scores, const RmjGrpOut* out,
                           void* hip_stream);
+/* Play statistics: how every seat played every kyoku of a log set - int32 rows[n_kyokus][4][RMJ_PLAYSTAT_COLUMNS], one row block per
+ * kyoku in table order kyoku_offsets[log] + kyoku - 1.  A kyoku runs from its START_KYOKU record up to the next START_KYOKU of the same
+ * log, or to the log's end; events before a log's first START_KYOKU belong to no row.  Only type, actor and flags of an event's first
+ * record are read (and the oya of a START_KYOKU); an event whose actor >= num_players is skipped as if its type were NONE.
+ * Hora records carry no target, so who dealt in is derived from the stream.  A tile event is a TSUMO, DAHAI, KAKAN, ANKAN or KITA; for a
+ * HORA of seat a, with L the last tile event before it in the same kyoku: L a TSUMO by a - a tsumo win; else L by a seat x != a - x dealt
+ * in (ron, chankan, kokushi on an ankan); else (no L, or another tile event of a's own) - a win only.
+ * Columns of seat p: */
+#define RMJ_PLAYSTAT_COLUMNS 16
+#define RMJ_PLAYSTAT_WIN 0              /* HORA events of p */
+#define RMJ_PLAYSTAT_WIN_TSUMO 1        /* those that are tsumo wins */
+#define RMJ_PLAYSTAT_DEAL_IN 2          /* HORA events of other seats into which p dealt (a double ron counts 2) */
+#define RMJ_PLAYSTAT_RIICHI 3           /* REACH events of p */
+#define RMJ_PLAYSTAT_RIICHI_ACCEPTED 4  /* REACH_ACCEPTED events of p */
+#define RMJ_PLAYSTAT_RIICHI_TURN 5      /* 1 + the DAHAI events of p before its first REACH of the kyoku; 0 without one */
+#define RMJ_PLAYSTAT_CALLS 6            /* CHI + PON + DAIMINKAN of p */
+#define RMJ_PLAYSTAT_CHI 7
+#define RMJ_PLAYSTAT_PON 8
+#define RMJ_PLAYSTAT_KANS 9             /* DAIMINKAN + ANKAN + KAKAN of p */
+#define RMJ_PLAYSTAT_KITA 10
+#define RMJ_PLAYSTAT_DISCARDS 11        /* DAHAI events of p */
+#define RMJ_PLAYSTAT_TSUMOGIRI 12       /* of those, the ones with flags bit 0 */
+#define RMJ_PLAYSTAT_WIN_TURN 13        /* the DAHAI events of p before its first HORA of the kyoku; 0 without one */
+#define RMJ_PLAYSTAT_DEALER 14          /* 1 if the kyoku's oya is p */
+#define RMJ_PLAYSTAT_END 15             /* the same in every seat < num_players: bit 0 a HORA occurred, bit 1 a RYUKYOKU occurred */
+/* Seats >= num_players are all zero (END included).  Every kyoku row of a log whose status is not RMJ_LOGTEXT_OK holds -1 in all 64
+ * words, so a sum that forgot to mask those rows is visibly wrong.  Every word of the table is written exactly once per call: the
+ * caller does not clear it.  Asynchronous on `hip_stream` (NULL = the null stream), allocates nothing, waits for nothing; works on both
+ * kinds of set and needs no score tables.  RMJ_ERR_ARG for a null set and for num_players other than 3 or 4.  A set without kyokus then
+ * returns RMJ_OK without a launch and without looking at d_rows (an empty table may have a null pointer).  Otherwise RMJ_ERR_ARG for
+ * null rows and for rows that are not 16-byte aligned. */
+int rmj_logset_playstats_device(rmj_logset_handle s, uint32_t num_players, int32_t* d_rows /*[n_kyokus][4][16]*/, void* hip_stream);
 /* Which slot replays which logs (host only, no device needed): the logs are handed out in log order, each to the slot that is free
  * first when every event takes one step, ties to the lowest slot - a pure function of (n_logs, n_slots, the logs' lengths), so the
  * order of the samples is the same run after run.  slot_of_log [n_logs]; slot s replays slot_logs[slot_first[s] .. slot_first[s + 1])

@@ -7,7 +7,8 @@ HandEvaluator3P, Wind, WinResult, Score, calculate_score, calculate_shanten, cal
 parse_hand, parse_tile (riichienv_amd.hand); MjaiReplay, MjSoulReplay, Kyoku, WinResultContext (riichienv_amd.replay); Yaku, get_yaku_by_id, get_all_yaku
 (riichienv_amd.yaku_table); the
 `convert` and `consts` modules.  PPOCollector (riichienv_amd.ppo), LogSet (riichienv_amd.logset), LogSampleBuilder
-(riichienv_amd.datasets) and grp_rows, GrpDataset, DeviceRewardPredictor (riichienv_amd.grp) are the device-side training feeds.
+(riichienv_amd.datasets) and grp_rows, GrpDataset, DeviceRewardPredictor (riichienv_amd.grp) are the device-side training feeds;
+play_stats and summarize (riichienv_amd.stats) tell from the same log sets how the agents played.
 """
 from .vecenv import VecRiichiEnv, RmjError, load_lib  # noqa: F401
 
@@ -21,6 +22,7 @@ _LAZY = {
     "logset": ("LogSet",),
     "datasets": ("LogSampleBuilder",),
     "grp": ("grp_rows", "GrpDataset", "DeviceRewardPredictor"),
+    "stats": ("play_stats", "summarize"),
 }
 __all__ = ["VecRiichiEnv", "RmjError", "load_lib", "convert", "consts"] + [n for names in _LAZY.values() for n in names]
 

@@ -307,6 +307,15 @@ class GrpOut(C.Structure):           # RmjGrpOut (rmj_logset_grp_device): device
     _fields_ = [(k, C.c_void_p) for k in ("meta", "x", "rank", "log_of")]
 
 
+# RMJ_PLAYSTAT_*: the columns of rmj_logset_playstats_device's rows [n_kyokus][4][PLAYSTAT_COLUMNS] int32
+PLAYSTAT_NAMES = ["WIN", "WIN_TSUMO", "DEAL_IN", "RIICHI", "RIICHI_ACCEPTED", "RIICHI_TURN", "CALLS", "CHI", "PON", "KANS", "KITA", "DISCARDS",
+                  "TSUMOGIRI", "WIN_TURN", "DEALER", "END"]
+PLAYSTAT_COLUMNS = len(PLAYSTAT_NAMES)
+PLAYSTAT_WIN, PLAYSTAT_WIN_TSUMO, PLAYSTAT_DEAL_IN, PLAYSTAT_RIICHI, PLAYSTAT_RIICHI_ACCEPTED, PLAYSTAT_RIICHI_TURN, PLAYSTAT_CALLS, PLAYSTAT_CHI, \
+    PLAYSTAT_PON, PLAYSTAT_KANS, PLAYSTAT_KITA, PLAYSTAT_DISCARDS, PLAYSTAT_TSUMOGIRI, PLAYSTAT_WIN_TURN, PLAYSTAT_DEALER, PLAYSTAT_END = range(16)
+PLAYSTAT_END_HORA, PLAYSTAT_END_RYUKYOKU = 1, 2   # the bits of the END column
+
+
 class BenchResult(C.Structure):
     _fields_ = [("total_ms", C.c_double), ("step_kernel_ms", C.c_double), ("env_steps", C.c_uint64),
                 ("launches", C.c_uint32), ("launches_in_flight", C.c_uint32), ("full_path_steps", C.c_uint64),
@@ -408,6 +417,7 @@ PROTOTYPES = [
     ("rmj_logset_status", [vp, vp, vp, vp, vp]),
     ("rmj_grp_rows_device", [cint, vp, vp, vp, u32, u32, vp, vp]),
     ("rmj_logset_grp_device", [vp, u32, vp, vp, P(GrpOut), vp]),
+    ("rmj_logset_playstats_device", [vp, u32, vp, vp]),
     ("rmj_logreplay_assign", [vp, u32, u32, vp, vp, vp, P(u32)]),
     ("rmj_logreplay_create", [vp, vp, P(LogReplayConfig), P(vp)]),
     ("rmj_logreplay_destroy", [vp]),

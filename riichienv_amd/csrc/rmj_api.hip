@@ -49,6 +49,7 @@ using namespace rmj;
 #include "rmj_logreplay.hip.h"
 #include "rmj_logtext.hip.h"
 #include "rmj_grp.hip.h"
+#include "rmj_playstats.hip.h"
 #include "rmj_handtab.hip.h"
 #include "rmj_events.hip.h"
 
@@ -2275,6 +2276,20 @@ int rmj_logset_grp_device(rmj_logset_handle s, uint32_t num_players, const int32
                        (const uint32_t*)s->d_koff, s->M, (const uint8_t*)s->d_status, en, num_players, out->meta, out->rank, out->log_of);
     if (out->x)
         hipLaunchKernelGGL(k_grp_rows<true>, grp_rows_grid(s->K, num_players), dim3(GRP_BLOCK), 0, stream, st, en, (const int32_t*)out->meta, s->K, num_players, out->x);
+    HIPCHK(hipGetLastError());
+    return RMJ_OK;
+}
+// ---- play statistics (rmj_playstats.hip.h): one launch on the caller's stream
+int rmj_logset_playstats_device(rmj_logset_handle s, uint32_t num_players, int32_t* d_rows, void* hip_stream) {
+    using namespace rmjstat;
+    if (!s) return fail(RMJ_ERR_ARG, "null argument");
+    if (num_players != 3u && num_players != 4u) return fail(RMJ_ERR_ARG, "rmj_logset_playstats_device: num_players is 3 or 4");
+    if (!s->K) return RMJ_OK;
+    if (!d_rows) return fail(RMJ_ERR_ARG, "null argument");
+    if (!grp_aligned(d_rows)) return fail(RMJ_ERR_ARG, "rmj_logset_playstats_device: the rows must be 16-byte aligned");
+    HIPCHK(hipSetDevice(s->device));
+    hipLaunchKernelGGL(k_playstats, dim3((s->M + PS_BLOCK / 64u - 1u) / (PS_BLOCK / 64u)), dim3(PS_BLOCK), 0, (hipStream_t)hip_stream, (const RmjEvent*)s->d_ev,
+                       (const uint32_t*)s->d_off, (const uint32_t*)s->d_koff, s->M, (const uint8_t*)s->d_status, num_players, d_rows);
     HIPCHK(hipGetLastError());
     return RMJ_OK;
 }

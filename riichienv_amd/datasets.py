@@ -251,6 +251,10 @@ class LogSampleBuilder:
         model, grp.DeviceRewardPredictor(model, pts_weight).kyoku_rewards(self) is the table finalize() takes"""
         return self.logset.grp_rows(num_players)
 
+    def play_stats(self, num_players=None):
+        """LogSet.play_stats of the builder's set: how every seat played every kyoku, on the device (riichienv_amd.stats summarises it)"""
+        return self.logset.play_stats(num_players)
+
     def finalize(self, rewards=None):
         """returns and ranks of the pool's samples (rmj_logreplay_finalize_device); rewards: [K, 4] float64 (numpy or torch) by kyoku
         row, default default_rewards()"""

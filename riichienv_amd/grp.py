@@ -120,6 +120,10 @@ class GrpDataset:
             self._rows = self.logset.grp_rows()
         return self._rows
 
+    def play_stats(self, num_players=None):
+        """LogSet.play_stats of the set: how every seat played every kyoku, on the device (riichienv_amd.stats summarises it)"""
+        return self.logset.play_stats(num_players)
+
     def tensors(self):
         """Every (kyoku, seat) row of the good logs at once, in (log, kyoku, seat) order: {"x" [R, 4n + 4] f32, "y" [R, n] f32 (one-hot of
         rank), "rank" [R] i64, "log", "kyoku" (the table row), "seat" [R] i32} on the device.  Reads the row count on the host once."""

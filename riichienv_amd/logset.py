@@ -316,3 +316,48 @@ class LogSet:
         for a in tables:
             a.record_stream(stream)
         return out
+
+    def final_ranks(self, num_players=None):
+        """uint8 [K, n] device tensor: grp_rows()["rank"] alone - every seat's place (0 = first) in its log's final scores, repeated in
+        each kyoku row of the log, 255 in the kyokus of a log that did not parse - through rmj_logset_grp_device with no other output (its
+        walk of the records and the x kernel are not run).  Asynchronous on torch's current stream."""
+        torch, dev = self.torch, self.device
+        n, K = int(self.num_players if num_players is None else num_players), self.n_kyokus
+        rank = torch.full((K, n), 255, dtype=torch.uint8, device=dev)
+        if not K:
+            return rank
+        if not self.handle:
+            raise vecenv.RmjError("the log set is closed")
+        tables = [] if self.owns_tables else [torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32), device=dev) for a in (self.start_scores, self.end_scores)]
+        o = abi.GrpOut(None, None, rank.data_ptr(), None)
+        stream = torch.cuda.current_stream(dev)
+        vecenv._chk(self.L.rmj_logset_grp_device(self.handle, n, *([C.c_void_p(a.data_ptr()) for a in tables] or [None, None]), C.byref(o), C.c_void_p(stream.cuda_stream)))
+        for a in tables:
+            a.record_stream(stream)
+        return rank
+
+    def log_of(self):
+        """int64 [K] device tensor: the log of every kyoku row (from the host's kyoku_offsets: an upload, nothing is read back)"""
+        return self.torch.as_tensor(np.repeat(np.arange(self.M, dtype=np.int64), np.diff(self.kyoku_offsets.astype(np.int64))), device=self.device)
+
+    def play_stats(self, num_players=None):
+        """How every seat played every kyoku (rmj_logset_playstats_device; the columns are abi.PLAYSTAT_NAMES, riichienv_amd.stats summarises
+        them), as device tensors in table order `kyoku_offsets[log] + kyoku - 1`:
+          rows [K, 4, 16] i32 (seats >= num_players all zero; -1 everywhere in the kyokus of a log that did not parse), valid [K] bool (the
+          kyoku's log parsed), log_of [K] i64, kyoku_offsets [M + 1] i64.
+        num_players defaults to the set's.  Asynchronous on torch's current stream; nothing is read back."""
+        torch, dev = self.torch, self.device
+        n, K = int(self.num_players if num_players is None else num_players), self.n_kyokus
+        if n not in (3, 4):
+            raise ValueError("num_players is 3 or 4")
+        if K and not self.handle:
+            raise vecenv.RmjError("the log set is closed")
+        log_of = self.log_of()
+        out = {"rows": torch.empty((K, 4, abi.PLAYSTAT_COLUMNS), dtype=torch.int32, device=dev), "valid": torch.ones((K,), dtype=torch.bool, device=dev),
+               "log_of": log_of, "kyoku_offsets": torch.as_tensor(np.asarray(self.kyoku_offsets, dtype=np.int64), device=dev), "num_players": n}
+        if not K:
+            return out
+        if self.owns_tables:
+            out["valid"] = self._wrap(self._views().status, (self.M,), "|u1")[log_of] == abi.LOGTEXT_OK
+        vecenv._chk(self.L.rmj_logset_playstats_device(self.handle, n, C.c_void_p(out["rows"].data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return out
