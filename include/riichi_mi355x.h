@@ -817,6 +817,89 @@ int rmj_logreplay_counts(rmj_logreplay_handle r, RmjLogReplayCounts* out);
 /* Empties the pool and rewinds every slot to its first log (the handle's games are rewritten by the logs' own start events). */
 int rmj_logreplay_clear(rmj_logreplay_handle r);
 
+/* ------------------------------------------------------------------ log validation
+ * A verdict for every log of a log set before samples are built from it (riichienv-ml validates a corpus one log at a time through
+ * Python, scripts/validate_logs.py): a checking replay on the device, in the slots of a handle like the sample builder's, that records
+ * no sample and allocates no pool.  Every log gets its FIRST finding - the one at the lowest event index, and at one event the lowest
+ * code: code, event (the index of the offending MJAI event in the log, from 0), kyoku (the start_kyoku events of the log up to there),
+ * seat (255: the event names none) and a detail word.  n = the number of players.
+ *   OK
+ *   PARSE               the set keeps the log with a text status other than RMJ_LOGTEXT_OK: it is not replayed; event = the set's
+ *                       error line, detail = the status
+ *   NO_START_KYOKU      an event other than start_game, start_kyoku, end_kyoku, end_game or NONE before the log's first start_kyoku
+ *   AFTER_END           the open kyoku is over (a hora, ryukyoku or end_kyoku was applied) and the event is not hora, end_kyoku,
+ *                       end_game, start_kyoku, start_game or NONE
+ *   UNFINISHED          a start_kyoku, start_game or end_game arrives, or the log ends (event = the log's length), while a kyoku is
+ *                       started and not over - how a log drained from a game in progress ends: the caller may accept the code
+ *   ACTOR               tsumo dahai reach reach_accepted chi pon daiminkan ankan kakan hora (3P: kita) with actor >= n; chi pon
+ *                       daiminkan with target >= n or target == actor; a start_kyoku with oya >= n (kyoku counts it, seat = 255).
+ *                       Such an event is never applied: no game indexes a seat it does not have
+ *   DRAW_OUT_OF_TURN    a tsumo by a seat other than the one due to draw: the oya after start_kyoku, (actor + 1) % n after a dahai,
+ *                       the actor after daiminkan ankan kakan (3P: kita), nobody after tsumo chi pon
+ *   NOT_OFFERED         the kyoku is open and the actor of a decision event (dahai chi pon daiminkan ankan kakan reach hora kita) is
+ *                       offered no list: not among the active seats, or its published list is empty.  The Ron on a robbed kan, as
+ *                       the sample builder recognises it, is exempt
+ *   TILE_NOT_HELD       the actor's concealed hand does not hold the event's tile ids as a multiset: the tile of a dahai or kakan,
+ *                       the first 2 consumed tiles of a chi or pon, 3 of a daiminkan, 4 of an ankan; detail = the tile id
+ *   TILE_COUNT          at start_kyoku, tsumo or dora: among the dealt tiles, the dora markers and the draws of the kyoku so far a
+ *                       tile type occurs more than 4 times (a red five counts to its type) or a red five more than once; detail = a
+ *                       tile id of that name (the event's tile at tsumo / dora).  Masked logs ("?" read as tile 0) trip this
+ *   NO_LEGAL_MATCH      the actor is offered a list and the event matches none of its entries (what fails a log in the sample builder)
+ *   SCORE_CONTINUITY    the end scores of kyoku k - its start scores and what its hora / ryukyoku events move, computed as the kyoku
+ *                       tables compute them for a log's last kyoku - differ from the start scores of kyoku k + 1: reported at the
+ *                       start_kyoku of kyoku k + 1 with kyoku = k + 1, seat = the first seat that differs.  A ryukyoku's deltas are read
+ *                       both ways, without the riichi deposits (converted Tenhou logs: the tables' reading) and with them (logs this
+ *                       engine writes): a kyoku that fits either reading in every seat passes.  (The tables' own end column cannot
+ *                       tell: for every kyoku but the last it IS the next start_kyoku's scores; a set parsed from text keeps these.)
+ *   SCORE_CONSERVATION  sum(end - start) of kyoku k - end as the tables hold it, the start scores of kyoku k + 1 - is not
+ *                       -1000 x (kyotaku[k + 1] - kyotaku[k]), kyotaku from the start_kyoku records; reported like SCORE_CONTINUITY;
+ *                       detail = the sum
+ * Not checked: a second or third hora of a multiple ron against an offer (the kyoku is over when it arrives), settlement amounts (the
+ * records carry no ura markers), feature encodings. */
+#define RMJ_LOGCHECK_OK 0
+#define RMJ_LOGCHECK_PARSE 1
+#define RMJ_LOGCHECK_NO_START_KYOKU 2
+#define RMJ_LOGCHECK_AFTER_END 3
+#define RMJ_LOGCHECK_UNFINISHED 4
+#define RMJ_LOGCHECK_ACTOR 5
+#define RMJ_LOGCHECK_DRAW_OUT_OF_TURN 6
+#define RMJ_LOGCHECK_NOT_OFFERED 7
+#define RMJ_LOGCHECK_TILE_NOT_HELD 8
+#define RMJ_LOGCHECK_TILE_COUNT 9
+#define RMJ_LOGCHECK_NO_LEGAL_MATCH 10
+#define RMJ_LOGCHECK_SCORE_CONTINUITY 11
+#define RMJ_LOGCHECK_SCORE_CONSERVATION 12
+#define RMJ_LOGCHECK_CODES 13
+#define RMJ_LOGCHECK_COUNTERS 16          /* words of the per-code counters */
+#define RMJ_LOGCHECK_GUARDS 1u            /* create flag: RMJ_LOGCHECK_GUARD_WORDS words of RMJ_LOGCHECK_GUARD_WORD either side of every verdict array */
+#define RMJ_LOGCHECK_GUARD_WORDS 64
+#define RMJ_LOGCHECK_GUARD_WORD 0xA5C3F00Du
+struct rmj_logcheck;
+/* The name of a code ("TILE_NOT_HELD"), NULL for a number that is none. */
+const char* rmj_logcheck_name(uint32_t code);
+/* The first n_slots games of the handle are the slots (0 = all of them; else 1 <= n_slots <= the handle's games), at most one per log.
+ * The handle should be used for nothing else while the validation is under way, and its game mode decides the number of players and
+ * the rules the offers follow.  flags: RMJ_LOGCHECK_GUARDS or 0.  The checker lives until its destroy call (before the handle's
+ * rmj_destroy); the log set must outlive it.  RMJ_ERR_ARG for a set on another device, an unknown flag, more slots than logs or games,
+ * a set without logs. */
+int rmj_logcheck_create(rmj_handle h, rmj_logset_handle set, uint32_t n_slots, uint32_t flags, struct rmj_logcheck** out);
+int rmj_logcheck_destroy(struct rmj_logcheck* c);
+/* The score tables (device pointers, i32) the two score checks read instead of the set's own - the start scores [n_kyokus][4], and
+ * [n_kyokus][8] the end scores every kyoku's own events give in both readings (NOT the tables' end column, see SCORE_CONTINUITY): a
+ * set made by rmj_logset_create holds none, and without this call those two checks are left out for it.  Read during
+ * rmj_logcheck_run_device. */
+int rmj_logcheck_set_scores(struct rmj_logcheck* c, const int32_t* d_start_scores /*[n_kyokus][4]*/, const int32_t* d_own_end_scores /*[n_kyokus][8]*/);
+/* n_steps event indices of the validation (0 = to the end), asynchronous on the handle's stream: no host synchronisation, two launches
+ * per event index (the checking pass, the event).  *steps_left (may be NULL) = what remains; the verdicts are complete at 0. */
+int rmj_logcheck_run_device(struct rmj_logcheck* c, uint32_t n_steps, uint32_t* steps_left);
+/* Device pointers to the verdicts: per log code, seat (u8), kyoku, event, detail (u32); counts [RMJ_LOGCHECK_COUNTERS] u32 = logs per code. */
+typedef struct RmjLogCheckViews {
+    uint32_t n_logs, steps;
+    const uint8_t *code, *seat;
+    const uint32_t *kyoku, *event, *detail, *counts;
+} RmjLogCheckViews;
+int rmj_logcheck_views(struct rmj_logcheck* c, RmjLogCheckViews* out);
+
 /* Round boundaries and per-round score deltas for a trainer on the same GPU (what riichienv-ml's PPO worker computes on the host
  * between steps: trainers/_ppo_worker.py:100-116 GRP features, :240-266 the reward at a kyoku boundary, :283-291 rank rewards).
  * Call after every step (asynchronous on the handle's stream): d_ended [n] u8 = 0 the round goes on, 1 a round ended in this step and

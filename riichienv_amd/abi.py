@@ -303,6 +303,18 @@ class LogReplayCounts(C.Structure):  # RmjLogReplayCounts
     _fields_ = [(k, C.c_uint32) for k in ("fill", "overflowed", "failed_logs", "complete_logs", "decisions", "events", "steps_done", "steps_left")]
 
 
+# RMJ_LOGCHECK_*: the verdict codes of rmj_logcheck_* (LogSet.validate), their counters' words, the create flag and its guard words
+LOGCHECK_NAMES = ["OK", "PARSE", "NO_START_KYOKU", "AFTER_END", "UNFINISHED", "ACTOR", "DRAW_OUT_OF_TURN", "NOT_OFFERED", "TILE_NOT_HELD", "TILE_COUNT",
+                  "NO_LEGAL_MATCH", "SCORE_CONTINUITY", "SCORE_CONSERVATION"]
+LOGCHECK_OK, LOGCHECK_PARSE, LOGCHECK_NO_START_KYOKU, LOGCHECK_AFTER_END, LOGCHECK_UNFINISHED, LOGCHECK_ACTOR, LOGCHECK_DRAW_OUT_OF_TURN, LOGCHECK_NOT_OFFERED, \
+    LOGCHECK_TILE_NOT_HELD, LOGCHECK_TILE_COUNT, LOGCHECK_NO_LEGAL_MATCH, LOGCHECK_SCORE_CONTINUITY, LOGCHECK_SCORE_CONSERVATION = range(13)
+LOGCHECK_COUNTERS, LOGCHECK_GUARDS, LOGCHECK_GUARD_WORDS, LOGCHECK_GUARD_WORD = 16, 1, 64, 0xA5C3F00D
+
+
+class LogCheckViews(C.Structure):    # RmjLogCheckViews: device pointers to the verdicts
+    _fields_ = [("n_logs", C.c_uint32), ("steps", C.c_uint32)] + [(k, C.c_void_p) for k in ("code", "seat", "kyoku", "event", "detail", "counts")]
+
+
 class GrpOut(C.Structure):           # RmjGrpOut (rmj_logset_grp_device): device pointers, any may be NULL (x needs meta)
     _fields_ = [(k, C.c_void_p) for k in ("meta", "x", "rank", "log_of")]
 
@@ -427,6 +439,13 @@ PROTOTYPES = [
     ("rmj_logreplay_views", [vp, P(LogReplayViews)]),
     ("rmj_logreplay_counts", [vp, P(LogReplayCounts)]),
     ("rmj_logreplay_clear", [vp]),
+    # ---- log validation
+    ("rmj_logcheck_name", [u32], C.c_char_p),
+    ("rmj_logcheck_create", [vp, vp, u32, u32, P(vp)]),
+    ("rmj_logcheck_destroy", [vp]),
+    ("rmj_logcheck_set_scores", [vp, vp, vp]),
+    ("rmj_logcheck_run_device", [vp, u32, P(u32)]),
+    ("rmj_logcheck_views", [vp, P(LogCheckViews)]),
     ("rmj_round_track_device", [vp, vp, vp, vp, vp]),
     ("rmj_round_track_reset", [vp]),
     ("rmj_scores_device", [vp, vp, vp]),

@@ -47,6 +47,7 @@ using namespace rmj;
 #include "rmj_obs.hip.h"
 #include "rmj_ppo.hip.h"
 #include "rmj_logreplay.hip.h"
+#include "rmj_logcheck.hip.h"
 #include "rmj_logtext.hip.h"
 #include "rmj_grp.hip.h"
 #include "rmj_playstats.hip.h"
@@ -270,6 +271,7 @@ struct rmj_logset {
     uint32_t *d_off = nullptr, *d_koff = nullptr;
     // a set parsed from text (rmj_logset_create_from_text) also holds its score tables and per-log results
     int32_t *d_start = nullptr, *d_end = nullptr;   // [K][4]
+    int32_t* d_own = nullptr;                       // [K][8] the end scores every kyoku's own events gave, in two readings (rmj_logcheck_*)
     uint8_t* d_status = nullptr;                    // [M]
     uint32_t *d_errline = nullptr, *d_dec = nullptr;
 };
@@ -284,6 +286,14 @@ struct rmj_logreplay {
     uint32_t n_powers = 0;
     uint32_t steps = 0, step = 0;      // steps of a whole replay (the longest slot's events), steps taken
     std::vector<uint32_t> slot_first, slot_logs;
+};
+// a checking replay bound to a handle and a log set (rmj_logcheck_create): its verdicts and bookkeeping are one device allocation
+struct rmj_logcheck {
+    rmj_env* env = nullptr;
+    rmj_logset* set = nullptr;
+    void* mem = nullptr;
+    LogCheck R{};
+    uint32_t steps = 0, step = 0;
 };
 // the shanten tables on a device, uploaded once (rmj_create: the handle's Env; the hand API)
 static int shanten_tables_for(int device, ShantenTables* out) {
@@ -2091,7 +2101,7 @@ int rmj_logset_destroy(rmj_logset_handle s) {
     if (!s) return RMJ_OK;
     hipSetDevice(s->device);
     hipFree(s->d_ev); hipFree(s->d_off); hipFree(s->d_koff);
-    hipFree(s->d_start); hipFree(s->d_end); hipFree(s->d_status); hipFree(s->d_errline); hipFree(s->d_dec);
+    hipFree(s->d_start); hipFree(s->d_end); hipFree(s->d_own); hipFree(s->d_status); hipFree(s->d_errline); hipFree(s->d_dec);
     delete s;
     return RMJ_OK;
 }
@@ -2200,8 +2210,9 @@ static int logset_from_text_impl(rmj_logset* s, const uint8_t* text, const uint6
     s->K = s->koff[M];
     if ((rc = dalloc(&s->d_start, (size_t)s->K * 16, true))) return rc;
     if ((rc = dalloc(&s->d_end, (size_t)s->K * 16, true))) return rc;
+    if ((rc = dalloc(&s->d_own, (size_t)s->K * 32, true))) return rc;
     if (M) hipLaunchKernelGGL(k_lt_tables, per_log, b256, 0, 0, (const rmjp::Side*)d_side, (const uint32_t*)s->d_off, (const uint32_t*)s->d_koff, M,
-                              (const unsigned long long*)d_ferr, s->d_start, s->d_end, s->d_status, s->d_errline);
+                              (const unsigned long long*)d_ferr, s->d_start, s->d_end, s->d_own, s->d_status, s->d_errline);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     return RMJ_OK;
@@ -2486,6 +2497,119 @@ int rmj_logreplay_counts(rmj_logreplay_handle r, RmjLogReplayCounts* out) {
     HIPCHK(hipMemcpyAsync(c, r->R.ctr, sizeof(c), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     *out = RmjLogReplayCounts{c[LR_C_FILL], c[LR_C_OVERFLOWED], c[LR_C_FAILED], c[LR_C_COMPLETE], c[LR_C_DECISIONS], c[LR_C_EVENTS], r->step, r->steps - r->step};
+    return RMJ_OK;
+}
+
+// ---- log validation (rmj_logcheck.hip.h) ------------------------------------------------------------------------
+const char* rmj_logcheck_name(uint32_t code) {
+    static const char* const names[RMJ_LOGCHECK_CODES] = {"OK", "PARSE", "NO_START_KYOKU", "AFTER_END", "UNFINISHED", "ACTOR", "DRAW_OUT_OF_TURN", "NOT_OFFERED",
+                                                          "TILE_NOT_HELD", "TILE_COUNT", "NO_LEGAL_MATCH", "SCORE_CONTINUITY", "SCORE_CONSERVATION"};
+    return code < RMJ_LOGCHECK_CODES ? names[code] : nullptr;
+}
+int rmj_logcheck_create(rmj_handle h, rmj_logset_handle set, uint32_t n_slots, uint32_t flags, struct rmj_logcheck** out) {
+    if (!h || !set || !out) return fail(RMJ_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (set->device != h->cfg.device) return fail(RMJ_ERR_ARG, "rmj_logcheck_create: the log set lives on another device");
+    if (flags & ~(uint32_t)RMJ_LOGCHECK_GUARDS) return fail(RMJ_ERR_ARG, "rmj_logcheck_create: unknown flag");
+    const uint32_t games = h->cfg.n_games, n = n_slots ? n_slots : games, M = set->M;
+    if (!M) return fail(RMJ_ERR_ARG, "rmj_logcheck_create: the set holds no log");
+    if (n > games || n > M) return fail(RMJ_ERR_ARG, "rmj_logcheck_create: 1 <= n_slots <= the handle's games, and at most one slot per log");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    std::vector<uint32_t> slot_first(n + 1, 0u), slot_logs(M, 0u), pos(n), cur(n);
+    rmj_logcheck* c = new rmj_logcheck();
+    c->env = h;
+    c->set = set;
+    c->steps = lr_assign(set->off.data(), M, n, nullptr, slot_logs.data(), slot_first.data());
+    for (uint32_t s = 0; s < n; s++) {
+        pos[s] = slot_first[s];
+        cur[s] = set->off[slot_logs[pos[s]]];   // (n <= M: every slot has a log)
+    }
+    const bool sanma = h->cfg.game_mode >= 3;
+    LogCheck& R = c->R;
+    R.n = n; R.M = M; R.NP = sanma ? 3u : 4u; R.sanma = sanma ? 1u : 0u;
+    R.ev = set->d_ev; R.off = set->d_off; R.koff = set->d_koff; R.status = set->d_status; R.errline = set->d_errline;
+    R.start = set->d_start; R.end = set->d_own;
+    const size_t guard = (flags & RMJ_LOGCHECK_GUARDS) ? (size_t)RMJ_LOGCHECK_GUARD_WORDS * 4 : 0;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    auto verdict = [&](size_t bytes) { take(guard); const size_t o = take(bytes); return o; };   // (256-byte steps: a guard of 64 words ends where its array begins)
+    const size_t o_code = verdict(M), o_seat = verdict(M), o_kyoku = verdict((size_t)M * 4), o_event = verdict((size_t)M * 4), o_detail = verdict((size_t)M * 4),
+                 o_counts = verdict(RMJ_LOGCHECK_COUNTERS * 4), o_tail = take(guard), o_sfirst = take((size_t)(n + 1) * 4), o_slogs = take((size_t)M * 4),
+                 o_pos = take((size_t)n * 4), o_cur = take((size_t)n * 4), o_kcount = take((size_t)n * 4), o_word = take((size_t)n * 4),
+                 o_seen = take((size_t)n * LC_SEEN), o_apply = take((size_t)games * 4);
+    (void)o_tail;
+    if (hipMalloc(&c->mem, off) != hipSuccess) {
+        (void)hipGetLastError();
+        delete c;
+        return fail(RMJ_ERR_HIP, "rmj_logcheck_create: no device memory for the verdicts");
+    }
+    uint8_t* m = (uint8_t*)c->mem;
+    R.code = m + o_code; R.seat = m + o_seat; R.kyoku = (uint32_t*)(m + o_kyoku); R.event = (uint32_t*)(m + o_event); R.detail = (uint32_t*)(m + o_detail);
+    R.counts = (uint32_t*)(m + o_counts); R.slot_first = (uint32_t*)(m + o_sfirst); R.slot_logs = (uint32_t*)(m + o_slogs); R.pos = (uint32_t*)(m + o_pos);
+    R.cur = (uint32_t*)(m + o_cur); R.kcount = (uint32_t*)(m + o_kcount); R.word = (uint32_t*)(m + o_word); R.seen = m + o_seen; R.apply_at = (uint32_t*)(m + o_apply);
+    // zeros everywhere, then the guards (which end where an array begins, and begin where the array's 256-byte step ends), the "nobody is
+    // due" words, "no event" for every game of the handle, the assignment and the cursors; the verdicts start as OK / PARSE
+    std::vector<uint32_t> gw(RMJ_LOGCHECK_GUARD_WORDS, RMJ_LOGCHECK_GUARD_WORD), word(n, (uint32_t)LC_NONE | (LC_NO_SEAT << 8));
+    bool ok = hipMemsetAsync(m, 0, off, h->stream) == hipSuccess && hipStreamSynchronize(h->stream) == hipSuccess;
+    if (guard)
+        for (size_t o : {o_code, o_seat, o_kyoku, o_event, o_detail, o_counts, o_tail + guard})
+            ok = ok && hipMemcpy(m + o - guard, gw.data(), guard, hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && hipMemset(R.apply_at, 0xFF, (size_t)games * 4) == hipSuccess && hipMemcpy(R.word, word.data(), (size_t)n * 4, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(m + o_sfirst, slot_first.data(), (size_t)(n + 1) * 4, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(m + o_slogs, slot_logs.data(), (size_t)M * 4, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(R.pos, pos.data(), (size_t)n * 4, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(R.cur, cur.data(), (size_t)n * 4, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+        hipLaunchKernelGGL(k_logcheck_init, dim3((M + 255u) / 256u), dim3(256), 0, h->stream, R);
+        ok = hipGetLastError() == hipSuccess;
+    }
+    if (!ok) {
+        (void)hipGetLastError();
+        hipFree(c->mem);
+        delete c;
+        return fail(RMJ_ERR_HIP, "rmj_logcheck_create: initialising the verdicts failed");
+    }
+    *out = c;
+    return RMJ_OK;
+}
+int rmj_logcheck_destroy(struct rmj_logcheck* c) {
+    if (!c) return RMJ_OK;
+    rmj_env* h = c->env;
+    hipSetDevice(h->cfg.device);
+    if (h->stream) hipStreamSynchronize(h->stream);
+    hipFree(c->mem);
+    delete c;
+    return RMJ_OK;
+}
+int rmj_logcheck_set_scores(struct rmj_logcheck* c, const int32_t* d_start_scores, const int32_t* d_end_scores) {
+    if (!c) return fail(RMJ_ERR_ARG, "null argument");
+    if (!d_start_scores != !d_end_scores) return fail(RMJ_ERR_ARG, "rmj_logcheck_set_scores: give both tables or neither");
+    c->R.start = d_start_scores ? d_start_scores : c->set->d_start;
+    c->R.end = d_end_scores ? d_end_scores : c->set->d_own;
+    return RMJ_OK;
+}
+int rmj_logcheck_run_device(struct rmj_logcheck* c, uint32_t n_steps, uint32_t* steps_left) {
+    if (!c) return fail(RMJ_ERR_ARG, "null argument");
+    rmj_env* h = c->env;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const LogCheck& R = c->R;
+    const uint32_t left = c->steps - c->step, todo = n_steps && n_steps < left ? n_steps : left;
+    const bool sanma = h->cfg.game_mode >= 3;
+    for (uint32_t i = 0; i < todo; i++) {
+        hipLaunchKernelGGL(k_log_check, game_grid(R.n), dim3(256), 0, h->stream, h->d, R, 0);
+        if (sanma) hipLaunchKernelGGL(rmj3::k_log_apply, game_grid(R.n), dim3(256), 0, h->stream, (const Env*)h->d_env, R.ev, (const uint32_t*)R.apply_at);
+        else hipLaunchKernelGGL(rmj4::k_log_apply, game_grid(R.n), dim3(256), 0, h->stream, (const Env*)h->d_env, R.ev, (const uint32_t*)R.apply_at);
+    }
+    c->step += todo;
+    // the verdicts of the logs that just ended
+    hipLaunchKernelGGL(k_log_check, game_grid(R.n), dim3(256), 0, h->stream, h->d, R, 1);
+    HIPCHK(hipGetLastError());
+    if (steps_left) *steps_left = c->steps - c->step;
+    return RMJ_OK;
+}
+int rmj_logcheck_views(struct rmj_logcheck* c, RmjLogCheckViews* out) {
+    if (!c || !out) return fail(RMJ_ERR_ARG, "null argument");
+    const LogCheck& R = c->R;
+    *out = RmjLogCheckViews{R.M, c->steps, R.code, R.seat, R.kyoku, R.event, R.detail, R.counts};
     return RMJ_OK;
 }
 

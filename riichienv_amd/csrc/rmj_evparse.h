@@ -794,6 +794,11 @@ RMJP_FN uint8_t parse_line(const uint8_t* p, uint32_t len, uint32_t num_players,
 // end-of-round `scores` has another length than the kyoku's.
 struct KyokuWalk {
     int32_t start[4], end[4];
+    // with a row: the end scores the kyoku's own events gave, before the next start_kyoku's scores replace them - own[0..3] as `end` holds
+    // them, own[4..7] with a ryukyoku's deltas read as already holding the riichi deposits (logs written by this engine do; log validation
+    // accepts either reading)
+    int32_t own[8];
+    int32_t end2[4];           // the second reading while the kyoku is open
     uint32_t n = 0;            // seats of the open kyoku's scores (min 4)
     uint32_t n_raw = 0;        // len(scores) uncut
     uint32_t kyokus = 0;       // start_kyoku events so far
@@ -809,10 +814,10 @@ struct KyokuWalk {
         bool emit = false;
         if (s.cls == CLS_START_KYOKU) {
             if (have) {
-                for (int k = 0; k < 4; k++) { start_out[k] = start[k]; end_out[k] = s.scores[k]; }
+                for (int k = 0; k < 4; k++) { start_out[k] = start[k]; end_out[k] = s.scores[k]; own[k] = end[k]; own[4 + k] = end2[k]; }
                 emit = true;
             }
-            for (int k = 0; k < 4; k++) start[k] = end[k] = s.scores[k];
+            for (int k = 0; k < 4; k++) start[k] = end[k] = end2[k] = s.scores[k];
             n_raw = s.n_scores;
             n = n_raw > 4u ? 4u : n_raw;
             kyokus++;
@@ -836,7 +841,7 @@ struct KyokuWalk {
         } else if (s.cls == CLS_HORA || s.cls == CLS_RYUKYOKU) {
             if (s.flags & SF_HAS_SCORES) {
                 if ((s.n_scores > 4u ? 4u : s.n_scores) != n) { fail(RMJ_LOGTEXT_UNSUPPORTED); return false; }
-                for (int k = 0; k < 4; k++) end[k] = s.scores[k];
+                for (int k = 0; k < 4; k++) end[k] = end2[k] = s.scores[k];
             } else if (s.flags & SF_HAS_DELTAS) {
                 const uint8_t sticks = s.cls == CLS_HORA ? accepted : reached;
                 for (uint32_t k = 0; k < 4u; k++) {
@@ -846,6 +851,8 @@ struct KyokuWalk {
                     else v = (int64_t)start[k] + s.deltas[k] - (((sticks >> k) & 1u) ? 1000 : 0);
                     if (v < -(int64_t)2147483648LL || v > (int64_t)2147483647LL) { fail(RMJ_LOGTEXT_UNSUPPORTED); return false; }
                     end[k] = (int32_t)v;
+                    const int64_t v2 = s.cls == CLS_RYUKYOKU ? (int64_t)start[k] + s.deltas[k] : v;
+                    end2[k] = (int32_t)(v2 > (int64_t)2147483647LL ? (int64_t)2147483647LL : v2);
                 }
             }
         }
@@ -854,7 +861,7 @@ struct KyokuWalk {
     // after the last event: true when a last row (`kyokus - 1`) is pending
     RMJP_FN bool finish(int32_t* start_out, int32_t* end_out) {
         if (!have) return false;
-        for (int k = 0; k < 4; k++) { start_out[k] = start[k]; end_out[k] = end[k]; }
+        for (int k = 0; k < 4; k++) { start_out[k] = start[k]; end_out[k] = own[k] = end[k]; own[4 + k] = end2[k]; }
         return true;
     }
 };

@@ -133,15 +133,34 @@ __device__ __forceinline__ uint64_t lr_select(const uint64_t* __restrict__ lg, u
     return lg[__ffsll((long long)b) - 1];
 }
 
+// The tile of the kan that the hora `e` at event `cur` of a log (its first event: `lo`) robs, RMJ_TILE_NONE if it robs none: the log's
+// previous action - dora events do not count - is a kakan or an ankan by another seat (the record carries no target: on a played log
+// that seat is the target).  The caller has seen that the hora's actor is not among the active seats.
+__device__ __forceinline__ uint32_t lr_robbed_kan_tile(const RmjEvent* __restrict__ ev, uint32_t lo, uint32_t cur, const RmjEvent* __restrict__ e) {
+    uint32_t tile = RMJ_TILE_NONE;
+    for (uint32_t j = cur; j > lo;) {
+        j--;
+        const RmjEvent* q = ev + (size_t)j * 3;
+        if (q->type == RMJ_EV_DORA) continue;
+        if (q->actor != e->actor) {
+            if (q->type == RMJ_EV_KAKAN) tile = q->tile;
+            else if (q->type == RMJ_EV_ANKAN && (q->flags >> 4)) tile = q->consumed[0];
+        }
+        break;
+    }
+    return tile;
+}
+
 // One step of the replay, part one: one wave per slot.  The slot first leaves logs that are over (marking them complete) and takes its
 // next one; then the decisions of ReplayBatch._decisions_before for the event at the slot's cursor - see lr_select, plus what the log
 // walker yields without a direct match: the Pass of every seat that let a claim go (include_pass), the Ron on a robbed kakan / ankan
 // (replay/mod.rs:483-527: not in the published lists, the seat is not even active), and skip_single_action (a decision over a list of
 // at most one entry is not a sample and does not count in `t`).  Passes come first, highest seat first, like Kyoku.steps delivers them.
 // A decision event whose actor is offered a list that holds no match fails the log (status word, counter): its slot goes on to its
-// next log in the same step.  That is the ONLY failure detected: apply_event reports nothing, so an event that does not fit the state in
-// another way - a decision event by a seat that is not to act, a tsumo out of turn - is applied as rmj_apply_events applies it, and the
-// log counts as complete.  settle_only: only the bookkeeping (the last call of a run: the logs that just ended become complete).
+// next log in the same step.  That is the only failure THIS replay detects: apply_event reports nothing, so an event that does not fit the
+// state in another way - a decision event by a seat that is not to act, a tsumo out of turn - is applied as rmj_apply_events applies it,
+// and the log counts as complete.  The checking replay (rmj_logcheck.hip.h, LogSet.validate()) finds those before samples are built.
+// settle_only: only the bookkeeping (the last call of a run: the logs that just ended become complete).
 // Wave 0 also adds the samples of the previous step to the pool's fill (nothing reads the fill during this launch).
 __global__ __launch_bounds__(256) void k_log_decide(Env E, LogRun R, int settle_only) {
     const int lane = threadIdx.x & 63;
@@ -190,19 +209,8 @@ __global__ __launch_bounds__(256) void k_log_decide(Env E, LogRun R, int settle_
         for (int s = 0; s < 4; s++) sel[s] = RMJ_NO_ACTION;
         bool matched = false;
         if (ty == RMJ_EV_HORA && !done && !((am >> actor) & 1u)) {
-            // the Ron on a robbed kan: the log's previous action - dora events do not count - is a kakan or an ankan by another seat
-            // (the record carries no target: on a played log that seat is the target)
-            uint32_t tile = RMJ_TILE_NONE;
-            for (uint32_t j = cur, lo = R.off[log]; j > lo;) {
-                j--;
-                const RmjEvent* q = R.ev + (size_t)j * 3;
-                if (q->type == RMJ_EV_DORA) continue;
-                if (q->actor != e->actor) {
-                    if (q->type == RMJ_EV_KAKAN) tile = q->tile;
-                    else if (q->type == RMJ_EV_ANKAN && (q->flags >> 4)) tile = q->consumed[0];
-                }
-                break;
-            }
+            // the Ron on a robbed kan
+            const uint32_t tile = lr_robbed_kan_tile(R.ev, R.off[log], cur, e);
             if (tile != RMJ_TILE_NONE) {
                 const uint64_t ron = mk_action(RMJ_RON, tile, 0);
 #pragma unroll

@@ -12,7 +12,9 @@
 //                      rmjp::parse_line out of LDS into records in LDS, and the wave stores the records with 16-byte vector stores.  The side
 //                      structs go to a temporary array; kyoku / decision counts and the first failing line go to per-log words by atomics.
 //   k_lt_tables        one wave per log walks the side structs in order (rmjp::KyokuWalk, uniform across the wave; only the events that
-//                      matter are broadcast) and writes start / end scores, status and error line.
+//                      matter are broadcast) and writes start / end scores, status and error line - and `own` [K][8], the end scores
+//                      every kyoku's own events gave in two readings (rmjp::KyokuWalk::own; the `end` of a kyoku before the last is the next
+//                      start_kyoku's scores: log validation compares the two).
 // start_kyoku lines (~450 bytes, about 1 in 500) stay with their lane: see DESIGN.md.
 #pragma once
 #include "rmj_evparse.h"
@@ -215,7 +217,7 @@ __global__ __launch_bounds__(64) void k_lt_parse(const uint8_t* __restrict__ tex
 
 __global__ __launch_bounds__(256) void k_lt_tables(const rmjp::Side* __restrict__ sides, const uint32_t* __restrict__ off, const uint32_t* __restrict__ koff, uint32_t M,
                                                    const unsigned long long* __restrict__ first_err, int32_t* __restrict__ start, int32_t* __restrict__ end,
-                                                   uint8_t* __restrict__ status, uint32_t* __restrict__ error_line) {
+                                                   int32_t* __restrict__ own, uint8_t* __restrict__ status, uint32_t* __restrict__ error_line) {
     const uint32_t lane = threadIdx.x & 63u, l = blockIdx.x * 4u + (threadIdx.x >> 6);
     if (l >= M) return;
     rmjp::KyokuWalk walk;
@@ -250,7 +252,7 @@ __global__ __launch_bounds__(256) void k_lt_tables(const rmjp::Side* __restrict_
             for (int k = 0; k < 10; k++) tp[k] = __shfl(w[k], j);
             if (walk.feed(t, so, eo)) {
                 if (lane == 0 && row < r1) {
-                    for (int k = 0; k < 4; k++) { start[(size_t)row * 4 + k] = so[k]; end[(size_t)row * 4 + k] = eo[k]; }
+                    for (int k = 0; k < 4; k++) { start[(size_t)row * 4 + k] = so[k]; end[(size_t)row * 4 + k] = eo[k]; own[(size_t)row * 8 + k] = walk.own[k]; own[(size_t)row * 8 + 4 + k] = walk.own[4 + k]; }
                 }
                 row++;
             }
@@ -259,7 +261,7 @@ __global__ __launch_bounds__(256) void k_lt_tables(const rmjp::Side* __restrict_
     }
     if (walk.finish(so, eo)) {
         if (lane == 0 && row < r1) {
-            for (int k = 0; k < 4; k++) { start[(size_t)row * 4 + k] = so[k]; end[(size_t)row * 4 + k] = eo[k]; }
+            for (int k = 0; k < 4; k++) { start[(size_t)row * 4 + k] = so[k]; end[(size_t)row * 4 + k] = eo[k]; own[(size_t)row * 8 + k] = walk.own[k]; own[(size_t)row * 8 + 4 + k] = walk.own[4 + k]; }
         }
     }
     if (lane == 0) {

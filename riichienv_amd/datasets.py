@@ -16,8 +16,9 @@ What the records do not carry.  Matching follows the packed records, which hold 
 field reads as tsumogiri = false (select_action_from_mjai skips the drawn-tile rule when the field is absent, so on third-party logs
 without it the builder may pick the other tile of the same name), a kakan is matched by its tile name without `consumed`, and the seat
 a robbed kan is taken from is the log's previous actor, not the hora's `target`.  On logs that a game produced these agree.  The only
-failure detected is a decision that matches nothing in the list its actor is offered; an event that does not fit the state in another
-way (a decision by a seat that is not to act) is applied like apply_events applies it and the log counts as complete.
+failure the builder detects is a decision that matches nothing in the list its actor is offered; an event that does not fit the state in
+another way (a decision by a seat that is not to act) is applied like apply_events applies it and the log counts as complete.  For logs
+of unknown quality call validate() first (LogSet.validate, logcheck.py): a checking replay that gives every log a verdict.
 
 Memory: the pool is capacity x (C x W x 4 + A + 52) bytes, and samples() holds a second copy of what it emits (fill x the same row) until
 the next run() / finalize() / clear() - at the default capacity about three times the samples' own size in all.  What does not fit is counted (`counts()["overflowed"]`) and the trajectory that lost a
@@ -254,6 +255,11 @@ class LogSampleBuilder:
     def play_stats(self, num_players=None):
         """LogSet.play_stats of the builder's set: how every seat played every kyoku, on the device (riichienv_amd.stats summarises it)"""
         return self.logset.play_stats(num_players)
+
+    def validate(self, n_slots=None):
+        """LogSet.validate of the builder's set, with the builder's game mode and rule: a verdict for every log (logcheck.LogReport), by a
+        checking replay of its own - the builder's pool and slots are not touched"""
+        return self.logset.validate(self.game_mode, self.rule, n_slots, self.shared)
 
     def finalize(self, rewards=None):
         """returns and ranks of the pool's samples (rmj_logreplay_finalize_device); rewards: [K, 4] float64 (numpy or torch) by kyoku

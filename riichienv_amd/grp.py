@@ -124,6 +124,11 @@ class GrpDataset:
         """LogSet.play_stats of the set: how every seat played every kyoku, on the device (riichienv_amd.stats summarises it)"""
         return self.logset.play_stats(num_players)
 
+    def validate(self, rule=None, n_slots=None):
+        """LogSet.validate of the set, in the dataset's game mode: a verdict for every log (logcheck.LogReport) - a log that did not parse,
+        which this dataset keeps out of its rows, is PARSE there"""
+        return self.logset.validate(self.game_mode, rule, n_slots)
+
     def tensors(self):
         """Every (kyoku, seat) row of the good logs at once, in (log, kyoku, seat) order: {"x" [R, 4n + 4] f32, "y" [R, n] f32 (one-hot of
         rank), "rank" [R] i64, "log", "kyoku" (the table row), "seat" [R] i32} on the device.  Reads the row count on the host once."""

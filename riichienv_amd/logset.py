@@ -60,6 +60,39 @@ def kyoku_tables(logs, n_players):
     return np.array(start, dtype=np.int32).reshape(-1, 4), np.array(end, dtype=np.int32).reshape(-1, 4)
 
 
+def kyoku_own_end_scores(logs, n_players):
+    """[K, 8] int32: the end scores every kyoku's own hora / ryukyoku events give - kyoku_tables' end column before MjaiReplay replaces it,
+    for every kyoku but a log's last, with the next start_kyoku's scores - in two readings: [:, :4] as Kyoku computes them (a ryukyoku's
+    deltas without the riichi deposits, as converted Tenhou logs hold them), [:, 4:] with a ryukyoku's deltas read as already holding the
+    deposits (as this engine writes them).  validate() compares them with the next kyoku's start scores."""
+    from .replay import Kyoku
+
+    rows = []
+
+    def close(k, alt):
+        rows.append((list(k.end_scores) + [0] * 4)[:4] + (list(alt) + [0] * 4)[:4])
+
+    for log in logs:
+        cur = alt = None
+        for ev in _events_of(log):
+            ty = ev.get("type")
+            if ty == "start_kyoku" or ty in ("end_kyoku", "end_game"):
+                if cur is not None:
+                    close(cur, alt)
+                cur = Kyoku(ev) if ty == "start_kyoku" else None
+                alt = list(cur.scores) if cur is not None else None
+            elif cur is not None:
+                cur._feed(ev)
+                deltas = ev.get("deltas", ev.get("delta"))
+                if ty == "ryukyoku" and ev.get("scores") is None and deltas is not None:
+                    alt = [s + d for s, d in zip(cur.scores, deltas)] + list(cur.scores[len(deltas):])
+                elif ty in ("hora", "ryukyoku"):
+                    alt = list(cur.end_scores)
+        if cur is not None:
+            close(cur, alt)
+    return np.array(rows, dtype=np.int32).reshape(-1, 8)
+
+
 def _text_and_ranges(text, ranges):
     """(uint8 array, [M, 2] uint64 ranges) of from_text's two input forms"""
     if ranges is None:
@@ -361,3 +394,12 @@ class LogSet:
             out["valid"] = self._wrap(self._views().status, (self.M,), "|u1")[log_of] == abi.LOGTEXT_OK
         vecenv._chk(self.L.rmj_logset_playstats_device(self.handle, n, C.c_void_p(out["rows"].data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
         return out
+
+    def validate(self, game_mode=None, rule=None, n_slots=None, share_stream=True):
+        """A verdict for every log, by a checking replay on the device (rmj_logcheck_*): a logcheck.LogReport with the first finding of
+        every log - code, event, kyoku, seat, detail - and summary() / good_ids() / describe(i).  riichienv_amd.logcheck lists the codes
+        and the known limits (a later hora of a multiple ron is not checked against an offer, settlement amounts are not recomputed,
+        feature encodings are not inspected, masked logs trip TILE_COUNT).  A set of no logs returns an empty report."""
+        from . import logcheck
+
+        return logcheck.validate(self, game_mode, rule, n_slots, share_stream)
