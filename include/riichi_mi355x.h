@@ -457,6 +457,36 @@ int rmj_step_ids_encode_batch_device(rmj_handle h, const int32_t* d_action_ids, 
 int rmj_step_sample_encode_batch_device(rmj_handle h, const float* d_logits, uint32_t stride, uint64_t seed, int auto_reset,
                                         int32_t* d_ids, const RmjObsBatch* b);
 
+/* Hidden-hand targets: what the observation hides from a seat - the concealed tiles, shanten number, waits and flags of its three
+ * opponents - read from the complete state on the device (auxiliary heads for opponent tenpai / waits / hand; the input of an oracle
+ * or perfect-information critic).  For the pair (game g, hero seat a) opponent r = 0, 1, 2 is seat (a + 1 + r) mod NP: shimocha,
+ * toimen, kamicha; in 3P r = 2 is absent (every field zero, flags 0), and so is every opponent of a row whose index names no
+ * (game, seat < NP) of the handle.
+ *   d_opp_hand    [rows][3][34] u8  concealed tiles by tile type (red fives count as fives; 34 columns in 3P too)
+ *   d_opp_shanten [rows][3] i8      calculate_shanten / calculate_shanten_3p (shanten.rs:244-261 / :470-484) of that histogram with
+ *                                   total / 3 groups: rmj_shanten of the same row (-1 = complete; chiitoi and kokushi with four groups)
+ *   d_opp_waits   [rows][3] u64     bit t: HandEvaluator(hand, melds).get_waits() holds type t (hand_evaluator.rs:196-213) - empty
+ *                                   unless concealed + 3 x melds = 13; a type already held four times is skipped
+ *   d_opp_flags   [rows][3] u8      RMJ_HIDDEN_* bits, n_melds in bits 4..6 */
+#define RMJ_HIDDEN_PRESENT 1u  /* the opponent exists */
+#define RMJ_HIDDEN_TENPAI 2u   /* waits != 0 */
+#define RMJ_HIDDEN_RIICHI 4u   /* riichi_declared */
+#define RMJ_HIDDEN_FURITEN 8u  /* the waits meet a type of the seat's discards, or missed_agari_doujun, or missed_agari_riichi */
+#define RMJ_HIDDEN_MELDS_SHIFT 4
+typedef struct RmjHiddenOut {
+    uint8_t* d_opp_hand;
+    int8_t* d_opp_shanten;
+    uint64_t* d_opp_waits;
+    uint8_t* d_opp_flags;
+} RmjHiddenOut;
+/* The rows of d_index [rows] i32 = game * 4 + seat - what rmj_encode_compact_device and rmj_get_legal_compact hand out, or any other
+ * (game, seat), acting or not - into the caller's device arrays.  d_count (device u32, may be NULL): rows at or behind
+ * min(rows, *d_count) are left untouched, so the count of a compact batch can stay on the device.  Only reads the state (no cache is
+ * written back).  Asynchronous on the handle's stream.  RMJ_ERR_ARG for a null handle / descriptor, or null arrays with rows > 0. */
+int rmj_hidden_targets_device(rmj_handle h, const int32_t* d_index, uint32_t rows, const uint32_t* d_count, const RmjHiddenOut* out);
+/* The same with host pointers (index and the four arrays of `out`): staged on the device, returns when the rows are there. */
+int rmj_hidden_targets(rmj_handle h, const int32_t* index, uint32_t rows, const RmjHiddenOut* out);
+
 /* shanten.rs:244-261 calculate_shanten / :470-484 calculate_shanten_3p over raw 34-histograms
  * (len_div3 = tile count / 3; -1 = complete hand).  Tables are generated at first use, on the host. */
 int rmj_shanten(int device, const uint8_t* counts /*[n][34]*/, uint32_t n, int sanma, int8_t* out /*[n]*/);
@@ -729,9 +759,10 @@ int rmj_logreplay_assign(const uint32_t* offsets, uint32_t n_logs, uint32_t n_sl
                          uint32_t* steps);
 #define RMJ_LOGREPLAY_INCLUDE_PASS 1u        /* the Pass of every seat that was offered a claim and let it go is a sample */
 #define RMJ_LOGREPLAY_SKIP_SINGLE_ACTION 2u  /* a decision over a list of at most one action is no sample (LogKyoku.steps' default) */
+#define RMJ_LOGREPLAY_HIDDEN 4u              /* every pool slot also keeps its hidden-hand record and event index: rmj_logreplay_emit_hidden_device */
 typedef struct RmjLogReplayConfig {
     int32_t features;           /* RMJ_FEATURES_*: the rows the pool stores */
-    uint32_t capacity;          /* samples: capacity x (C x W x 4 + A + 52) bytes of device memory */
+    uint32_t capacity;          /* samples: capacity x (C x W x 4 + A + 52) bytes of device memory, + 152 with RMJ_LOGREPLAY_HIDDEN */
     uint32_t flags;             /* RMJ_LOGREPLAY_* */
     uint32_t n_powers;
     double gamma;
@@ -816,6 +847,32 @@ typedef struct RmjLogReplayCounts {
 int rmj_logreplay_counts(rmj_logreplay_handle r, RmjLogReplayCounts* out);
 /* Empties the pool and rewinds every slot to its first log (the handle's games are rewritten by the logs' own start events). */
 int rmj_logreplay_clear(rmj_logreplay_handle r);
+/* RMJ_LOGREPLAY_HIDDEN: every sample also gets the hidden-hand row of (its slot's game, the deciding seat) - the fields of
+ * rmj_hidden_targets_device - and `event`, the index in its log of the event the decision precedes.  Both are taken at the moment
+ * the feature row is: from the state before the step's event is applied, by a kernel of their own between the step's record and apply
+ * launches (without the flag the replay launches what it always did and allocates nothing more).  A sample that found no pool slot
+ * has no record either.  The records lie in a second allocation of capacity x 152 bytes: per slot three opponents of 48 bytes (waits
+ * u64 at 0, hand [34] u8 at 8, shanten i8 at 42, flags u8 at 43), then the event i32 at 144.  Meaningless on logs with masked ("?")
+ * tiles: the caller keeps such sets away (the records do not say how a set was made).
+ * The emit call writes the records of the samples rmj_logreplay_emit_device emits, to the same rows in the same order: d_opp_* as
+ * in RmjHiddenOut, d_event [rows] i32; rows beyond `rows` are dropped like there.  Call it while the pool is as the other emit call
+ * saw it.  RMJ_ERR_ARG for a builder made without the flag. */
+typedef struct RmjLogHiddenBatch {
+    uint8_t* d_opp_hand;     /* [rows][3][34] */
+    int8_t* d_opp_shanten;   /* [rows][3] */
+    uint64_t* d_opp_waits;   /* [rows][3] */
+    uint8_t* d_opp_flags;    /* [rows][3] */
+    int32_t* d_event;        /* [rows] */
+    uint32_t rows, reserved;
+} RmjLogHiddenBatch;
+int rmj_logreplay_emit_hidden_device(rmj_logreplay_handle r, const RmjLogHiddenBatch* out);
+/* The records themselves, without a copy (slot s < fill at records + s x record_bytes); records = NULL for a builder made without
+ * the flag. */
+typedef struct RmjLogHiddenViews {
+    uint32_t capacity, record_bytes;
+    const uint8_t* records;
+} RmjLogHiddenViews;
+int rmj_logreplay_hidden_views(rmj_logreplay_handle r, RmjLogHiddenViews* out);
 
 /* ------------------------------------------------------------------ log validation
  * A verdict for every log of a log set before samples are built from it (riichienv-ml validates a corpus one log at a time through

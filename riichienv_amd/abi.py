@@ -280,7 +280,12 @@ LOGTEXT_OK, LOGTEXT_UNSUPPORTED, LOGTEXT_ERR_JSON, LOGTEXT_ERR_KEY, LOGTEXT_ERR_
 LOGTEXT_STATUS_NAMES = ["OK", "UNSUPPORTED", "ERR_JSON", "ERR_KEY", "ERR_TEHAI", "ERR_TILE", "ERR_VALUE", "ERR_REPLAY"]
 LOGTEXT_ON_DEVICE, LOGTEXT_MASKED_OK = 1, 2
 
-LOGREPLAY_INCLUDE_PASS, LOGREPLAY_SKIP_SINGLE_ACTION = 1, 2   # RMJ_LOGREPLAY_*
+LOGREPLAY_INCLUDE_PASS, LOGREPLAY_SKIP_SINGLE_ACTION, LOGREPLAY_HIDDEN = 1, 2, 4   # RMJ_LOGREPLAY_*
+HIDDEN_PRESENT, HIDDEN_TENPAI, HIDDEN_RIICHI, HIDDEN_FURITEN, HIDDEN_MELDS_SHIFT = 1, 2, 4, 8, 4   # RMJ_HIDDEN_*: the bits of opp_flags
+
+
+class HiddenOut(C.Structure):        # RmjHiddenOut (rmj_hidden_targets_device)
+    _fields_ = [(k, C.c_void_p) for k in ("opp_hand", "opp_shanten", "opp_waits", "opp_flags")]
 
 
 class LogReplayConfig(C.Structure):  # RmjLogReplayConfig
@@ -297,6 +302,14 @@ class LogReplayViews(C.Structure):   # RmjLogReplayViews
     _fields_ = [(k, C.c_uint32) for k in ("capacity", "row_stride", "action_space", "steps")] + [
         (k, C.c_void_p) for k in ("features", "mask", "action", "packed", "ret", "ret64", "rank", "log", "kyoku", "seat", "t", "log_status", "traj_len",
                                   "traj_broken", "counters")]
+
+
+class LogHiddenBatch(C.Structure):   # RmjLogHiddenBatch (rmj_logreplay_emit_hidden_device)
+    _fields_ = [(k, C.c_void_p) for k in ("opp_hand", "opp_shanten", "opp_waits", "opp_flags", "event")] + [("rows", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class LogHiddenViews(C.Structure):   # RmjLogHiddenViews
+    _fields_ = [("capacity", C.c_uint32), ("record_bytes", C.c_uint32), ("records", C.c_void_p)]
 
 
 class LogReplayCounts(C.Structure):  # RmjLogReplayCounts
@@ -401,6 +414,8 @@ PROTOTYPES = [
     ("rmj_encode_batch", [vp, P(ObsBatch)]),
     ("rmj_step_ids_encode_batch_device", [vp, vp, cint, P(ObsBatch)]),
     ("rmj_step_sample_encode_batch_device", [vp, vp, u32, u64, cint, vp, P(ObsBatch)]),
+    ("rmj_hidden_targets_device", [vp, vp, u32, vp, P(HiddenOut)]),
+    ("rmj_hidden_targets", [vp, vp, u32, P(HiddenOut)]),
     ("rmj_shanten", [cint, vp, u32, cint, vp]),
     ("rmj_effective_tiles", [cint, vp, u32, cint, vp]),
     ("rmj_best_ukeire", [cint, vp, vp, u32, cint, vp]),
@@ -439,6 +454,8 @@ PROTOTYPES = [
     ("rmj_logreplay_views", [vp, P(LogReplayViews)]),
     ("rmj_logreplay_counts", [vp, P(LogReplayCounts)]),
     ("rmj_logreplay_clear", [vp]),
+    ("rmj_logreplay_emit_hidden_device", [vp, P(LogHiddenBatch)]),
+    ("rmj_logreplay_hidden_views", [vp, P(LogHiddenViews)]),
     # ---- log validation
     ("rmj_logcheck_name", [u32], C.c_char_p),
     ("rmj_logcheck_create", [vp, vp, u32, u32, P(vp)]),

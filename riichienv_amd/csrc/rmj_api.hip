@@ -53,6 +53,7 @@ using namespace rmj;
 #include "rmj_playstats.hip.h"
 #include "rmj_handtab.hip.h"
 #include "rmj_events.hip.h"
+#include "rmj_hidden.hip.h"
 
 static inline dim3 step_grid(uint32_t n) { return dim3((n + RMJ_STEP_WPB - 1) / RMJ_STEP_WPB); }
 // smallest batch that a multi-step device rollout splits over several streams of a handle (rmj_step_random)
@@ -283,6 +284,7 @@ struct rmj_logreplay {
     void* mem = nullptr;
     LogRun R{};
     double* d_powers = nullptr;
+    uint8_t* d_hid = nullptr;          // RMJ_LOGREPLAY_HIDDEN: [capacity][HID_SLOT_BYTES] hidden records, an allocation of its own (rmj_hidden.hip.h)
     uint32_t n_powers = 0;
     uint32_t steps = 0, step = 0;      // steps of a whole replay (the longest slot's events), steps taken
     std::vector<uint32_t> slot_first, slot_logs;
@@ -1928,6 +1930,41 @@ int rmj_step_sample_encode_batch_device(rmj_handle h, const float* d_logits, uin
     HIPCHK(hipGetLastError());
     return RMJ_OK;
 }
+
+// ---- hidden-hand targets (rmj_hidden.hip.h) ----------------------------------------------------------------------
+int rmj_hidden_targets_device(rmj_handle h, const int32_t* d_index, uint32_t rows, const uint32_t* d_count, const RmjHiddenOut* out) {
+    if (!h || !out) return fail(RMJ_ERR_ARG, "null argument");
+    if (!rows) return RMJ_OK;
+    if (!d_index || !out->d_opp_hand || !out->d_opp_shanten || !out->d_opp_waits || !out->d_opp_flags) return fail(RMJ_ERR_ARG, "null argument");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    hipLaunchKernelGGL(k_hidden_targets, dim3((rows + 3u) / 4u), dim3(256), 0, h->stream, h->d, d_index, rows, d_count, *out);
+    HIPCHK(hipGetLastError());
+    return RMJ_OK;
+}
+int rmj_hidden_targets(rmj_handle h, const int32_t* index, uint32_t rows, const RmjHiddenOut* out) {
+    if (!h || !out) return fail(RMJ_ERR_ARG, "null argument");
+    if (!rows) return RMJ_OK;
+    if (!index || !out->d_opp_hand || !out->d_opp_shanten || !out->d_opp_waits || !out->d_opp_flags) return fail(RMJ_ERR_ARG, "null argument");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    // the index and the four arrays at 256-byte steps of the handle's scratch
+    const size_t sz[5] = {(size_t)rows * 4, (size_t)rows * 24, (size_t)rows * 102, (size_t)rows * 3, (size_t)rows * 3};
+    size_t off[6] = {0};
+    for (int i = 0; i < 5; i++) off[i + 1] = off[i] + ((sz[i] + 255) & ~(size_t)255);
+    void* sp;
+    int rc = scratch_for(h, off[5], &sp);
+    if (rc) return rc;
+    char* b = (char*)sp;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(b, index, sz[0], hipMemcpyHostToDevice));
+    const RmjHiddenOut d{(uint8_t*)(b + off[2]), (int8_t*)(b + off[4]), (uint64_t*)(b + off[1]), (uint8_t*)(b + off[3])};
+    if ((rc = rmj_hidden_targets_device(h, (const int32_t*)b, rows, nullptr, &d))) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(out->d_opp_waits, b + off[1], sz[1], hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out->d_opp_hand, b + off[2], sz[2], hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out->d_opp_flags, b + off[3], sz[3], hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out->d_opp_shanten, b + off[4], sz[4], hipMemcpyDeviceToHost));
+    return RMJ_OK;
+}
 // ---- PPO transition collector (rmj_ppo.hip.h) ------------------------------------------------------------------
 static int ppo_clear_impl(rmj_ppo* p) {
     rmj_env* h = p->env;
@@ -2342,7 +2379,7 @@ int rmj_logreplay_create(rmj_handle h, rmj_logset_handle set, const RmjLogReplay
     if (set->device != h->cfg.device) return fail(RMJ_ERR_ARG, "rmj_logreplay_create: the log set lives on another device");
     const uint32_t n = h->cfg.n_games;
     if (n > set->M) return fail(RMJ_ERR_ARG, "rmj_logreplay_create: more slots (the handle's games) than logs: n_slots <= M");
-    if (cfg->flags & ~(uint32_t)(RMJ_LOGREPLAY_INCLUDE_PASS | RMJ_LOGREPLAY_SKIP_SINGLE_ACTION)) return fail(RMJ_ERR_ARG, "rmj_logreplay_create: unknown flag");
+    if (cfg->flags & ~(uint32_t)(RMJ_LOGREPLAY_INCLUDE_PASS | RMJ_LOGREPLAY_SKIP_SINGLE_ACTION | RMJ_LOGREPLAY_HIDDEN)) return fail(RMJ_ERR_ARG, "rmj_logreplay_create: unknown flag");
     uint32_t ch, w, rs;
     float dummy;
     RmjObsBatch b{};
@@ -2391,6 +2428,12 @@ int rmj_logreplay_create(rmj_handle h, rmj_logset_handle set, const RmjLogReplay
         delete r;
         return fail(RMJ_ERR_HIP, "rmj_logreplay_create: no device memory for a pool of " + std::to_string(off >> 20) + " MiB (capacity x row bytes: choose a smaller capacity)");
     }
+    if ((cfg->flags & RMJ_LOGREPLAY_HIDDEN) && hipMalloc(&r->d_hid, (size_t)cap * HID_SLOT_BYTES) != hipSuccess) {
+        (void)hipGetLastError();
+        hipFree(r->mem);
+        delete r;
+        return fail(RMJ_ERR_HIP, "rmj_logreplay_create: no device memory for the hidden records (capacity x 152 bytes: choose a smaller capacity)");
+    }
     uint8_t* m = (uint8_t*)r->mem;
     R.feat = (float*)(m + o_feat); R.packed = (uint64_t*)(m + o_packed); R.ret64 = (double*)(m + o_ret64); R.dec_action = (uint64_t*)(m + o_dact);
     r->d_powers = (double*)(m + o_powers);
@@ -2403,7 +2446,8 @@ int rmj_logreplay_create(rmj_handle h, rmj_logset_handle set, const RmjLogReplay
     R.log_status = m + o_status; R.traj_broken = m + o_broken;
     h->logreplay.push_back(r);
     // everything behind the feature rows starts as zeros (the views show defined values in slots that were never filled)
-    if (hipMemsetAsync(m + o_packed, 0, off - o_packed, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
+    if (hipMemsetAsync(m + o_packed, 0, off - o_packed, h->stream) != hipSuccess ||
+        (r->d_hid && hipMemsetAsync(r->d_hid, 0, (size_t)cap * HID_SLOT_BYTES, h->stream) != hipSuccess) || hipStreamSynchronize(h->stream) != hipSuccess ||
         hipMemcpy(m + o_sfirst, r->slot_first.data(), (size_t)(n + 1) * 4, hipMemcpyHostToDevice) != hipSuccess ||
         (M && hipMemcpy(m + o_slogs, r->slot_logs.data(), (size_t)M * 4, hipMemcpyHostToDevice) != hipSuccess) ||
         hipMemcpy(r->d_powers, pw.data(), (size_t)r->n_powers * 8, hipMemcpyHostToDevice) != hipSuccess || (rc = logreplay_clear_impl(r))) {
@@ -2421,6 +2465,7 @@ int rmj_logreplay_destroy(rmj_logreplay_handle r) {
     for (size_t i = 0; i < h->logreplay.size(); i++)
         if (h->logreplay[i] == r) { h->logreplay.erase(h->logreplay.begin() + i); break; }
     hipFree(r->mem);
+    if (r->d_hid) hipFree(r->d_hid);
     delete r;
     return RMJ_OK;
 }
@@ -2449,6 +2494,7 @@ int rmj_logreplay_run_device(rmj_logreplay_handle r, uint32_t n_steps, uint32_t*
         else if (feat == RMJ_FEATURES_DISCARD_SHANTEN) RMJ_LAUNCH_RECORD(false, RMJ_FEATURES_DISCARD_SHANTEN);
         else RMJ_LAUNCH_RECORD(false, RMJ_FEATURES_BASE);
 #undef RMJ_LAUNCH_RECORD
+        if (r->d_hid) hipLaunchKernelGGL(k_log_hidden, dim3(n * 4), dim3(64), 0, h->stream, h->d, R, r->d_hid);   // the state is still the one the rows were encoded from
         if (sanma) hipLaunchKernelGGL(rmj3::k_log_apply, game_grid(n), dim3(256), 0, h->stream, (const Env*)h->d_env, R.ev, (const uint32_t*)R.apply_at);
         else hipLaunchKernelGGL(rmj4::k_log_apply, game_grid(n), dim3(256), 0, h->stream, (const Env*)h->d_env, R.ev, (const uint32_t*)R.apply_at);
     }
@@ -2480,6 +2526,24 @@ int rmj_logreplay_emit_device(rmj_logreplay_handle r, const RmjLogBatch* out) {
     hipLaunchKernelGGL(k_log_emit_scan, dim3((cap + PPO_SCAN_BLOCK - 1) / PPO_SCAN_BLOCK), dim3(PPO_SCAN_BLOCK), 0, h->stream, r->R);
     hipLaunchKernelGGL(k_log_emit, ppo_wave_grid(cap), dim3(256), 0, h->stream, r->R, O);
     HIPCHK(hipGetLastError());
+    return RMJ_OK;
+}
+int rmj_logreplay_emit_hidden_device(rmj_logreplay_handle r, const RmjLogHiddenBatch* out) {
+    if (!r || !out) return fail(RMJ_ERR_ARG, "null argument");
+    if (!r->d_hid) return fail(RMJ_ERR_ARG, "rmj_logreplay_emit_hidden_device: the builder was made without RMJ_LOGREPLAY_HIDDEN");
+    if (out->rows && (!out->d_opp_hand || !out->d_opp_shanten || !out->d_opp_waits || !out->d_opp_flags || !out->d_event)) return fail(RMJ_ERR_ARG, "null argument");
+    rmj_env* h = r->env;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const uint32_t cap = r->R.capacity;
+    LogHiddenOut O{RmjHiddenOut{out->d_opp_hand, out->d_opp_shanten, out->d_opp_waits, out->d_opp_flags}, out->d_event, out->rows};
+    hipLaunchKernelGGL(k_log_emit_scan, dim3((cap + PPO_SCAN_BLOCK - 1) / PPO_SCAN_BLOCK), dim3(PPO_SCAN_BLOCK), 0, h->stream, r->R);
+    hipLaunchKernelGGL(k_log_emit_hidden, ppo_wave_grid(cap), dim3(256), 0, h->stream, r->R, (const uint8_t*)r->d_hid, O);
+    HIPCHK(hipGetLastError());
+    return RMJ_OK;
+}
+int rmj_logreplay_hidden_views(rmj_logreplay_handle r, RmjLogHiddenViews* out) {
+    if (!r || !out) return fail(RMJ_ERR_ARG, "null argument");
+    *out = RmjLogHiddenViews{r->R.capacity, HID_SLOT_BYTES, r->d_hid};
     return RMJ_OK;
 }
 int rmj_logreplay_views(rmj_logreplay_handle r, RmjLogReplayViews* out) {
@@ -2522,7 +2586,7 @@ int rmj_logcheck_create(rmj_handle h, rmj_logset_handle set, uint32_t n_slots, u
     c->steps = lr_assign(set->off.data(), M, n, nullptr, slot_logs.data(), slot_first.data());
     for (uint32_t s = 0; s < n; s++) {
         pos[s] = slot_first[s];
-        cur[s] = set->off[slot_logs[pos[s]]];   // (n <= M: every slot has a log)
+        cur[s] = pos[s] < slot_first[s + 1] ? set->off[slot_logs[pos[s]]] : 0u;   // (a slot may be left without a log: a log of no events keeps its slot free for the next one)
     }
     const bool sanma = h->cfg.game_mode >= 3;
     LogCheck& R = c->R;

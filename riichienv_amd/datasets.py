@@ -20,7 +20,7 @@ failure the builder detects is a decision that matches nothing in the list its a
 another way (a decision by a seat that is not to act) is applied like apply_events applies it and the log counts as complete.  For logs
 of unknown quality call validate() first (LogSet.validate, logcheck.py): a checking replay that gives every log a verdict.
 
-Memory: the pool is capacity x (C x W x 4 + A + 52) bytes, and samples() holds a second copy of what it emits (fill x the same row) until
+Memory: the pool is capacity x (C x W x 4 + A + 52) bytes (+ 152 with hidden=True), and samples() holds a second copy of what it emits (fill x the same row) until
 the next run() / finalize() / clear() - at the default capacity about three times the samples' own size in all.  What does not fit is counted (`counts()["overflowed"]`) and the trajectory that lost a
 sample is not emitted; a log in which a decision matches no legal action is dropped whole (`counts()["failed_logs"]`), like a file whose
 replay raises in MCDataset."""
@@ -87,6 +87,10 @@ class LogSampleBuilder:
     twice the logs' decision events - is a heuristic, not a bound: a discard can add a Pass sample for up to three seats, and those are
     not counted.  Check counts()["overflowed"] after run(); it is 0 on every log set of the tests.  rule=None: "tenhou" (default) or
     "mjsoul".  gamma=0.99, include_pass=True, skip_single_action=True, share_stream=True, kyoku_scale=1 / 1000.
+    hidden=False: with True every sample also carries what its seat could not see - samples() gains "opp_hand" [N, 3, 34] u8, "opp_shanten"
+    [N, 3] i8, "opp_waits" [N, 3] i64, "opp_flags" [N, 3] u8 (the rows of TorchVecEnv.hidden_compact: the opponents (seat + 1 + r) mod NP
+    at the moment of the decision) and "event" [N] i32, the index in the log of the event the decision precedes; 152 more bytes per pool
+    slot.  ValueError over a log set made with masked_ok=True: "?" tiles make those targets meaningless.
     rewards: finalize(rewards) takes a float64 [K, 4] table by kyoku row (`kyoku_offsets[log] + kyoku - 1`; the GRP reward model's
     output) - default: the seat's score change of the kyoku times kyoku_scale.
     on_error (text): "raise" or "drop" as LogSet takes them; after a drop the `log` field of the samples counts set logs (`log_ids`)."""
@@ -121,7 +125,7 @@ class LogSampleBuilder:
         return self._attach(LogSet.from_device_text(text, offsets, self.n_players, masked_ok, device, on_error), True)
 
     def _settings(self, game_mode, on_error="raise", features="base", n_slots=None, capacity=None, gamma=0.99, include_pass=True, skip_single_action=True,
-                  rule=None, share_stream=True, kyoku_scale=1.0 / 1000.0):
+                  rule=None, share_stream=True, kyoku_scale=1.0 / 1000.0, hidden=False):
         """validates and stores what every constructor shares (no device work)"""
         import torch
 
@@ -142,7 +146,7 @@ class LogSampleBuilder:
         self.n_slots, self.capacity = n_slots, capacity
         self.gamma, self.kyoku_scale = float(gamma), float(kyoku_scale)
         self.include_pass, self.skip_single_action = bool(include_pass), bool(skip_single_action)
-        self.shared = bool(share_stream)
+        self.shared, self.hidden = bool(share_stream), bool(hidden)
         self._finalized = False
         self._emitted = None    # what samples() returned last, until run() / finalize() / clear()
         self.h = self.env = self.logset = None
@@ -165,6 +169,8 @@ class LogSampleBuilder:
         self.logset, self._owned = logset, owned
         try:
             assert self.n_players == logset.num_players, "the log set was made for another number of players"
+            if self.hidden and getattr(logset, "masked_ok", False):
+                raise ValueError("hidden=True over a log set made with masked_ok=True: the masked seats' tiles are unknown, so are their hands, shanten and waits")
             for k in ("logs", "M", "device", "kyoku_offsets", "n_kyokus", "log_ids", "dropped", "lengths"):
                 setattr(self, k, getattr(logset, k))
             self.host_seconds = dict(logset.host_seconds)
@@ -178,7 +184,8 @@ class LogSampleBuilder:
             if self.shared:
                 vecenv._chk(L.rmj_set_stream(self.env.h, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream), 0))
             self._powers = gamma_powers(self.gamma, logset.longest_log + 1)
-            flags = (abi.LOGREPLAY_INCLUDE_PASS if self.include_pass else 0) | (abi.LOGREPLAY_SKIP_SINGLE_ACTION if self.skip_single_action else 0)
+            flags = (abi.LOGREPLAY_INCLUDE_PASS if self.include_pass else 0) | (abi.LOGREPLAY_SKIP_SINGLE_ACTION if self.skip_single_action else 0) | \
+                (abi.LOGREPLAY_HIDDEN if self.hidden else 0)
             cfg = abi.LogReplayConfig(self._feat, self.capacity, flags, len(self._powers), self.gamma, self._powers.ctypes.data)
             h = C.c_void_p()
             vecenv._chk(L.rmj_logreplay_create(self.env.h, logset.handle, C.byref(cfg), C.byref(h)))
@@ -195,6 +202,10 @@ class LogSampleBuilder:
                          "kyoku": wrap(v.kyoku, (cap,), "<i4"), "seat": wrap(v.seat, (cap,), "<i4"), "t": wrap(v.t, (cap,), "<i4"),
                          "log_status": wrap(v.log_status, (self.M,), "|u1"), "traj_len": wrap(v.traj_len, (K, 4), "<i4"),
                          "traj_broken": wrap(v.traj_broken, (K, 4), "|u1"), "counters": wrap(v.counters, (6,), "<i4")}
+            if self.hidden:   # the records as they lie: [capacity, 152] bytes (header: RmjLogHiddenViews)
+                hv = abi.LogHiddenViews()
+                vecenv._chk(L.rmj_logreplay_hidden_views(self.h, C.byref(hv)))
+                self.pool["hidden"] = wrap(hv.records, (cap, hv.record_bytes), "|u1")
             self._sync()
         except Exception:
             self.close()
@@ -303,6 +314,13 @@ class LogSampleBuilder:
 
     def _empty(self, k):
         t, d = self.torch, self.device
+        hid = {"opp_hand": t.empty((k, 3, 34), dtype=t.uint8, device=d), "opp_shanten": t.empty((k, 3), dtype=t.int8, device=d),
+               "opp_waits": t.empty((k, 3), dtype=t.int64, device=d), "opp_flags": t.empty((k, 3), dtype=t.uint8, device=d),
+               "event": t.empty((k,), dtype=t.int32, device=d)} if self.hidden else {}
+        return {**self._empty_plain(k), **hid}
+
+    def _empty_plain(self, k):
+        t, d = self.torch, self.device
         return {"features": t.empty((k, self.channels, self.width), dtype=t.float32, device=d), "mask": t.empty((k, self.A), dtype=t.uint8, device=d),
                 "action": t.empty((k,), dtype=t.int64, device=d), "packed": t.empty((k,), dtype=t.int64, device=d),
                 "return": t.empty((k,), dtype=t.float32, device=d), "return64": t.empty((k,), dtype=t.float64, device=d),
@@ -311,7 +329,8 @@ class LogSampleBuilder:
 
     def samples(self):
         """The dataset: {"features" [N, C, W] f32, "action" [N] i64, "return" [N] f32, "return64" [N] f64, "mask" [N, A] u8, "rank" [N] i64,
-        "packed" [N] i64 (the packed action's bits), "log", "kyoku", "seat", "t" [N] i32} on the device, in pool order - the samples of the
+        "packed" [N] i64 (the packed action's bits), "log", "kyoku", "seat", "t" [N] i32} - with hidden=True also "opp_hand", "opp_shanten",
+        "opp_waits", "opp_flags" and "event" (class docstring), same rows, same order - on the device, in pool order - the samples of the
         logs replayed to their end, without the trajectories that lost a sample to a full pool (rmj_logreplay_emit_device).  Finalizes with
         the default rewards if finalize() was not called since the last run.  Reads the pool's fill on the host to size the tensors.  The
         result is kept (and returned again, the same tensors) until run(), finalize() or clear()."""
@@ -330,6 +349,10 @@ class LogSampleBuilder:
                          out["t"].data_ptr(), cnt.data_ptr(), rows, 0)
         self._pre()
         vecenv._chk(self.L.rmj_logreplay_emit_device(self.h, C.byref(b)))
+        if self.hidden:
+            hb = abi.LogHiddenBatch(out["opp_hand"].data_ptr(), out["opp_shanten"].data_ptr(), out["opp_waits"].data_ptr(), out["opp_flags"].data_ptr(),
+                                    out["event"].data_ptr(), rows, 0)
+            vecenv._chk(self.L.rmj_logreplay_emit_hidden_device(self.h, C.byref(hb)))
         self._sync()
         k = int(cnt[0])
         self._emitted = {name: v[:k] for name, v in out.items()}

@@ -162,6 +162,7 @@ class LogSet:
         self.torch, self.L, self.handle = torch, vecenv.load_lib(), None
         self.device_index, self.device, self.num_players = int(device), torch.device("cuda", int(device)), int(num_players)
         self.owns_tables = bool(owns_tables)      # parsed from text: the score tables and the per-log status live in the set
+        self.masked_ok = False                    # made with masked_ok=True: "?" tiles were read as tile 0 - the hidden seats' state is then garbage
         self.logs, self.log_ids, self.dropped = None, np.arange(n_logs, dtype=np.int64), []
         self.M, self.n_events, self.n_kyokus, self.longest_log = int(n_logs), 0, 0, 0
         self.kyoku_offsets = np.zeros(self.M + 1, dtype=np.uint32)
@@ -180,7 +181,7 @@ class LogSet:
         t0 = time.perf_counter()
         logs = [_events_of(l) for l in logs]
         self = cls(device, num_players, False, len(logs))
-        self.logs = logs
+        self.logs, self.masked_ok = logs, bool(masked_ok)
         t1 = time.perf_counter()
         self.start_scores, self.end_scores = kyoku_tables(logs, self.num_players)
         self.host_seconds = {"kyoku_tables": time.perf_counter() - t1}   # the one-off host work of the constructor, for cost reports
@@ -225,6 +226,7 @@ class LogSet:
         """rmj_logset_create_from_text over (text, rng) - numpy arrays on the host or torch tensors on the device - then the one status read"""
         n_logs, host = len(rng), isinstance(rng, np.ndarray)
         self = cls(device, num_players, True, n_logs)
+        self.masked_ok = bool(masked_ok)
         L, torch = self.L, self.torch
         flags = (abi.LOGTEXT_MASKED_OK if masked_ok else 0) | (0 if host else abi.LOGTEXT_ON_DEVICE)
 

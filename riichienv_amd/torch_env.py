@@ -156,6 +156,28 @@ class TorchVecEnv:
         self.sync()
         return self._compact_result(sync_count)
 
+    def hidden_compact(self, index, count=None, out=None):
+        """What the observation hides from the rows of a compact batch: index [k] int32 = game * 4 + seat as obs_compact returns it (or
+        any other seats, acting or not) -> {"opp_hand" uint8 [k, 3, 34], "opp_shanten" int8 [k, 3], "opp_waits" int64 [k, 3] (bit t =
+        tile type t), "opp_flags" uint8 [k, 3] (abi.HIDDEN_* bits, n_melds << 4)} on the device, for the opponents (seat + 1 + r) mod NP
+        (rmj_hidden_targets_device; 3P: the third opponent is zeros).  count: the device count tensor of obs_compact(sync_count=False) -
+        rows at or behind it are left as they were; out: the dict of an earlier call to write into (no allocation)."""
+        t = self.torch
+        idx = index.to(device=self.device, dtype=t.int32).contiguous().reshape(-1)
+        k = int(idx.shape[0])
+        if out is None:
+            out = {"opp_hand": t.zeros((k, 3, 34), dtype=t.uint8, device=self.device), "opp_shanten": t.zeros((k, 3), dtype=t.int8, device=self.device),
+                   "opp_waits": t.zeros((k, 3), dtype=t.int64, device=self.device), "opp_flags": t.zeros((k, 3), dtype=t.uint8, device=self.device)}
+        assert all(out[f].shape[0] >= k and out[f].is_contiguous() for f in ("opp_hand", "opp_shanten", "opp_waits", "opp_flags")), "out is too small for the index"
+        if k:
+            if not self.shared:
+                t.cuda.current_stream(self.device).synchronize()   # the buffers were made on torch's stream
+            b = abi.HiddenOut(*(out[f].data_ptr() for f in ("opp_hand", "opp_shanten", "opp_waits", "opp_flags")))
+            vecenv._chk(self.env.L.rmj_hidden_targets_device(self.env.h, C.c_void_p(idx.data_ptr()), k, None if count is None else C.c_void_p(count.data_ptr()),
+                                                             C.byref(b)))
+            self.sync()
+        return out
+
     def scores(self):
         vecenv._chk(self.env.L.rmj_scores_device(self.env.h, C.c_void_p(self._scores.data_ptr()), None))
         self.sync()

@@ -342,6 +342,20 @@ class VecRiichiEnv:
             cap_r, cap_e = max(cap_r, nr.value + nr.value // 8), max(cap_e, ne.value + ne.value // 8)
             self._lc_buf = None
 
+    def hidden_targets(self, index):
+        """What the observation hides from the seats `index` [k] = game * 4 + seat (any seat, acting or not - e.g. legal_compact()'s
+        index): {"opp_hand" uint8 [k, 3, 34], "opp_shanten" int8 [k, 3], "opp_waits" int64 [k, 3] (bit t = tile type t), "opp_flags"
+        uint8 [k, 3] (abi.HIDDEN_* bits, n_melds << 4)} of the opponents (seat + 1 + r) mod NP, r = 0, 1, 2 - rmj_hidden_targets (header).
+        In 3P the third opponent is absent: zeros."""
+        idx = np.ascontiguousarray(index, dtype=np.int32).reshape(-1)
+        k = int(idx.size)
+        out = {"opp_hand": np.zeros((k, 3, 34), np.uint8), "opp_shanten": np.zeros((k, 3), np.int8), "opp_waits": np.zeros((k, 3), np.int64),
+               "opp_flags": np.zeros((k, 3), np.uint8)}
+        if k:
+            b = abi.HiddenOut(*(out[f].ctypes.data for f in ("opp_hand", "opp_shanten", "opp_waits", "opp_flags")))
+            _chk(self.L.rmj_hidden_targets(self.h, idx.ctypes.data, k, C.byref(b)))
+        return out
+
     def mask(self):
         m = np.zeros((self.n, 4, 82), np.uint8)
         _chk(self.L.rmj_get_mask(self.h, m.ctypes.data))
