@@ -7,6 +7,7 @@
 // (block b runs on XCD b % 8) and its 640-byte record is re-read from that XCD's L2 / MALL.
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -78,6 +79,36 @@ static int fail(int code, const std::string& msg) {
         if (e_ != hipSuccess) return fail(RMJ_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
+// A buffer a handle grows on demand: need() leaves room for `bytes` bytes, by free-then-allocate when it is short.  Device memory is
+// freed only after the stream `st` has drained (work queued there may still read it); pinned host memory is freed at once.
+// headroom: a grown buffer gets bytes + bytes / 8 + 1 MiB, so that the next call of a similar size fits; always: allocated on first
+// use even for 0 bytes (a non-null pointer for the kernels).  The members of rmj_env state which buffer has which rule.
+struct Grown {
+    enum Kind { DEVICE, PINNED };
+    Kind kind;
+    bool headroom = false, always = false;
+    void* p = nullptr;
+    size_t cap = 0;
+    Grown(Kind k, bool headroom_ = false, bool always_ = false) : kind(k), headroom(headroom_), always(always_) {}
+    hipError_t need(size_t bytes, hipStream_t st = nullptr) {   // st: device memory only
+        if (bytes <= cap && (p || !always)) return hipSuccess;
+        if (kind == DEVICE) {
+            hipError_t e = hipStreamSynchronize(st);
+            if (e != hipSuccess) return e;
+        }
+        release();
+        const size_t want = headroom ? bytes + bytes / 8 + ((size_t)1 << 20) : bytes;
+        hipError_t e = kind == DEVICE ? hipMalloc(&p, want) : hipHostMalloc(&p, want, hipHostMallocDefault);
+        if (e == hipSuccess) cap = want;
+        return e;
+    }
+    void release() {
+        if (p) kind == DEVICE ? (void)hipFree(p) : (void)hipHostFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+};
+
 struct rmj_env {
     RmjConfig cfg;
     Env d;
@@ -95,8 +126,7 @@ struct rmj_env {
     uint32_t* d_obs_offs = nullptr;    // [n_games] + [blocks] slots of the compact observation batch (rmj_encode_compact_device)
     uint32_t ring = 0;
     float* d_decay = nullptr;  // expf(-0.2f * age), age 0..31, computed on the host (encode_extended)
-    void* d_scratch = nullptr; // staging buffer of the host-copy entry points (grown on demand, never per call)
-    size_t scratch_bytes = 0;
+    Grown scratch{Grown::DEVICE};   // staging buffer of the host-copy entry points (grown on demand to the exact size, never per call): scratch_for
     int want_streams = 4;      // parts a multi-step device rollout is cut into (rmj_set_rollout_streams; RMJ_STEP_STREAMS at create)
     int quad = 2;              // device-policy steps: 0 = one game per wave (k_step), 1 = four games per wave (k_step4), 2 = and a
                                // rollout of >= 2 steps is ONE launch in which every wave steps its own games (k_step4<true>); RMJ_STEP4 at create
@@ -119,40 +149,35 @@ struct rmj_env {
     std::vector<struct rmj_ppo*> ppo;   // transition collectors bound to this handle (rmj_ppo_create): destroyed with it
     std::vector<struct rmj_logreplay*> logreplay;   // log sample builders bound to this handle (rmj_logreplay_create): destroyed with it
     void* d_track = nullptr;        // round tracker (rmj_round_track_device): hand index / scores / meta where every game's round began
-    // staging of rmj_drain_format's size call (the records sit in h_pin): reused by the call that brings the text buffer
+    // staging of rmj_drain_format's size call (the records sit in `pin`): reused by the call that brings the text buffer
     bool stage_valid = false;
     int stage_seat = 0;
     uint32_t stage_events = 0;
     double stage_ms[2] = {0, 0};
     std::vector<uint32_t> stage_cursor;
-    void* h_pin = nullptr;          // pinned host staging of the host-buffer entry points (rmj_get_legal_compact, rmj_drain_*), grown on demand
-    size_t pin_bytes = 0;
-    // buffers of the text calls (rmj_drain_text / rmj_format_events_device): what the last call's RmjTextView points at, grown on demand
-    char* d_txt = nullptr;          // device text
-    uint64_t txt_cap = 0;
-    uint64_t* d_txt_offs = nullptr; // device text offsets [games + 1]
-    size_t txt_offs_slots = 0;
-    void* d_txt_work = nullptr;     // sizes, stops and scan of the text calls
-    size_t txt_work_bytes = 0;
-    void* h_txt = nullptr;          // pinned text (host delivery)
-    uint64_t txt_pin_bytes = 0;
-    void* h_txt_offs = nullptr;     // pinned text offsets [games + 1], then the new cursors
-    size_t txt_pin_offs_bytes = 0;
+    Grown pin{Grown::PINNED};       // pinned host staging of the host-buffer entry points (rmj_get_legal_compact, rmj_drain_*), exact size; when it
+                                    // moves, the staged size call is gone (stage_valid = false): pin_for
+    // buffers of the text calls (rmj_drain_text / rmj_format_events_device): what the last call's RmjTextView points at
+    Grown txt{Grown::DEVICE, true, true};   // device text: headroom, and there from the first call on even when that call's text is empty
+    Grown txt_offs{Grown::DEVICE};  // device text offsets: [games + 1] slots of 8 bytes
+    Grown txt_work{Grown::DEVICE};  // sizes, stops and scan of the text calls (text_format_device lays it out)
+    Grown h_txt{Grown::PINNED, true};   // pinned text (host delivery): headroom
+    Grown h_txt_offs{Grown::PINNED};    // pinned text offsets [games + 1], then the new cursors
     int enc_fused = 1;              // RMJ_ENC_FUSED at create: the step + encode rollout as ONE launch (k_step4_enc / k_step4_queue_enc); 0 = parts on streams
     uint32_t q_slots_enc = 0;       // waves of k_step4_queue_enc the device holds at once
 };
 // device staging memory of at least `bytes` bytes, owned by the handle
 static int scratch_for(rmj_env* h, size_t bytes, void** out) {
-    if (bytes > h->scratch_bytes) {
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (h->d_scratch) hipFree(h->d_scratch);
-        h->d_scratch = nullptr;
-        h->scratch_bytes = 0;
-        HIPCHK(hipMalloc(&h->d_scratch, bytes));
-        h->scratch_bytes = bytes;
-    }
-    *out = h->d_scratch;
+    HIPCHK(h->scratch.need(bytes, h->stream));
+    *out = h->scratch.p;
     return RMJ_OK;
+}
+// the same, laid out: the arrays registered in `L` point into the scratch
+static int scratch_for(rmj_env* h, const rmjh::DevLayout& L) {
+    void* sp;
+    int rc = scratch_for(h, L.bytes(), &sp);
+    if (!rc) L.bind(sp);
+    return rc;
 }
 
 static int ensure_device(int device) {
@@ -163,6 +188,13 @@ static int ensure_device(int device) {
     return RMJ_OK;
 }
 static inline dim3 game_grid(uint32_t n) { return dim3((n + WPB - 1) / WPB); }
+// one launch of the handle's variant of KERNEL (rmj3:: for three players, rmj4:: for four) on its stream, the handle's device Env as the
+// first argument.  A macro, expanded in place: where a kernel is first named decides its place in the code object.
+#define RMJ_LAUNCH_MODE(h, KERNEL, grid, block, ...)                                                                                   \
+    do {                                                                                                                                \
+        if ((h)->cfg.game_mode >= 3) hipLaunchKernelGGL(rmj3::KERNEL, grid, block, 0, (h)->stream, (const Env*)(h)->d_env, __VA_ARGS__); \
+        else hipLaunchKernelGGL(rmj4::KERNEL, grid, block, 0, (h)->stream, (const Env*)(h)->d_env, __VA_ARGS__);                         \
+    } while (0)
 
 // Temporary device buffers (and timing events) of one entry point: released on EVERY return path, so that an error
 // in the middle of a call (HIPCHK returns at once) strands nothing on the device.
@@ -213,20 +245,19 @@ static int fill_and_fetch(rmj_env* h, void* out, size_t bytes, Fill fill) {
 template <class Buffers, class Twin>
 static int encode_seq_host(rmj_env* h, int game_style, const Buffers* out, const size_t (&sz)[7], Twin twin) {
     HIPCHK(hipSetDevice(h->cfg.device));
-    size_t off[8] = {0};
-    for (int i = 0; i < 7; i++) off[i + 1] = off[i] + ((sz[i] + 255) & ~(size_t)255);
-    void* sp;
-    int rc = scratch_for(h, off[7], &sp);
+    Buffers d{};
+    rmjh::DevLayout L;
+    L.add(&d.sparse, sz[0]); L.add(&d.n_sparse, sz[1]); L.add(&d.numeric, sz[2]); L.add(&d.progression, sz[3]); L.add(&d.n_progression, sz[4]);
+    L.add(&d.candidates, sz[5]); L.add(&d.n_candidates, sz[6]);
+    int rc = scratch_for(h, L);
     if (rc) return rc;
-    char* b = (char*)sp;
-    Buffers d{(uint16_t*)(b + off[0]), (uint8_t*)(b + off[1]), (float*)(b + off[2]), (uint16_t*)(b + off[3]), (uint16_t*)(b + off[4]),
-              (uint16_t*)(b + off[5]), (uint8_t*)(b + off[6])};
     if ((rc = twin(h, game_style, &d))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
     void* dst[7] = {out->sparse, out->n_sparse, out->numeric, out->progression, out->n_progression, out->candidates, out->n_candidates};
+    const void* src[7] = {d.sparse, d.n_sparse, d.numeric, d.progression, d.n_progression, d.candidates, d.n_candidates};
     for (int i = 0; i < 7; i++) {
         if (!dst[i]) return fail(RMJ_ERR_ARG, "null output array");
-        HIPCHK(hipMemcpy(dst[i], b + off[i], sz[i], hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(dst[i], src[i], sz[i], hipMemcpyDeviceToHost));
     }
     return RMJ_OK;
 }
@@ -286,8 +317,7 @@ struct rmj_logreplay {
     double* d_powers = nullptr;
     uint8_t* d_hid = nullptr;          // RMJ_LOGREPLAY_HIDDEN: [capacity][HID_SLOT_BYTES] hidden records, an allocation of its own (rmj_hidden.hip.h)
     uint32_t n_powers = 0;
-    uint32_t steps = 0, step = 0;      // steps of a whole replay (the longest slot's events), steps taken
-    std::vector<uint32_t> slot_first, slot_logs;
+    rmjh::SlotChain chain;             // which slot replays which logs, the steps of a whole replay and the steps taken
 };
 // a checking replay bound to a handle and a log set (rmj_logcheck_create): its verdicts and bookkeeping are one device allocation
 struct rmj_logcheck {
@@ -295,8 +325,21 @@ struct rmj_logcheck {
     rmj_logset* set = nullptr;
     void* mem = nullptr;
     LogCheck R{};
-    uint32_t steps = 0, step = 0;
+    rmjh::SlotChain chain;
 };
+// the assignment of a replay on the device: slot_first [n + 1], slot_logs [M]
+static hipError_t upload_chain(const rmjh::SlotChain& c, uint32_t M, const uint32_t* d_first, const uint32_t* d_logs) {
+    hipError_t e = hipMemcpy((void*)d_first, c.slot_first.data(), c.slot_first.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && M) e = hipMemcpy((void*)d_logs, c.slot_logs.data(), (size_t)M * 4, hipMemcpyHostToDevice);
+    return e;
+}
+// where every slot of a replay starts, on the device (the stream has drained: the copies are not ordered behind it)
+static hipError_t upload_start_cursors(const rmjh::SlotChain& c, const rmj_logset* set, uint32_t n, uint32_t* d_pos, uint32_t* d_cur) {
+    std::vector<uint32_t> pos(n), cur(n);
+    c.start_cursors(set->off.data(), pos.data(), cur.data());
+    hipError_t e = hipMemcpy(d_pos, pos.data(), (size_t)n * 4, hipMemcpyHostToDevice);
+    return e != hipSuccess ? e : hipMemcpy(d_cur, cur.data(), (size_t)n * 4, hipMemcpyHostToDevice);
+}
 // the shanten tables on a device, uploaded once (rmj_create: the handle's Env; the hand API)
 static int shanten_tables_for(int device, ShantenTables* out) {
     static ShantenTables cache[64];
@@ -328,6 +371,17 @@ static int shanten_tables_for(int device, ShantenTables* out) {
     }
     *out = cache[device];
     return RMJ_OK;
+}
+// The slabs of a handle's Env, each named once, in the order rmj_create allocates them: where the pointer lives, its bytes for B games
+// and an event ring of `ring` records, and when rmj_create zeroes it - NEVER (k_reset writes all of it), AT_ALLOC, or LATE (queued
+// behind the XCC probe).  create_impl, rmj_clone and rmj_destroy walk it.
+struct EnvSlab { void** p; size_t bytes; enum { NEVER, AT_ALLOC, LATE } zero; };
+static std::array<EnvSlab, 10> env_slabs(Env& d, size_t B = 0, size_t ring = 0) {   // (no sizes: for the pointers alone)
+    return {{{(void**)&d.core, B * sizeof(GState), EnvSlab::NEVER}, {(void**)&d.wall, B * RMJ_WALL_STRIDE, EnvSlab::NEVER},
+             {(void**)&d.legal, B * 4 * RMJ_MAX_LEGAL * sizeof(uint64_t), EnvSlab::LATE}, {(void**)&d.nlegal, B * 4, EnvSlab::LATE},
+             {(void**)&d.mask, B * 4 * 82, EnvSlab::LATE}, {(void**)&d.waits, B * 4 * sizeof(uint64_t), EnvSlab::NEVER},
+             {(void**)&d.status, B * sizeof(uint32_t), EnvSlab::NEVER}, {(void**)&d.events, B * ring * sizeof(RmjEvent), EnvSlab::LATE},
+             {(void**)&d.win, B * 4 * sizeof(RmjWinResult), EnvSlab::AT_ALLOC}, {(void**)&d.wall_dg, B * 32, EnvSlab::AT_ALLOC}}};
 }
 // (defined in its section: ahead of rmj_step_random_encode it would put k_encode_base before the fused step kernels in the code object)
 static void launch_encode_base_range(rmj_env* h, hipStream_t st, int only_active, float* d_out, uint32_t g0, uint32_t g1);
@@ -368,18 +422,11 @@ static int create_impl(rmj_env* h, const RmjConfig* cfg, uint64_t** d_seeds_out)
     // the two events of rmj_time_rollout* / rmj_bench_rollout: here, not at their first use - the driver's timed region IS their first use, and two
     // hipEventCreate calls between its host timestamps cost the 20-step window ~4 % (round 6, scripts/r06_window_order.py: first window 1.65-1.69 G, later ones 1.76 G)
     for (int i = 0; i < 2; i++) HIPCHK(hipEventCreate(&h->ev_time[i]));
-    HIPCHK(hipMalloc(&d.core, B * sizeof(GState)));
-    HIPCHK(hipMalloc(&d.wall, B * RMJ_WALL_STRIDE));
-    HIPCHK(hipMalloc(&d.legal, B * 4 * RMJ_MAX_LEGAL * sizeof(uint64_t)));
-    HIPCHK(hipMalloc(&d.nlegal, B * 4));
-    HIPCHK(hipMalloc(&d.mask, B * 4 * 82));
-    HIPCHK(hipMalloc(&d.waits, B * 4 * sizeof(uint64_t)));
-    HIPCHK(hipMalloc(&d.status, B * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&d.events, B * (size_t)r2 * sizeof(RmjEvent)));
-    HIPCHK(hipMalloc(&d.win, B * 4 * sizeof(RmjWinResult)));
-    HIPCHK(hipMemsetAsync(d.win, 0, B * 4 * sizeof(RmjWinResult), h->stream));
-    HIPCHK(hipMalloc(&d.wall_dg, B * 32));
-    HIPCHK(hipMemsetAsync(d.wall_dg, 0, B * 32, h->stream));
+    const auto slabs = env_slabs(d, B, r2);
+    for (const EnvSlab& s : slabs) {
+        HIPCHK(hipMalloc(s.p, s.bytes));
+        if (s.zero == EnvSlab::AT_ALLOC) HIPCHK(hipMemsetAsync(*s.p, 0, s.bytes, h->stream));
+    }
     HIPCHK(hipMalloc(&h->d_actions, B * 4 * sizeof(uint64_t)));
     HIPCHK(hipMalloc(&h->d_counter, sizeof(unsigned long long)));
     {   // The ticket rollout (k_step4_queue) hands a quad from wave to wave through ONE XCD's L2 and keys its eight queues by
@@ -395,10 +442,8 @@ static int create_impl(rmj_env* h, const RmjConfig* cfg, uint64_t** d_seeds_out)
         h->max_xcc_id = (uint32_t)m;
     }
     HIPCHK(hipMalloc(&h->d_obs_offs, (B + (B + 1023) / 1024) * sizeof(uint32_t)));   // per game + per scan block
-    HIPCHK(hipMemsetAsync(d.legal, 0, B * 4 * RMJ_MAX_LEGAL * sizeof(uint64_t), h->stream));
-    HIPCHK(hipMemsetAsync(d.nlegal, 0, B * 4, h->stream));
-    HIPCHK(hipMemsetAsync(d.mask, 0, B * 4 * 82, h->stream));
-    HIPCHK(hipMemsetAsync(d.events, 0, B * (size_t)r2 * sizeof(RmjEvent), h->stream));
+    for (const EnvSlab& s : slabs)
+        if (s.zero == EnvSlab::LATE) HIPCHK(hipMemsetAsync(*s.p, 0, s.bytes, h->stream));
     d.ring_mask = r2 - 1;
     d.n_games = cfg->n_games;
     d.rule_bits = cfg->rule_bits;
@@ -427,8 +472,7 @@ static int create_impl(rmj_env* h, const RmjConfig* cfg, uint64_t** d_seeds_out)
         HIPCHK(hipMemcpy(*d_seeds_out, cfg->seeds, B * sizeof(uint64_t), hipMemcpyHostToDevice));
         A.seeds = *d_seeds_out;
     }
-    if (cfg->game_mode >= 3) hipLaunchKernelGGL(rmj3::k_reset, game_grid(cfg->n_games), dim3(256), 0, h->stream, (const Env*)h->d_env, A);
-    else hipLaunchKernelGGL(rmj4::k_reset, game_grid(cfg->n_games), dim3(256), 0, h->stream, (const Env*)h->d_env, A);
+    RMJ_LAUNCH_MODE(h, k_reset, game_grid(cfg->n_games), dim3(256), A);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
     return RMJ_OK;
@@ -459,15 +503,13 @@ int rmj_destroy(rmj_handle h) {
     if (!h) return RMJ_OK;
     hipSetDevice(h->cfg.device);
     if (h->stream) hipStreamSynchronize(h->stream);
-    if (h->h_pin) hipHostFree(h->h_pin);
-    hipFree(h->d.core); hipFree(h->d.wall); hipFree(h->d.wall_dg); hipFree(h->d.legal); hipFree(h->d.nlegal); hipFree(h->d_decay); if (h->d_scratch) hipFree(h->d_scratch); hipFree(h->d.mask);
-    hipFree(h->d.waits); hipFree(h->d.status); hipFree(h->d.events); hipFree(h->d.win); hipFree(h->d_actions); hipFree(h->d_counter); hipFree(h->d_obs_offs); hipFree(h->d_env); hipFree(h->d_qheads);   // (d_qdone lives in the same allocation)
-    hipFree(h->d_ev_lost); hipFree(h->d_track); hipFree(h->d_heavy);
+    for (const EnvSlab& s : env_slabs(h->d)) hipFree(*s.p);
+    for (void* p : {(void*)h->d_decay, (void*)h->d_actions, (void*)h->d_counter, (void*)h->d_obs_offs, (void*)h->d_env, (void*)h->d_qheads /* (and d_qdone behind it) */,
+                    (void*)h->d_ev_lost, h->d_track, h->d_heavy})
+        hipFree(p);
     while (!h->ppo.empty()) rmj_ppo_destroy(h->ppo.back());
     while (!h->logreplay.empty()) rmj_logreplay_destroy(h->logreplay.back());
-    hipFree(h->d_txt); hipFree(h->d_txt_offs); hipFree(h->d_txt_work);
-    if (h->h_txt) hipHostFree(h->h_txt);
-    if (h->h_txt_offs) hipHostFree(h->h_txt_offs);
+    for (Grown* g : {&h->scratch, &h->pin, &h->txt, &h->txt_offs, &h->txt_work, &h->h_txt, &h->h_txt_offs}) g->release();
     for (int i = 0; i < 2; i++) if (h->ev_time[i]) hipEventDestroy(h->ev_time[i]);
     if (h->own_stream) hipStreamDestroy(h->own_stream);
     for (int i = 0; i < RMJ_MAX_ROLLOUT_STREAMS - 1; i++) {
@@ -500,14 +542,9 @@ int rmj_clone(rmj_handle h, rmj_handle* out) {
     c->enc_fused = h->enc_fused;
     if (h->d.enc_stride != c->d.enc_stride) { int rc2 = rmj_set_encode_row_stride(c, h->d.enc_stride); if (rc2) { rmj_destroy(c); return rc2; } }
     const size_t B = h->cfg.n_games, ring = (size_t)h->d.ring_mask + 1u;
-    const struct { void* dst; const void* src; size_t bytes; } slabs[] = {
-        {c->d.core, h->d.core, B * sizeof(GState)}, {c->d.wall, h->d.wall, B * RMJ_WALL_STRIDE},
-        {c->d.legal, h->d.legal, B * 4 * RMJ_MAX_LEGAL * sizeof(uint64_t)}, {c->d.nlegal, h->d.nlegal, B * 4}, {c->d.mask, h->d.mask, B * 4 * 82},
-        {c->d.waits, h->d.waits, B * 4 * sizeof(uint64_t)}, {c->d.status, h->d.status, B * sizeof(uint32_t)},
-        {c->d.events, h->d.events, B * ring * sizeof(RmjEvent)}, {c->d.win, h->d.win, B * 4 * sizeof(RmjWinResult)},
-        {c->d.wall_dg, h->d.wall_dg, B * 32}};
-    for (const auto& s : slabs) {
-        if (hipMemcpyAsync(s.dst, s.src, s.bytes, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) {
+    const auto from = env_slabs(h->d, B, ring), to = env_slabs(c->d, B, ring);
+    for (size_t i = 0; i < from.size(); i++) {
+        if (hipMemcpyAsync(*to[i].p, *from[i].p, from[i].bytes, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) {
             rmj_destroy(c);
             return fail(RMJ_ERR_HIP, "rmj_clone: device copy failed");
         }
@@ -533,8 +570,7 @@ int rmj_copy_games(rmj_handle dst, const uint32_t* dst_idx, rmj_handle src, cons
     int rc;
     if ((rc = tmp.upload(dst_idx, n, &d_a)) || (rc = tmp.upload(src_idx, n, &d_b))) return rc;
     if (src != dst) HIPCHK(hipStreamSynchronize(src->stream));
-    if (dst->cfg.game_mode >= 3) hipLaunchKernelGGL(rmj3::k_copy_games, dim3(n), dim3(64), 0, dst->stream, (const Env*)dst->d_env, (const Env*)src->d_env, d_a, d_b, n);
-    else hipLaunchKernelGGL(rmj4::k_copy_games, dim3(n), dim3(64), 0, dst->stream, (const Env*)dst->d_env, (const Env*)src->d_env, d_a, d_b, n);
+    RMJ_LAUNCH_MODE(dst, k_copy_games, dim3(n), dim3(64), (const Env*)src->d_env, d_a, d_b, n);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(dst->stream));
     return RMJ_OK;
@@ -547,8 +583,7 @@ int rmj_copy_games_device(rmj_handle dst, const uint32_t* d_dst_idx, rmj_handle 
     if (n == 0) return RMJ_OK;
     HIPCHK(hipSetDevice(dst->cfg.device));
     if (src != dst && src->stream != dst->stream) HIPCHK(hipStreamSynchronize(src->stream));
-    if (dst->cfg.game_mode >= 3) hipLaunchKernelGGL(rmj3::k_copy_games, dim3(n), dim3(64), 0, dst->stream, (const Env*)dst->d_env, (const Env*)src->d_env, d_dst_idx, d_src_idx, n);
-    else hipLaunchKernelGGL(rmj4::k_copy_games, dim3(n), dim3(64), 0, dst->stream, (const Env*)dst->d_env, (const Env*)src->d_env, d_dst_idx, d_src_idx, n);
+    RMJ_LAUNCH_MODE(dst, k_copy_games, dim3(n), dim3(64), (const Env*)src->d_env, d_dst_idx, d_src_idx, n);
     HIPCHK(hipGetLastError());
     return RMJ_OK;
 }
@@ -573,8 +608,7 @@ int rmj_reset(rmj_handle h, const uint8_t* select, const uint8_t* walls, const u
     ResetArgs A;
     memset(&A, 0, sizeof(A));
     A.select = d_sel; A.walls = d_walls; A.oya = d_oya; A.round_wind = d_rw; A.scores = d_sc; A.honba = d_honba; A.kyotaku = d_ky;
-    if (h->cfg.game_mode >= 3) hipLaunchKernelGGL(rmj3::k_reset, game_grid(h->cfg.n_games), dim3(256), 0, h->stream, (const Env*)h->d_env, A);
-    else hipLaunchKernelGGL(rmj4::k_reset, game_grid(h->cfg.n_games), dim3(256), 0, h->stream, (const Env*)h->d_env, A);
+    RMJ_LAUNCH_MODE(h, k_reset, game_grid(h->cfg.n_games), dim3(256), A);
     if (h->d_track)   // the round tracker must not read the reset as the end of a round (rmj_round_track_device)
         hipLaunchKernelGGL(k_track_mark, dim3((h->cfg.n_games + 255u) / 256u), dim3(256), 0, h->stream, (uint8_t*)h->d_track + B * 37, (const uint8_t*)d_sel, 0u, h->cfg.n_games);
     HIPCHK(hipGetLastError());
@@ -1052,13 +1086,8 @@ int rmj_get_legal_compact(rmj_handle h, uint32_t* index, uint32_t* offsets /*[ca
     HIPCHK(hipGetLastError());
     const size_t need_pin = 16 + (size_t)cap_rows * 8 + 4 + (size_t)cap_entries * 8;
     h->stage_valid = false;   // (the pinned staging is shared with rmj_drain_format's size call)
-    if (need_pin > h->pin_bytes) {
-        if (h->h_pin) hipHostFree(h->h_pin);
-        h->h_pin = nullptr; h->pin_bytes = 0;
-        HIPCHK(hipHostMalloc(&h->h_pin, need_pin, hipHostMallocDefault));
-        h->pin_bytes = need_pin;
-    }
-    uint8_t* pin = (uint8_t*)h->h_pin;
+    HIPCHK(h->pin.need(need_pin));
+    uint8_t* pin = (uint8_t*)h->pin.p;
     HIPCHK(hipMemcpyAsync(pin, tot, 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     const uint32_t rows = ((uint32_t*)pin)[0], ents = ((uint32_t*)pin)[1];
@@ -1261,8 +1290,7 @@ int rmj_poke_state(rmj_handle h, uint32_t game, const RmjStateView* v) {
     if (const char* err = rmjh::from_view(S, W, v)) return fail(RMJ_ERR_ARG, err);
     HIPCHK(hipMemcpy(h->d.core + game, &S, sizeof(GState), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->d.wall + (size_t)game * RMJ_WALL_STRIDE, W, RMJ_WALL_STRIDE, hipMemcpyHostToDevice));
-    if (h->cfg.game_mode >= 3) hipLaunchKernelGGL(rmj3::k_refresh, dim3(1), dim3(64), 0, h->stream, (const Env*)h->d_env, game);
-    else hipLaunchKernelGGL(rmj4::k_refresh, dim3(1), dim3(64), 0, h->stream, (const Env*)h->d_env, game);
+    RMJ_LAUNCH_MODE(h, k_refresh, dim3(1), dim3(64), game);
     if (h->d_track) hipLaunchKernelGGL(k_track_mark, dim3(1), dim3(64), 0, h->stream, (uint8_t*)h->d_track + (size_t)h->cfg.n_games * 37, (const uint8_t*)nullptr, game, 1u);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -1295,15 +1323,14 @@ static int drain_device(rmj_env* h, const uint32_t* cursor, uint32_t cap_events,
         HIPCHK(hipMalloc(&h->d_ev_lost, (size_t)n * 4));
         HIPCHK(hipMemsetAsync(h->d_ev_lost, 0, (size_t)n * 4, h->stream));
     }
-    const size_t o_first = (size_t)n * 4, o_pre = o_first + (size_t)n * 4, o_blk = o_pre + (size_t)n * 4, o_tot = o_blk + (size_t)blocks * 4;
-    const size_t o_off = o_tot + 16, o_new = o_off + ((size_t)n + 1) * 4, o_ev = (o_new + (size_t)n * 4 + 31) & ~(size_t)31;
-    // the records: a first pass sizes them (the scan total), the buffer is sized by the caller's cap or, when it passes 0, by the total
-    void* sp;
-    int rc = scratch_for(h, o_ev + (size_t)cap_events * sizeof(RmjEvent), &sp);
+    // packed words, the records behind them at a multiple of 32 bytes: a first pass sizes them (the scan total), the buffer is sized by
+    // the caller's cap or, when it passes 0, by the total
+    rmjh::DevLayout L(4);
+    L.add(&P->d_cur, (size_t)n * 4); L.add(&P->d_first, (size_t)n * 4); L.add(&P->d_pre, (size_t)n * 4); L.add(&P->d_blk, (size_t)blocks * 4);
+    L.add(&P->d_tot, 16); L.add(&P->d_off, ((size_t)n + 1) * 4); L.add(&P->d_new, (size_t)n * 4, 32);
+    L.add(&P->d_ev, (size_t)cap_events * sizeof(RmjEvent), 1);
+    int rc = scratch_for(h, L);
     if (rc) return rc;
-    uint8_t* base = (uint8_t*)sp;
-    P->d_cur = (uint32_t*)base; P->d_first = (uint32_t*)(base + o_first); P->d_pre = (uint32_t*)(base + o_pre); P->d_blk = (uint32_t*)(base + o_blk);
-    P->d_tot = (uint32_t*)(base + o_tot); P->d_off = (uint32_t*)(base + o_off); P->d_new = (uint32_t*)(base + o_new); P->d_ev = (RmjEvent*)(base + o_ev);
     P->cap = cap_events;
     HIPCHK(hipMemcpyAsync(P->d_cur, cursor, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(k_ev_count, dim3(blocks), dim3(LC_BLOCK), 0, h->stream, (const GState*)h->d.core, n, h->ring, (const uint32_t*)P->d_cur, P->d_first, P->d_pre, P->d_blk);
@@ -1323,13 +1350,8 @@ static void drain_book(rmj_env* h, const DrainPlan& P) {
     hipLaunchKernelGGL(k_ev_book, dim3((n + 255u) / 256u), dim3(256), 0, h->stream, (const uint32_t*)P.d_cur, (const uint32_t*)P.d_first, n, h->d_ev_lost);
 }
 static int pin_for(rmj_env* h, size_t bytes) {
-    if (bytes > h->pin_bytes) {
-        if (h->h_pin) hipHostFree(h->h_pin);
-        h->h_pin = nullptr; h->pin_bytes = 0;
-        h->stage_valid = false;
-        HIPCHK(hipHostMalloc(&h->h_pin, bytes, hipHostMallocDefault));
-        h->pin_bytes = bytes;
-    }
+    if (bytes > h->pin.cap) h->stage_valid = false;
+    HIPCHK(h->pin.need(bytes));
     return RMJ_OK;
 }
 int rmj_get_log_positions(rmj_handle h, uint32_t* base, uint32_t* pos) {
@@ -1361,7 +1383,7 @@ int rmj_drain_events(rmj_handle h, uint32_t* cursor, RmjEvent* out, uint32_t cap
     HIPCHK(hipGetLastError());
     rc = pin_for(h, ((size_t)n * 2 + 1) * 4 + (size_t)*n_events * sizeof(RmjEvent));
     if (rc) return rc;
-    uint8_t* pin = (uint8_t*)h->h_pin;
+    uint8_t* pin = (uint8_t*)h->pin.p;
     HIPCHK(hipMemcpyAsync(pin, P.d_off, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(pin + ((size_t)n + 1) * 4, P.d_new, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
     if (*n_events) HIPCHK(hipMemcpyAsync(out, P.d_ev, (size_t)*n_events * sizeof(RmjEvent), hipMemcpyDeviceToHost, h->stream));
@@ -1397,7 +1419,7 @@ int rmj_drain_format(rmj_handle h, uint32_t* cursor, int seat, char* buf, uint64
         auto t1 = now();
         rc = pin_for(h, o_ev + (size_t)*n_events * sizeof(RmjEvent));
         if (rc) return rc;
-        uint8_t* pin = (uint8_t*)h->h_pin;
+        uint8_t* pin = (uint8_t*)h->pin.p;
         HIPCHK(hipMemcpyAsync(pin, P.d_off, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipMemcpyAsync(pin + ((size_t)n + 1) * 4, P.d_new, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipMemcpyAsync(pin + ((size_t)n * 2 + 1) * 4, P.d_first, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
@@ -1411,7 +1433,7 @@ int rmj_drain_format(rmj_handle h, uint32_t* cursor, int seat, char* buf, uint64
         h->stage_events = *n_events;
         h->stage_valid = true;
     }
-    uint8_t* pin = (uint8_t*)h->h_pin;
+    uint8_t* pin = (uint8_t*)h->pin.p;
     *n_events = h->stage_events;
     auto t2 = now();
     *needed = rmjh::format_events((const RmjEvent*)(pin + o_ev), (const uint32_t*)pin, n, seat, buf, cap, text_offsets, 0);
@@ -1445,51 +1467,27 @@ int rmj_drain_format(rmj_handle h, uint32_t* cursor, int seat, char* buf, uint64
     return RMJ_OK;
 }
 // ---- MJAI text on the device (rmj_drain_text / rmj_format_events_device; k_text_*: rmj_events.hip.h) ------
-// handle-owned buffers of the text calls: device text / offsets / work, pinned text / offsets + cursors; grown on demand
-static int text_device_room(rmj_env* h, uint32_t n_games) {
-    const uint32_t blocks = (n_games + 255u) / 256u;
-    const size_t work = (((size_t)n_games * 8 + 15) & ~(size_t)15) + (size_t)n_games * 8 + ((size_t)blocks + 2) * 8;
-    if (work > h->txt_work_bytes) {
-        HIPCHK(hipStreamSynchronize(h->stream));
-        hipFree(h->d_txt_work);
-        h->d_txt_work = nullptr; h->txt_work_bytes = 0;
-        HIPCHK(hipMalloc(&h->d_txt_work, work));
-        h->txt_work_bytes = work;
-    }
-    if ((size_t)n_games + 1 > h->txt_offs_slots) {
-        HIPCHK(hipStreamSynchronize(h->stream));
-        hipFree(h->d_txt_offs);
-        h->d_txt_offs = nullptr; h->txt_offs_slots = 0;
-        HIPCHK(hipMalloc(&h->d_txt_offs, ((size_t)n_games + 1) * 8));
-        h->txt_offs_slots = (size_t)n_games + 1;
-    }
-    return RMJ_OK;
-}
 // size, scan and write the text of n games (n > 0) into the handle's device buffers; *bytes = the text's size
 static int text_format_device(rmj_env* h, const TextSrc& s, uint32_t n, int seat, uint32_t* d_newcur, uint64_t* bytes) {
-    int rc = text_device_room(h, n);
-    if (rc) return rc;
     const uint32_t blocks = (n + 255u) / 256u;
-    uint8_t* w = (uint8_t*)h->d_txt_work;
-    uint32_t* d_nrec = (uint32_t*)w;
-    uint32_t* d_bytes = d_nrec + n;
-    uint64_t* d_pre = (uint64_t*)(w + (((size_t)n * 8 + 15) & ~(size_t)15));
-    uint64_t* d_blk = d_pre + n;   // [blocks] + the total
+    // the work area: record and byte counts of every game, then (at a multiple of 16 bytes) the scan's prefixes and its [blocks] + the total + a spare
+    uint32_t *d_nrec, *d_bytes;
+    uint64_t *d_pre, *d_blk;
+    rmjh::DevLayout L(8);
+    L.add(&d_nrec, (size_t)n * 4, 4); L.add(&d_bytes, (size_t)n * 4, 16); L.add(&d_pre, (size_t)n * 8); L.add(&d_blk, ((size_t)blocks + 2) * 8);
+    HIPCHK(h->txt_work.need(L.bytes(), h->stream));
+    HIPCHK(h->txt_offs.need(((size_t)n + 1) * 8, h->stream));
+    L.bind(h->txt_work.p);
+    uint64_t* d_txt_offs = (uint64_t*)h->txt_offs.p;
     hipLaunchKernelGGL(k_text_size, dim3((n + 3u) / 4u), dim3(256), 0, h->stream, s, n, seat, d_nrec, d_bytes, d_newcur);
     hipLaunchKernelGGL(k_text_scan1, dim3(blocks), dim3(256), 0, h->stream, (const uint32_t*)d_bytes, n, d_pre, d_blk);
-    hipLaunchKernelGGL(k_text_scan2, dim3(1), dim3(1024), 0, h->stream, d_blk, blocks, h->d_txt_offs, n, d_blk + blocks);
+    hipLaunchKernelGGL(k_text_scan2, dim3(1), dim3(1024), 0, h->stream, d_blk, blocks, d_txt_offs, n, d_blk + blocks);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(bytes, d_blk + blocks, 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (*bytes > h->txt_cap || !h->d_txt) {
-        hipFree(h->d_txt);
-        h->d_txt = nullptr; h->txt_cap = 0;
-        const uint64_t cap = *bytes + *bytes / 8 + (1u << 20);   // growth headroom: the next drain of a similar batch fits
-        HIPCHK(hipMalloc(&h->d_txt, cap));
-        h->txt_cap = cap;
-    }
+    HIPCHK(h->txt.need(*bytes, h->stream));
     hipLaunchKernelGGL(k_text_write, dim3(n), dim3(64), 0, h->stream, s, n, seat, (const uint32_t*)d_nrec, (const uint32_t*)d_bytes, (const uint64_t*)d_pre,
-                       (const uint64_t*)d_blk, h->d_txt_offs, h->d_txt);
+                       (const uint64_t*)d_blk, d_txt_offs, (char*)h->txt.p);
     HIPCHK(hipGetLastError());
     return RMJ_OK;
 }
@@ -1500,31 +1498,20 @@ static int text_deliver(rmj_env* h, uint32_t n, uint64_t bytes, uint32_t flags, 
     HIPCHK(hipStreamSynchronize(h->stream));
     auto t1 = now();
     const size_t offs_b = ((size_t)n + 1) * 8, cur_b = cursor ? (size_t)n * 4 : 0;
-    if (offs_b + cur_b > h->txt_pin_offs_bytes) {
-        if (h->h_txt_offs) hipHostFree(h->h_txt_offs);
-        h->h_txt_offs = nullptr; h->txt_pin_offs_bytes = 0;
-        HIPCHK(hipHostMalloc(&h->h_txt_offs, offs_b + cur_b, hipHostMallocDefault));
-        h->txt_pin_offs_bytes = offs_b + cur_b;
-    }
+    HIPCHK(h->h_txt_offs.need(offs_b + cur_b));
     const bool host = !(flags & RMJ_TEXT_ON_DEVICE);
-    if (host && bytes > h->txt_pin_bytes) {
-        if (h->h_txt) hipHostFree(h->h_txt);
-        h->h_txt = nullptr; h->txt_pin_bytes = 0;
-        const uint64_t cap = bytes + bytes / 8 + (1u << 20);
-        HIPCHK(hipHostMalloc(&h->h_txt, cap, hipHostMallocDefault));
-        h->txt_pin_bytes = cap;
-    }
-    uint8_t* pin = (uint8_t*)h->h_txt_offs;
+    if (host) HIPCHK(h->h_txt.need(bytes));
+    uint8_t* pin = (uint8_t*)h->h_txt_offs.p;
     if (host) {
-        if (bytes) HIPCHK(hipMemcpyAsync(h->h_txt, h->d_txt, bytes, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipMemcpyAsync(pin, h->d_txt_offs, offs_b, hipMemcpyDeviceToHost, h->stream));
+        if (bytes) HIPCHK(hipMemcpyAsync(h->h_txt.p, h->txt.p, bytes, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(pin, h->txt_offs.p, offs_b, hipMemcpyDeviceToHost, h->stream));
     }
     if (cur_b) HIPCHK(hipMemcpyAsync(pin + offs_b, d_newcur, cur_b, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     auto t2 = now();
     if (cur_b) memcpy(cursor, pin + offs_b, cur_b);
-    out->text = host ? (const char*)h->h_txt : (const char*)h->d_txt;
-    out->text_offsets = host ? (const uint64_t*)pin : (const uint64_t*)h->d_txt_offs;
+    out->text = host ? (const char*)h->h_txt.p : (const char*)h->txt.p;
+    out->text_offsets = host ? (const uint64_t*)pin : (const uint64_t*)h->txt_offs.p;
     out->bytes = bytes;
     out->n_games = n;
     out->ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count();
@@ -1565,9 +1552,8 @@ int rmj_format_events_device(rmj_handle h, const RmjEvent* d_ev, const uint32_t*
         int rc = text_format_device(h, s, n_games, seat, nullptr, &bytes);
         if (rc) return rc;
     } else {
-        int rc = text_device_room(h, 0);
-        if (rc) return rc;
-        HIPCHK(hipMemsetAsync(h->d_txt_offs, 0, 8, h->stream));
+        HIPCHK(h->txt_offs.need(8, h->stream));   // (no games: one offset and no work area)
+        HIPCHK(hipMemsetAsync(h->txt_offs.p, 0, 8, h->stream));
     }
     uint32_t ends[2] = {0, 0};
     HIPCHK(hipMemcpyAsync(&ends[0], d_offsets, 4, hipMemcpyDeviceToHost, h->stream));
@@ -1880,15 +1866,12 @@ int rmj_encode_batch(rmj_handle h, const RmjObsBatch* b) {
     if (rc) return rc;
     HIPCHK(hipSetDevice(h->cfg.device));
     const size_t rows = b->compact ? (size_t)b->capacity : (size_t)h->cfg.n_games * 4;
-    const size_t out_bytes = rows * rs * sizeof(float), out_al = (out_bytes + 255) & ~(size_t)255;
-    const size_t idx_bytes = b->compact ? (size_t)b->capacity * sizeof(int32_t) : 0, idx_al = (idx_bytes + 255) & ~(size_t)255;
-    void* sp;
-    if ((rc = scratch_for(h, out_al + idx_al + sizeof(uint32_t), &sp))) return rc;
-    char* base = (char*)sp;
+    const size_t out_bytes = rows * rs * sizeof(float);
     RmjObsBatch d = *b;
-    d.d_out = (float*)base;
-    d.d_index = b->compact ? (int32_t*)(base + out_al) : nullptr;
-    d.d_count = b->compact ? (uint32_t*)(base + out_al + idx_al) : nullptr;
+    rmjh::DevLayout L;
+    L.add(&d.d_out, out_bytes); L.add(&d.d_index, b->compact ? (size_t)b->capacity * sizeof(int32_t) : 0); L.add(&d.d_count, sizeof(uint32_t), 1);
+    if ((rc = scratch_for(h, L))) return rc;
+    if (!b->compact) { d.d_index = nullptr; d.d_count = nullptr; }
     HIPCHK(hipStreamSynchronize(h->stream));
     if (!b->compact && out_bytes) HIPCHK(hipMemcpy(d.d_out, b->d_out, out_bytes, hipMemcpyHostToDevice));   // the rows that stay untouched
     launch_encode_batch(h, &d, rs);
@@ -1947,22 +1930,21 @@ int rmj_hidden_targets(rmj_handle h, const int32_t* index, uint32_t rows, const 
     if (!index || !out->d_opp_hand || !out->d_opp_shanten || !out->d_opp_waits || !out->d_opp_flags) return fail(RMJ_ERR_ARG, "null argument");
     HIPCHK(hipSetDevice(h->cfg.device));
     // the index and the four arrays at 256-byte steps of the handle's scratch
-    const size_t sz[5] = {(size_t)rows * 4, (size_t)rows * 24, (size_t)rows * 102, (size_t)rows * 3, (size_t)rows * 3};
-    size_t off[6] = {0};
-    for (int i = 0; i < 5; i++) off[i + 1] = off[i] + ((sz[i] + 255) & ~(size_t)255);
-    void* sp;
-    int rc = scratch_for(h, off[5], &sp);
+    const size_t r = rows;
+    int32_t* d_index;
+    RmjHiddenOut d{};
+    rmjh::DevLayout L;
+    L.add(&d_index, r * 4); L.add(&d.d_opp_waits, r * 24); L.add(&d.d_opp_hand, r * 102); L.add(&d.d_opp_flags, r * 3); L.add(&d.d_opp_shanten, r * 3);
+    int rc = scratch_for(h, L);
     if (rc) return rc;
-    char* b = (char*)sp;
     HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(b, index, sz[0], hipMemcpyHostToDevice));
-    const RmjHiddenOut d{(uint8_t*)(b + off[2]), (int8_t*)(b + off[4]), (uint64_t*)(b + off[1]), (uint8_t*)(b + off[3])};
-    if ((rc = rmj_hidden_targets_device(h, (const int32_t*)b, rows, nullptr, &d))) return rc;
+    HIPCHK(hipMemcpy(d_index, index, r * 4, hipMemcpyHostToDevice));
+    if ((rc = rmj_hidden_targets_device(h, d_index, rows, nullptr, &d))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(out->d_opp_waits, b + off[1], sz[1], hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out->d_opp_hand, b + off[2], sz[2], hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out->d_opp_flags, b + off[3], sz[3], hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out->d_opp_shanten, b + off[4], sz[4], hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out->d_opp_waits, d.d_opp_waits, r * 24, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out->d_opp_hand, d.d_opp_hand, r * 102, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out->d_opp_flags, d.d_opp_flags, r * 3, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out->d_opp_shanten, d.d_opp_shanten, r * 3, hipMemcpyDeviceToHost));
     return RMJ_OK;
 }
 // ---- PPO transition collector (rmj_ppo.hip.h) ------------------------------------------------------------------
@@ -1997,24 +1979,22 @@ int rmj_ppo_create(rmj_handle h, const RmjPpoConfig* cfg, rmj_ppo_handle* out) {
     P.capacity = cap; P.feat_floats = ch * w; P.row_floats = (ch * w + 3u) & ~3u; P.A = A;
     const size_t big = n > cap ? n : cap;
     // one allocation: the feature rows first (16-byte rows), then the 4-byte arrays, then the bytes
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_feat = take((size_t)cap * P.row_floats * 4), o_action = take((size_t)cap * 4), o_value = take((size_t)cap * 4), o_logp = take((size_t)cap * 4),
-                 o_adv = take((size_t)cap * 4), o_ret = take((size_t)cap * 4), o_game = take((size_t)cap * 4), o_serial = take((size_t)cap * 4), o_t = take((size_t)cap * 4),
-                 o_prev = take((size_t)cap * 4), o_slen = take((size_t)cap * 4), o_srew = take((size_t)cap * 4), o_tail = take((size_t)n * 4), o_olen = take((size_t)n * 4),
-                 o_gser = take((size_t)n * 4), o_rowof = take((size_t)n * 4), o_offs = take(big * 4), o_totals = take(((big + PPO_SCAN_BLOCK - 1) / PPO_SCAN_BLOCK) * 4),
-                 o_ctr = take(PPO_C_WORDS * 4), o_mask = take((size_t)cap * A), o_valid = take(cap), o_broken = take(n);
+    const size_t c4 = (size_t)cap * 4, n4 = (size_t)n * 4;
+    rmjh::DevLayout L;
+    L.add(&P.feat, (size_t)cap * P.row_floats * 4);
+    const size_t o_action = L.add(&P.action, c4);
+    L.add(&P.value, c4); L.add(&P.logp, c4); L.add(&P.adv, c4); L.add(&P.ret, c4); L.add(&P.game, c4); L.add(&P.serial, c4); L.add(&P.t, c4); L.add(&P.prev, c4);
+    L.add(&P.seg_len, c4); L.add(&P.seg_reward, c4); L.add(&P.tail, n4); L.add(&P.open_len, n4); L.add(&P.g_serial, n4); L.add(&P.rowof, n4);
+    L.add(&P.offs, big * 4); L.add(&P.totals, ((big + PPO_SCAN_BLOCK - 1) / PPO_SCAN_BLOCK) * 4); L.add(&P.ctr, PPO_C_WORDS * 4);
+    L.add(&P.mask, (size_t)cap * A); L.add(&P.valid, cap); L.add(&P.broken, n);
+    const size_t off = L.bytes();
     if (hipMalloc(&p->mem, off) != hipSuccess) {
         (void)hipGetLastError();
         delete p;
         return fail(RMJ_ERR_HIP, "rmj_ppo_create: no device memory for a pool of " + std::to_string(off >> 20) + " MiB (capacity x row bytes: choose a smaller capacity)");
     }
     uint8_t* m = (uint8_t*)p->mem;
-    P.feat = (float*)(m + o_feat); P.action = (int32_t*)(m + o_action); P.value = (float*)(m + o_value); P.logp = (float*)(m + o_logp); P.adv = (float*)(m + o_adv);
-    P.ret = (float*)(m + o_ret); P.game = (int32_t*)(m + o_game); P.serial = (uint32_t*)(m + o_serial); P.t = (int32_t*)(m + o_t); P.prev = (int32_t*)(m + o_prev);
-    P.seg_len = (int32_t*)(m + o_slen); P.seg_reward = (float*)(m + o_srew); P.tail = (int32_t*)(m + o_tail); P.open_len = (uint32_t*)(m + o_olen);
-    P.g_serial = (uint32_t*)(m + o_gser); P.rowof = (int32_t*)(m + o_rowof); P.offs = (uint32_t*)(m + o_offs); P.totals = (uint32_t*)(m + o_totals);
-    P.ctr = (uint32_t*)(m + o_ctr); P.mask = m + o_mask; P.valid = m + o_valid; P.broken = m + o_broken;
+    L.bind(m);
     h->ppo.push_back(p);
     // everything behind the feature rows starts as zeros (the views show defined values in slots that were never filled)
     if (hipMemsetAsync(m + o_action, 0, off - o_action, h->stream) != hipSuccess || (rc = ppo_clear_impl(p))) {
@@ -2344,7 +2324,7 @@ int rmj_logset_playstats_device(rmj_logset_handle s, uint32_t num_players, int32
 int rmj_logreplay_assign(const uint32_t* offsets, uint32_t n_logs, uint32_t n_slots, uint32_t* slot_of_log, uint32_t* slot_logs, uint32_t* slot_first, uint32_t* steps) {
     if (!offsets) return fail(RMJ_ERR_ARG, "null argument");
     if (n_slots > n_logs || (!n_slots && n_logs)) return fail(RMJ_ERR_ARG, "rmj_logreplay_assign: 1 <= n_slots <= n_logs (a slot without a log replays nothing)");
-    const uint32_t st = n_slots ? lr_assign(offsets, n_logs, n_slots, slot_of_log, slot_logs, slot_first) : 0u;
+    const uint32_t st = n_slots ? rmjh::lr_assign(offsets, n_logs, n_slots, slot_of_log, slot_logs, slot_first) : 0u;
     if (!n_slots && slot_first) slot_first[0] = 0u;
     if (steps) *steps = st;
     return RMJ_OK;
@@ -2353,14 +2333,8 @@ static int logreplay_clear_impl(rmj_logreplay* r) {
     rmj_env* h = r->env;
     LogRun& R = r->R;
     const uint32_t n = R.n;
-    std::vector<uint32_t> pos(n), cur(n);
-    for (uint32_t s = 0; s < n; s++) {
-        pos[s] = r->slot_first[s];
-        cur[s] = pos[s] < r->slot_first[s + 1] ? r->set->off[r->slot_logs[pos[s]]] : 0u;
-    }
     HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(R.pos, pos.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(R.cur, cur.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    HIPCHK(upload_start_cursors(r->chain, r->set, n, R.pos, R.cur));
     HIPCHK(hipMemsetAsync(R.kcount, 0, (size_t)n * 4, h->stream));
     HIPCHK(hipMemsetAsync(R.tcount, 0, (size_t)n * 16, h->stream));
     HIPCHK(hipMemsetAsync(R.apply_at, 0xFF, (size_t)n * 4, h->stream));
@@ -2369,7 +2343,7 @@ static int logreplay_clear_impl(rmj_logreplay* r) {
     HIPCHK(hipMemsetAsync(R.traj_len, 0, (size_t)(R.K ? R.K : 1u) * 16, h->stream));
     HIPCHK(hipMemsetAsync(R.traj_broken, 0, (size_t)(R.K ? R.K : 1u) * 4, h->stream));
     HIPCHK(hipMemsetAsync(R.ctr, 0, LR_C_WORDS * 4, h->stream));
-    r->step = 0;
+    r->chain.step = 0;
     return RMJ_OK;
 }
 int rmj_logreplay_create(rmj_handle h, rmj_logset_handle set, const RmjLogReplayConfig* cfg, rmj_logreplay_handle* out) {
@@ -2395,9 +2369,7 @@ int rmj_logreplay_create(rmj_handle h, rmj_logset_handle set, const RmjLogReplay
     r->cfg.gamma_powers = nullptr;
     const bool sanma = h->cfg.game_mode >= 3;
     const uint32_t cap = cfg->capacity, M = set->M, K = set->K ? set->K : 1u, A = sanma ? RMJ_ACTION_SPACE_3P : RMJ_ACTION_SPACE_4P;
-    r->slot_first.assign(n + 1, 0u);
-    r->slot_logs.assign(M ? M : 1u, 0u);
-    r->steps = lr_assign(set->off.data(), M, n, nullptr, r->slot_logs.data(), r->slot_first.data());
+    r->chain.assign(set->off.data(), M, n);
     // P[k] = gamma ** k, k < the longest log + 1 (a trajectory has fewer decisions than its log has events)
     r->n_powers = cfg->gamma_powers ? cfg->n_powers : set->max_len + 1u;
     if (!r->n_powers || (cfg->gamma_powers && cfg->n_powers < set->max_len + 1u)) {
@@ -2413,16 +2385,17 @@ int rmj_logreplay_create(rmj_handle h, rmj_logset_handle set, const RmjLogReplay
     R.sanma = sanma ? 1u : 0u;
     R.ev = set->d_ev; R.off = set->d_off; R.koff = set->d_koff;
     const size_t big = n > cap ? n : cap;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_feat = take((size_t)cap * R.row_floats * 4), o_packed = take((size_t)cap * 8), o_ret64 = take((size_t)cap * 8), o_dact = take((size_t)n * 32),
-                 o_powers = take((size_t)r->n_powers * 8), o_action = take((size_t)cap * 4), o_log = take((size_t)cap * 4), o_kyoku = take((size_t)cap * 4),
-                 o_seat = take((size_t)cap * 4), o_t = take((size_t)cap * 4), o_krow = take((size_t)cap * 4), o_ret = take((size_t)cap * 4), o_rank = take((size_t)cap * 4),
-                 o_sfirst = take((size_t)(n + 1) * 4), o_slogs = take((size_t)(M ? M : 1u) * 4), o_pos = take((size_t)n * 4), o_cur = take((size_t)n * 4),
-                 o_kcount = take((size_t)n * 4), o_tcount = take((size_t)n * 16), o_apply = take((size_t)n * 4), o_dt = take((size_t)n * 16), o_dlog = take((size_t)n * 4),
-                 o_dkrow = take((size_t)n * 4), o_tlen = take((size_t)K * 16), o_offs = take(big * 4), o_totals = take(((big + PPO_SCAN_BLOCK - 1) / PPO_SCAN_BLOCK) * 4),
-                 o_ctr = take(LR_C_WORDS * 4), o_mask = take((size_t)cap * A), o_dn = take(n), o_dseat = take((size_t)n * 4), o_status = take(M ? M : 1u),
-                 o_broken = take((size_t)K * 4);
+    const size_t c4 = (size_t)cap * 4, n4 = (size_t)n * 4;
+    rmjh::DevLayout L;
+    L.add(&R.feat, (size_t)cap * R.row_floats * 4);
+    const size_t o_packed = L.add(&R.packed, c4 * 2);
+    L.add(&R.ret64, c4 * 2); L.add(&R.dec_action, n4 * 8); L.add(&r->d_powers, (size_t)r->n_powers * 8);
+    L.add(&R.action, c4); L.add(&R.log, c4); L.add(&R.kyoku, c4); L.add(&R.seat, c4); L.add(&R.t, c4); L.add(&R.krow, c4); L.add(&R.ret, c4); L.add(&R.rank, c4);
+    L.add(&R.slot_first, (size_t)(n + 1) * 4); L.add(&R.slot_logs, (size_t)(M ? M : 1u) * 4); L.add(&R.pos, n4); L.add(&R.cur, n4); L.add(&R.kcount, n4);
+    L.add(&R.tcount, n4 * 4); L.add(&R.apply_at, n4); L.add(&R.dec_t, n4 * 4); L.add(&R.dec_log, n4); L.add(&R.dec_krow, n4); L.add(&R.traj_len, (size_t)K * 16);
+    L.add(&R.offs, big * 4); L.add(&R.totals, ((big + PPO_SCAN_BLOCK - 1) / PPO_SCAN_BLOCK) * 4); L.add(&R.ctr, LR_C_WORDS * 4);
+    L.add(&R.mask, (size_t)cap * A); L.add(&R.dec_n, n); L.add(&R.dec_seat, n4); L.add(&R.log_status, M ? M : 1u); L.add(&R.traj_broken, (size_t)K * 4);
+    const size_t off = L.bytes();
     if (hipMalloc(&r->mem, off) != hipSuccess) {
         (void)hipGetLastError();
         delete r;
@@ -2435,21 +2408,12 @@ int rmj_logreplay_create(rmj_handle h, rmj_logset_handle set, const RmjLogReplay
         return fail(RMJ_ERR_HIP, "rmj_logreplay_create: no device memory for the hidden records (capacity x 152 bytes: choose a smaller capacity)");
     }
     uint8_t* m = (uint8_t*)r->mem;
-    R.feat = (float*)(m + o_feat); R.packed = (uint64_t*)(m + o_packed); R.ret64 = (double*)(m + o_ret64); R.dec_action = (uint64_t*)(m + o_dact);
-    r->d_powers = (double*)(m + o_powers);
-    R.action = (int32_t*)(m + o_action); R.log = (int32_t*)(m + o_log); R.kyoku = (int32_t*)(m + o_kyoku); R.seat = (int32_t*)(m + o_seat); R.t = (int32_t*)(m + o_t);
-    R.krow = (uint32_t*)(m + o_krow); R.ret = (float*)(m + o_ret); R.rank = (int32_t*)(m + o_rank);
-    R.slot_first = (uint32_t*)(m + o_sfirst); R.slot_logs = (uint32_t*)(m + o_slogs); R.pos = (uint32_t*)(m + o_pos); R.cur = (uint32_t*)(m + o_cur);
-    R.kcount = (uint32_t*)(m + o_kcount); R.tcount = (uint32_t*)(m + o_tcount); R.apply_at = (uint32_t*)(m + o_apply); R.dec_t = (uint32_t*)(m + o_dt);
-    R.dec_log = (uint32_t*)(m + o_dlog); R.dec_krow = (uint32_t*)(m + o_dkrow); R.traj_len = (uint32_t*)(m + o_tlen); R.offs = (uint32_t*)(m + o_offs);
-    R.totals = (uint32_t*)(m + o_totals); R.ctr = (uint32_t*)(m + o_ctr); R.mask = m + o_mask; R.dec_n = m + o_dn; R.dec_seat = m + o_dseat;
-    R.log_status = m + o_status; R.traj_broken = m + o_broken;
+    L.bind(m);
     h->logreplay.push_back(r);
     // everything behind the feature rows starts as zeros (the views show defined values in slots that were never filled)
     if (hipMemsetAsync(m + o_packed, 0, off - o_packed, h->stream) != hipSuccess ||
         (r->d_hid && hipMemsetAsync(r->d_hid, 0, (size_t)cap * HID_SLOT_BYTES, h->stream) != hipSuccess) || hipStreamSynchronize(h->stream) != hipSuccess ||
-        hipMemcpy(m + o_sfirst, r->slot_first.data(), (size_t)(n + 1) * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        (M && hipMemcpy(m + o_slogs, r->slot_logs.data(), (size_t)M * 4, hipMemcpyHostToDevice) != hipSuccess) ||
+        upload_chain(r->chain, M, R.slot_first, R.slot_logs) != hipSuccess ||
         hipMemcpy(r->d_powers, pw.data(), (size_t)r->n_powers * 8, hipMemcpyHostToDevice) != hipSuccess || (rc = logreplay_clear_impl(r))) {
         rmj_logreplay_destroy(r);
         return rc ? rc : fail(RMJ_ERR_HIP, "rmj_logreplay_create: initialising the pool failed");
@@ -2474,12 +2438,16 @@ int rmj_logreplay_clear(rmj_logreplay_handle r) {
     HIPCHK(hipSetDevice(r->env->cfg.device));
     return logreplay_clear_impl(r);
 }
+// the tail of an event step of both replays: every slot's variant applies the event the step chose for it (apply_at; LR_NO_EVENT: none)
+static void launch_log_apply(rmj_env* h, uint32_t n, const RmjEvent* ev, const uint32_t* apply_at) {
+    RMJ_LAUNCH_MODE(h, k_log_apply, game_grid(n), dim3(256), ev, apply_at);
+}
 int rmj_logreplay_run_device(rmj_logreplay_handle r, uint32_t n_steps, uint32_t* steps_left) {
     if (!r) return fail(RMJ_ERR_ARG, "null argument");
     rmj_env* h = r->env;
     HIPCHK(hipSetDevice(h->cfg.device));
     const LogRun& R = r->R;
-    const uint32_t n = R.n, nb = (n + PPO_SCAN_BLOCK - 1) / PPO_SCAN_BLOCK, left = r->steps - r->step;
+    const uint32_t n = R.n, nb = (n + PPO_SCAN_BLOCK - 1) / PPO_SCAN_BLOCK, left = r->chain.steps - r->chain.step;
     const uint32_t todo = n_steps && n_steps < left ? n_steps : left;
     const bool sanma = h->cfg.game_mode >= 3;
     const int feat = r->cfg.features;
@@ -2495,14 +2463,13 @@ int rmj_logreplay_run_device(rmj_logreplay_handle r, uint32_t n_steps, uint32_t*
         else RMJ_LAUNCH_RECORD(false, RMJ_FEATURES_BASE);
 #undef RMJ_LAUNCH_RECORD
         if (r->d_hid) hipLaunchKernelGGL(k_log_hidden, dim3(n * 4), dim3(64), 0, h->stream, h->d, R, r->d_hid);   // the state is still the one the rows were encoded from
-        if (sanma) hipLaunchKernelGGL(rmj3::k_log_apply, game_grid(n), dim3(256), 0, h->stream, (const Env*)h->d_env, R.ev, (const uint32_t*)R.apply_at);
-        else hipLaunchKernelGGL(rmj4::k_log_apply, game_grid(n), dim3(256), 0, h->stream, (const Env*)h->d_env, R.ev, (const uint32_t*)R.apply_at);
+        launch_log_apply(h, n, R.ev, R.apply_at);
     }
-    r->step += todo;
+    r->chain.step += todo;
     // the bookkeeping of the last step: its samples join the fill, the logs that just ended become complete
     if (n) hipLaunchKernelGGL(k_log_decide, game_grid(n), dim3(256), 0, h->stream, h->d, R, 1);
     HIPCHK(hipGetLastError());
-    if (steps_left) *steps_left = r->steps - r->step;
+    if (steps_left) *steps_left = r->chain.steps - r->chain.step;
     return RMJ_OK;
 }
 int rmj_logreplay_finalize_device(rmj_logreplay_handle r, const double* d_reward, const int32_t* d_end_scores) {
@@ -2549,7 +2516,7 @@ int rmj_logreplay_hidden_views(rmj_logreplay_handle r, RmjLogHiddenViews* out) {
 int rmj_logreplay_views(rmj_logreplay_handle r, RmjLogReplayViews* out) {
     if (!r || !out) return fail(RMJ_ERR_ARG, "null argument");
     const LogRun& R = r->R;
-    *out = RmjLogReplayViews{R.capacity, R.row_floats, R.A, r->steps, R.feat, R.mask, R.action, R.packed, R.ret, R.ret64, R.rank, R.log, R.kyoku, R.seat, R.t,
+    *out = RmjLogReplayViews{R.capacity, R.row_floats, R.A, r->chain.steps, R.feat, R.mask, R.action, R.packed, R.ret, R.ret64, R.rank, R.log, R.kyoku, R.seat, R.t,
                              R.log_status, R.traj_len, R.traj_broken, R.ctr};
     return RMJ_OK;
 }
@@ -2560,7 +2527,7 @@ int rmj_logreplay_counts(rmj_logreplay_handle r, RmjLogReplayCounts* out) {
     uint32_t c[LR_C_WORDS];
     HIPCHK(hipMemcpyAsync(c, r->R.ctr, sizeof(c), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    *out = RmjLogReplayCounts{c[LR_C_FILL], c[LR_C_OVERFLOWED], c[LR_C_FAILED], c[LR_C_COMPLETE], c[LR_C_DECISIONS], c[LR_C_EVENTS], r->step, r->steps - r->step};
+    *out = RmjLogReplayCounts{c[LR_C_FILL], c[LR_C_OVERFLOWED], c[LR_C_FAILED], c[LR_C_COMPLETE], c[LR_C_DECISIONS], c[LR_C_EVENTS], r->chain.step, r->chain.steps - r->chain.step};
     return RMJ_OK;
 }
 
@@ -2579,49 +2546,38 @@ int rmj_logcheck_create(rmj_handle h, rmj_logset_handle set, uint32_t n_slots, u
     if (!M) return fail(RMJ_ERR_ARG, "rmj_logcheck_create: the set holds no log");
     if (n > games || n > M) return fail(RMJ_ERR_ARG, "rmj_logcheck_create: 1 <= n_slots <= the handle's games, and at most one slot per log");
     HIPCHK(hipSetDevice(h->cfg.device));
-    std::vector<uint32_t> slot_first(n + 1, 0u), slot_logs(M, 0u), pos(n), cur(n);
     rmj_logcheck* c = new rmj_logcheck();
     c->env = h;
     c->set = set;
-    c->steps = lr_assign(set->off.data(), M, n, nullptr, slot_logs.data(), slot_first.data());
-    for (uint32_t s = 0; s < n; s++) {
-        pos[s] = slot_first[s];
-        cur[s] = pos[s] < slot_first[s + 1] ? set->off[slot_logs[pos[s]]] : 0u;   // (a slot may be left without a log: a log of no events keeps its slot free for the next one)
-    }
+    c->chain.assign(set->off.data(), M, n);
     const bool sanma = h->cfg.game_mode >= 3;
     LogCheck& R = c->R;
     R.n = n; R.M = M; R.NP = sanma ? 3u : 4u; R.sanma = sanma ? 1u : 0u;
     R.ev = set->d_ev; R.off = set->d_off; R.koff = set->d_koff; R.status = set->d_status; R.errline = set->d_errline;
     R.start = set->d_start; R.end = set->d_own;
     const size_t guard = (flags & RMJ_LOGCHECK_GUARDS) ? (size_t)RMJ_LOGCHECK_GUARD_WORDS * 4 : 0;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    auto verdict = [&](size_t bytes) { take(guard); const size_t o = take(bytes); return o; };   // (256-byte steps: a guard of 64 words ends where its array begins)
-    const size_t o_code = verdict(M), o_seat = verdict(M), o_kyoku = verdict((size_t)M * 4), o_event = verdict((size_t)M * 4), o_detail = verdict((size_t)M * 4),
-                 o_counts = verdict(RMJ_LOGCHECK_COUNTERS * 4), o_tail = take(guard), o_sfirst = take((size_t)(n + 1) * 4), o_slogs = take((size_t)M * 4),
-                 o_pos = take((size_t)n * 4), o_cur = take((size_t)n * 4), o_kcount = take((size_t)n * 4), o_word = take((size_t)n * 4),
-                 o_seen = take((size_t)n * LC_SEEN), o_apply = take((size_t)games * 4);
-    (void)o_tail;
+    const size_t M4 = (size_t)M * 4, n4 = (size_t)n * 4;
+    rmjh::DevLayout L;   // the verdict arrays, a guard in front of each (which ends where the array begins) and one behind the last, then the bookkeeping
+    L.add_guarded(&R.code, M, guard); L.add_guarded(&R.seat, M, guard); L.add_guarded(&R.kyoku, M4, guard); L.add_guarded(&R.event, M4, guard);
+    L.add_guarded(&R.detail, M4, guard); L.add_guarded(&R.counts, RMJ_LOGCHECK_COUNTERS * 4, guard); L.guard(guard);
+    L.add(&R.slot_first, (size_t)(n + 1) * 4); L.add(&R.slot_logs, M4); L.add(&R.pos, n4); L.add(&R.cur, n4); L.add(&R.kcount, n4); L.add(&R.word, n4);
+    L.add(&R.seen, (size_t)n * LC_SEEN); L.add(&R.apply_at, (size_t)games * 4);
+    const size_t off = L.bytes();
     if (hipMalloc(&c->mem, off) != hipSuccess) {
         (void)hipGetLastError();
         delete c;
         return fail(RMJ_ERR_HIP, "rmj_logcheck_create: no device memory for the verdicts");
     }
     uint8_t* m = (uint8_t*)c->mem;
-    R.code = m + o_code; R.seat = m + o_seat; R.kyoku = (uint32_t*)(m + o_kyoku); R.event = (uint32_t*)(m + o_event); R.detail = (uint32_t*)(m + o_detail);
-    R.counts = (uint32_t*)(m + o_counts); R.slot_first = (uint32_t*)(m + o_sfirst); R.slot_logs = (uint32_t*)(m + o_slogs); R.pos = (uint32_t*)(m + o_pos);
-    R.cur = (uint32_t*)(m + o_cur); R.kcount = (uint32_t*)(m + o_kcount); R.word = (uint32_t*)(m + o_word); R.seen = m + o_seen; R.apply_at = (uint32_t*)(m + o_apply);
+    L.bind(m);
     // zeros everywhere, then the guards (which end where an array begins, and begin where the array's 256-byte step ends), the "nobody is
     // due" words, "no event" for every game of the handle, the assignment and the cursors; the verdicts start as OK / PARSE
     std::vector<uint32_t> gw(RMJ_LOGCHECK_GUARD_WORDS, RMJ_LOGCHECK_GUARD_WORD), word(n, (uint32_t)LC_NONE | (LC_NO_SEAT << 8));
     bool ok = hipMemsetAsync(m, 0, off, h->stream) == hipSuccess && hipStreamSynchronize(h->stream) == hipSuccess;
     if (guard)
-        for (size_t o : {o_code, o_seat, o_kyoku, o_event, o_detail, o_counts, o_tail + guard})
-            ok = ok && hipMemcpy(m + o - guard, gw.data(), guard, hipMemcpyHostToDevice) == hipSuccess;
+        for (size_t o : L.guards()) ok = ok && hipMemcpy(m + o, gw.data(), guard, hipMemcpyHostToDevice) == hipSuccess;
     ok = ok && hipMemset(R.apply_at, 0xFF, (size_t)games * 4) == hipSuccess && hipMemcpy(R.word, word.data(), (size_t)n * 4, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(m + o_sfirst, slot_first.data(), (size_t)(n + 1) * 4, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(m + o_slogs, slot_logs.data(), (size_t)M * 4, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(R.pos, pos.data(), (size_t)n * 4, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(R.cur, cur.data(), (size_t)n * 4, hipMemcpyHostToDevice) == hipSuccess;
+         upload_chain(c->chain, M, R.slot_first, R.slot_logs) == hipSuccess && upload_start_cursors(c->chain, set, n, R.pos, R.cur) == hipSuccess;
     if (ok) {
         hipLaunchKernelGGL(k_logcheck_init, dim3((M + 255u) / 256u), dim3(256), 0, h->stream, R);
         ok = hipGetLastError() == hipSuccess;
@@ -2656,24 +2612,22 @@ int rmj_logcheck_run_device(struct rmj_logcheck* c, uint32_t n_steps, uint32_t* 
     rmj_env* h = c->env;
     HIPCHK(hipSetDevice(h->cfg.device));
     const LogCheck& R = c->R;
-    const uint32_t left = c->steps - c->step, todo = n_steps && n_steps < left ? n_steps : left;
-    const bool sanma = h->cfg.game_mode >= 3;
+    const uint32_t left = c->chain.steps - c->chain.step, todo = n_steps && n_steps < left ? n_steps : left;
     for (uint32_t i = 0; i < todo; i++) {
         hipLaunchKernelGGL(k_log_check, game_grid(R.n), dim3(256), 0, h->stream, h->d, R, 0);
-        if (sanma) hipLaunchKernelGGL(rmj3::k_log_apply, game_grid(R.n), dim3(256), 0, h->stream, (const Env*)h->d_env, R.ev, (const uint32_t*)R.apply_at);
-        else hipLaunchKernelGGL(rmj4::k_log_apply, game_grid(R.n), dim3(256), 0, h->stream, (const Env*)h->d_env, R.ev, (const uint32_t*)R.apply_at);
+        launch_log_apply(h, R.n, R.ev, R.apply_at);
     }
-    c->step += todo;
+    c->chain.step += todo;
     // the verdicts of the logs that just ended
     hipLaunchKernelGGL(k_log_check, game_grid(R.n), dim3(256), 0, h->stream, h->d, R, 1);
     HIPCHK(hipGetLastError());
-    if (steps_left) *steps_left = c->steps - c->step;
+    if (steps_left) *steps_left = c->chain.steps - c->chain.step;
     return RMJ_OK;
 }
 int rmj_logcheck_views(struct rmj_logcheck* c, RmjLogCheckViews* out) {
     if (!c || !out) return fail(RMJ_ERR_ARG, "null argument");
     const LogCheck& R = c->R;
-    *out = RmjLogCheckViews{R.M, c->steps, R.code, R.seat, R.kyoku, R.event, R.detail, R.counts};
+    *out = RmjLogCheckViews{R.M, c->chain.steps, R.code, R.seat, R.kyoku, R.event, R.detail, R.counts};
     return RMJ_OK;
 }
 
@@ -2738,8 +2692,7 @@ int rmj_apply_events(rmj_handle h, const RmjEvent* events) {
     if (rcs) return rcs;
     RmjEvent* d_ev = (RmjEvent*)sp;
     HIPCHK(hipMemcpyAsync(d_ev, events, bytes, hipMemcpyHostToDevice, h->stream));
-    if (h->cfg.game_mode >= 3) hipLaunchKernelGGL(rmj3::k_apply_event, game_grid(h->cfg.n_games), dim3(256), 0, h->stream, (const Env*)h->d_env, (const RmjEvent*)d_ev);
-    else hipLaunchKernelGGL(rmj4::k_apply_event, game_grid(h->cfg.n_games), dim3(256), 0, h->stream, (const Env*)h->d_env, (const RmjEvent*)d_ev);
+    RMJ_LAUNCH_MODE(h, k_apply_event, game_grid(h->cfg.n_games), dim3(256), (const RmjEvent*)d_ev);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
     return RMJ_OK;

@@ -359,4 +359,95 @@ inline uint64_t format_events(const RmjEvent* ev, const uint32_t* offsets, uint3
     return total;
 }
 
+// ---------------------------------------------------------------- layouts of one allocation
+// The arrays of a pool or of a scratch area, each named once: add() records where the array's typed pointer lives and how many bytes it
+// needs and returns its offset, bytes() is the size of the allocation, bind() points every registered pointer into it.  The area behind
+// an array ends at a multiple of the step (256 bytes unless the call says otherwise), where the next one begins.  Owns no memory.
+struct DevLayout {
+    explicit DevLayout(size_t step = 256) : step_(step) {}
+    template <class T>
+    size_t add(T** slot, size_t bytes) { return add(slot, bytes, step_); }
+    template <class T>
+    size_t add(T** slot, size_t bytes, size_t step) {
+        const size_t o = total_;
+        items_.push_back(Item{(void*)slot, o});
+        total_ = (o + bytes + step - 1) / step * step;
+        return o;
+    }
+    // a guard region of `guard` bytes that ends where the array begins: the array's offset (the guard's joins guards())
+    template <class T>
+    size_t add_guarded(T** slot, size_t bytes, size_t guard) {
+        total_ = (total_ + guard + step_ - 1) / step_ * step_;
+        guards_.push_back(total_ - guard);
+        return add(slot, bytes);
+    }
+    size_t guard(size_t bytes) {   // a guard region behind the last array: its offset
+        const size_t o = total_;
+        guards_.push_back(o);
+        total_ = (o + bytes + step_ - 1) / step_ * step_;
+        return o;
+    }
+    size_t bytes() const { return total_; }
+    const std::vector<size_t>& guards() const { return guards_; }
+    void bind(void* base) const {
+        for (const Item& it : items_) {
+            char* p = (char*)base + it.off;
+            memcpy(it.slot, &p, sizeof(p));   // (the slot is a T* of some T: written as the bytes of a pointer)
+        }
+    }
+
+private:
+    struct Item { void* slot; size_t off; };
+    std::vector<Item> items_;
+    std::vector<size_t> guards_;
+    size_t total_ = 0, step_;
+};
+
+// ---------------------------------------------------------------- chains of logs in replay slots
+// the assignment of logs to slots (see the head of rmj_logreplay.hip.h)
+inline uint32_t lr_assign(const uint32_t* off, uint32_t M, uint32_t n, uint32_t* slot_of_log, uint32_t* slot_logs, uint32_t* slot_first) {
+    std::vector<uint64_t> busy(n, 0);          // the step at which the slot is free again
+    std::vector<std::vector<uint32_t>> lists(n);
+    for (uint32_t l = 0; l < M; l++) {
+        uint32_t best = 0;
+        for (uint32_t s = 1; s < n; s++)
+            if (busy[s] < busy[best]) best = s;
+        busy[best] += off[l + 1] - off[l];
+        lists[best].push_back(l);
+        if (slot_of_log) slot_of_log[l] = best;
+    }
+    uint64_t steps = 0;
+    uint32_t at = 0;
+    for (uint32_t s = 0; s < n; s++) {
+        if (slot_first) slot_first[s] = at;
+        for (uint32_t l : lists[s]) {
+            if (slot_logs) slot_logs[at] = l;
+            at++;
+        }
+        if (busy[s] > steps) steps = busy[s];
+    }
+    if (slot_first) slot_first[n] = at;
+    return (uint32_t)steps;
+}
+// What a replay (sample builder, checker) keeps of its assignment on the host: slot s replays slot_logs[slot_first[s] .. slot_first[s + 1]),
+// a whole replay is `steps` event steps (the longest chain's events), `step` of them are taken.
+struct SlotChain {
+    std::vector<uint32_t> slot_first, slot_logs;   // [n + 1], [max(M, 1)]
+    uint32_t steps = 0, step = 0;
+    void assign(const uint32_t* off, uint32_t M, uint32_t n) {
+        slot_first.assign((size_t)n + 1, 0u);
+        slot_logs.assign(M ? M : 1u, 0u);
+        steps = lr_assign(off, M, n, nullptr, slot_logs.data(), slot_first.data());
+        step = 0;
+    }
+    // where every slot starts: pos[s] = its first entry of slot_logs, cur[s] = that log's first event.  A slot may be left without a
+    // log (a log of no events keeps its slot free for the next one): its cur stays 0 and slot_logs is not read at pos[s].
+    void start_cursors(const uint32_t* off, uint32_t* pos, uint32_t* cur) const {
+        for (size_t s = 0; s + 1 < slot_first.size(); s++) {
+            pos[s] = slot_first[s];
+            cur[s] = pos[s] < slot_first[s + 1] ? off[slot_logs[pos[s]]] : 0u;
+        }
+    }
+};
+
 }  // namespace rmjh

@@ -60,31 +60,7 @@ struct LogRun {
     uint32_t n, M, K, capacity, row_floats, feat_floats, A, NP, include_pass, skip_single, sanma;
 };
 
-// ---- host: the assignment of logs to slots (see the head of this file)
-static uint32_t lr_assign(const uint32_t* off, uint32_t M, uint32_t n, uint32_t* slot_of_log, uint32_t* slot_logs, uint32_t* slot_first) {
-    std::vector<uint64_t> busy(n, 0);          // the step at which the slot is free again
-    std::vector<std::vector<uint32_t>> lists(n);
-    for (uint32_t l = 0; l < M; l++) {
-        uint32_t best = 0;
-        for (uint32_t s = 1; s < n; s++)
-            if (busy[s] < busy[best]) best = s;
-        busy[best] += off[l + 1] - off[l];
-        lists[best].push_back(l);
-        if (slot_of_log) slot_of_log[l] = best;
-    }
-    uint64_t steps = 0;
-    uint32_t at = 0;
-    for (uint32_t s = 0; s < n; s++) {
-        if (slot_first) slot_first[s] = at;
-        for (uint32_t l : lists[s]) {
-            if (slot_logs) slot_logs[at] = l;
-            at++;
-        }
-        if (busy[s] > steps) steps = busy[s];
-    }
-    if (slot_first) slot_first[n] = at;
-    return (uint32_t)steps;
-}
+// ---- host: the assignment of logs to slots (see the head of this file) is rmjh::lr_assign (rmj_host.h: plain C++, also built without HIP)
 
 // ---- decision matching
 // the MJAI name of a tile id as a number (parser.rs:301-334 tid_to_mjai): the tile type, the red fives apart
