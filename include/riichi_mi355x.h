@@ -487,6 +487,43 @@ int rmj_hidden_targets_device(rmj_handle h, const int32_t* d_index, uint32_t row
 /* The same with host pointers (index and the four arrays of `out`): staged on the device, returns when the rows are there. */
 int rmj_hidden_targets(rmj_handle h, const int32_t* index, uint32_t rows, const RmjHiddenOut* out);
 
+/* Determinize: re-deal, in place, what seat a of game g cannot see - the concealed hands of its opponents and the part of the wall that can
+ * still be drawn or revealed - so that the game becomes a position the seat could not tell from the one it was; lists, masks, waits and
+ * status are republished and every call steps the game on (forks of rmj_copy_games_device become sampled worlds: PIMC, determinized
+ * search, value targets).  The pool in canonical order, in terms of RmjStateView: for r = 0, 1, 2 with r + 1 < NP and bit r of the row's
+ * `hold` byte clear, players[(a + 1 + r) mod NP].hand[0 .. hand_len); then wall[j], j ascending, except the revealed dora indicators
+ * (j + rinshan_draw_count = D + 2 k, k < n_dora; D = 4, in 3P 8).  The permutation:
+ *   mix(z):  z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31  (mod 2^64)
+ *   base  = mix(seed + global game)   (RmjConfig.game_offset + g, as the device policies count games)
+ *   key_i = mix(base + (a * 256 + i) * 0x9E3779B97F4A7C15),  i = canonical index;  perm = the indices sorted by (key_i, i)
+ *   the new tile at canonical position r is the old tile at canonical position perm[r]
+ * Then re-dealt hands are sorted (a re-dealt current player that holds a drawn tile keeps its last slot last; drawn_tile names the tile now
+ * there), in RMJ_WAIT_RESPONSE the claims of every seat but the discarder are rebuilt from the new hands (active_mask follows; seat a's own
+ * list, mask row and waits stay byte for byte), player flags stay, claim lists kept from before an accepted call are dropped as
+ * rmj_poke_state drops them, and salt / wall digest go on answering what they answered.  The event ring is NOT rewritten: the log of a
+ * determinized game no longer describes the opponents' tiles.  The sample is uniform over tile placements, not over worlds consistent
+ * with a riichi declaration (bits 4..6 of the status); weighting by tenpai is out of scope.
+ * d_status [rows] u8 (may be NULL): */
+#define RMJ_DET_OK 0u
+#define RMJ_DET_NOT_ACTING 1u    /* index out of range (negative too), seat >= NP, game done, or seat not in active_mask: game untouched */
+#define RMJ_DET_CHANKAN 2u       /* a robbed kan / kita is pending (pending_kan_pid set): its claims cannot be rebuilt; game untouched */
+#define RMJ_DET_DUPLICATE 3u     /* another row of the call that could be carried out names the same game and has a lower row number: of such rows exactly the lowest is carried out */
+#define RMJ_DET_RIICHI_NOTEN 16u /* << r: opponent r was re-dealt, has declared riichi and its 13 new tiles are not tenpai (with RMJ_DET_OK in the low bits) */
+typedef struct RmjDeterminize {
+    uint64_t seed;
+    const uint8_t* d_hold;   /* [rows] or NULL: bit r set = opponent r (seat (a + 1 + r) mod NP) keeps its concealed hand */
+    uint8_t* d_status;       /* [rows] or NULL */
+} RmjDeterminize;
+/* The rows of d_index [rows] i32 = game * 4 + seat (as rmj_encode_compact_device and rmj_get_legal_compact hand them out); d_count (device
+ * u32, may be NULL): rows at or behind min(rows, *d_count) are left untouched, their status too.  Asynchronous on the handle's stream (the
+ * first call of a handle allocates its claim words).  RMJ_ERR_ARG for a null handle / descriptor / index with rows > 0. */
+int rmj_determinize_device(rmj_handle h, const int32_t* d_index, uint32_t rows, const uint32_t* d_count, const RmjDeterminize* p);
+/* The same with host pointers (index, d_hold, d_status): staged on the device, returns when done.  Two rows that name one game are
+ * refused with RMJ_ERR_ARG before anything is touched. */
+int rmj_determinize(rmj_handle h, const int32_t* index, uint32_t rows, const RmjDeterminize* p);
+/* perm [m] of the permutation above for (seed, global game, seat, m <= 256), from the code the kernel runs; host only, needs no GPU. */
+int rmj_determinize_order(uint64_t seed, uint64_t global_game, uint32_t seat, uint32_t m, uint32_t* perm /*[m]*/);
+
 /* shanten.rs:244-261 calculate_shanten / :470-484 calculate_shanten_3p over raw 34-histograms
  * (len_div3 = tile count / 3; -1 = complete hand).  Tables are generated at first use, on the host. */
 int rmj_shanten(int device, const uint8_t* counts /*[n][34]*/, uint32_t n, int sanma, int8_t* out /*[n]*/);

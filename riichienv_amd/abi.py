@@ -288,6 +288,13 @@ class HiddenOut(C.Structure):        # RmjHiddenOut (rmj_hidden_targets_device)
     _fields_ = [(k, C.c_void_p) for k in ("opp_hand", "opp_shanten", "opp_waits", "opp_flags")]
 
 
+DET_OK, DET_NOT_ACTING, DET_CHANKAN, DET_DUPLICATE, DET_RIICHI_NOTEN = 0, 1, 2, 3, 16   # RMJ_DET_*: determinize status (RIICHI_NOTEN << r, r = 0, 1, 2)
+
+
+class Determinize(C.Structure):      # RmjDeterminize (rmj_determinize_device)
+    _fields_ = [("seed", C.c_uint64), ("hold", C.c_void_p), ("status", C.c_void_p)]
+
+
 class LogReplayConfig(C.Structure):  # RmjLogReplayConfig
     _fields_ = [("features", C.c_int32), ("capacity", C.c_uint32), ("flags", C.c_uint32), ("n_powers", C.c_uint32), ("gamma", C.c_double),
                 ("gamma_powers", C.c_void_p)]
@@ -416,6 +423,9 @@ PROTOTYPES = [
     ("rmj_step_sample_encode_batch_device", [vp, vp, u32, u64, cint, vp, P(ObsBatch)]),
     ("rmj_hidden_targets_device", [vp, vp, u32, vp, P(HiddenOut)]),
     ("rmj_hidden_targets", [vp, vp, u32, P(HiddenOut)]),
+    ("rmj_determinize_device", [vp, vp, u32, vp, P(Determinize)]),
+    ("rmj_determinize", [vp, vp, u32, P(Determinize)]),
+    ("rmj_determinize_order", [u64, u64, u32, u32, vp]),
     ("rmj_shanten", [cint, vp, u32, cint, vp]),
     ("rmj_effective_tiles", [cint, vp, u32, cint, vp]),
     ("rmj_best_ukeire", [cint, vp, vp, u32, cint, vp]),

@@ -55,6 +55,7 @@ using namespace rmj;
 #include "rmj_handtab.hip.h"
 #include "rmj_events.hip.h"
 #include "rmj_hidden.hip.h"
+#include "rmj_determinize.hip.h"
 
 static inline dim3 step_grid(uint32_t n) { return dim3((n + RMJ_STEP_WPB - 1) / RMJ_STEP_WPB); }
 // smallest batch that a multi-step device rollout splits over several streams of a handle (rmj_step_random)
@@ -165,6 +166,8 @@ struct rmj_env {
     Grown h_txt_offs{Grown::PINNED};    // pinned text offsets [games + 1], then the new cursors
     int enc_fused = 1;              // RMJ_ENC_FUSED at create: the step + encode rollout as ONE launch (k_step4_enc / k_step4_queue_enc); 0 = parts on streams
     uint32_t q_slots_enc = 0;       // waves of k_step4_queue_enc the device holds at once
+    Grown det_claim{Grown::DEVICE}; // rmj_determinize_device: [n_games] u64 claim words (epoch << 32 | ~row), allocated and cleared by the handle's first call
+    uint32_t det_epoch = 0;         // the last call's epoch: a word of an earlier call loses against any word of this one
 };
 // device staging memory of at least `bytes` bytes, owned by the handle
 static int scratch_for(rmj_env* h, size_t bytes, void** out) {
@@ -509,7 +512,7 @@ int rmj_destroy(rmj_handle h) {
         hipFree(p);
     while (!h->ppo.empty()) rmj_ppo_destroy(h->ppo.back());
     while (!h->logreplay.empty()) rmj_logreplay_destroy(h->logreplay.back());
-    for (Grown* g : {&h->scratch, &h->pin, &h->txt, &h->txt_offs, &h->txt_work, &h->h_txt, &h->h_txt_offs}) g->release();
+    for (Grown* g : {&h->scratch, &h->pin, &h->txt, &h->txt_offs, &h->txt_work, &h->h_txt, &h->h_txt_offs, &h->det_claim}) g->release();
     for (int i = 0; i < 2; i++) if (h->ev_time[i]) hipEventDestroy(h->ev_time[i]);
     if (h->own_stream) hipStreamDestroy(h->own_stream);
     for (int i = 0; i < RMJ_MAX_ROLLOUT_STREAMS - 1; i++) {
@@ -1945,6 +1948,61 @@ int rmj_hidden_targets(rmj_handle h, const int32_t* index, uint32_t rows, const 
     HIPCHK(hipMemcpy(out->d_opp_hand, d.d_opp_hand, r * 102, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(out->d_opp_flags, d.d_opp_flags, r * 3, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(out->d_opp_shanten, d.d_opp_shanten, r * 3, hipMemcpyDeviceToHost));
+    return RMJ_OK;
+}
+// ---- determinize (rmj_determinize.hip.h) ------------------------------------------------------------------------
+int rmj_determinize_device(rmj_handle h, const int32_t* d_index, uint32_t rows, const uint32_t* d_count, const RmjDeterminize* p) {
+    if (!h || !p) return fail(RMJ_ERR_ARG, "null argument");
+    if (!rows) return RMJ_OK;
+    if (!d_index) return fail(RMJ_ERR_ARG, "null argument");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const size_t claim_bytes = (size_t)h->cfg.n_games * 8;
+    if (!h->det_claim.p || h->det_epoch == 0xFFFFFFFFu) {   // first call (or the epochs are used up): words of epoch 0
+        HIPCHK(h->det_claim.need(claim_bytes, h->stream));
+        HIPCHK(hipMemsetAsync(h->det_claim.p, 0, claim_bytes, h->stream));
+        h->det_epoch = 0;
+    }
+    DetArgs A{d_index, d_count, p->d_hold, p->d_status, (unsigned long long*)h->det_claim.p, p->seed, rows, ++h->det_epoch};
+    hipLaunchKernelGGL(k_determinize_claim, dim3((rows + 255u) / 256u), dim3(256), 0, h->stream, h->d, A);
+    if (h->cfg.game_mode >= 3) hipLaunchKernelGGL(k_determinize<DetV3>, dim3((rows + WPB - 1u) / WPB), dim3(64 * WPB), 0, h->stream, (const Env*)h->d_env, A);
+    else hipLaunchKernelGGL(k_determinize<DetV4>, dim3((rows + WPB - 1u) / WPB), dim3(64 * WPB), 0, h->stream, (const Env*)h->d_env, A);
+    HIPCHK(hipGetLastError());
+    return RMJ_OK;
+}
+int rmj_determinize(rmj_handle h, const int32_t* index, uint32_t rows, const RmjDeterminize* p) {
+    if (!h || !p) return fail(RMJ_ERR_ARG, "null argument");
+    if (!rows) return RMJ_OK;
+    if (!index) return fail(RMJ_ERR_ARG, "null argument");
+    {   // two rows for one game: refused here (the device form carries out the lower row)
+        std::vector<uint32_t> games;
+        for (uint32_t i = 0; i < rows; i++)
+            if ((uint32_t)index[i] < h->cfg.n_games * 4u) games.push_back((uint32_t)index[i] >> 2);
+        std::sort(games.begin(), games.end());
+        if (std::adjacent_find(games.begin(), games.end()) != games.end()) return fail(RMJ_ERR_ARG, "rmj_determinize: two rows name the same game");
+    }
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const size_t r = rows;
+    int32_t* d_index;
+    uint8_t *d_hold, *d_status;
+    rmjh::DevLayout L;
+    L.add(&d_index, r * 4); L.add(&d_hold, r); L.add(&d_status, r);
+    int rc = scratch_for(h, L);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(d_index, index, r * 4, hipMemcpyHostToDevice));
+    if (p->d_hold) HIPCHK(hipMemcpy(d_hold, p->d_hold, r, hipMemcpyHostToDevice));
+    RmjDeterminize d{p->seed, p->d_hold ? d_hold : nullptr, d_status};
+    if ((rc = rmj_determinize_device(h, d_index, rows, nullptr, &d))) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (p->d_status) HIPCHK(hipMemcpy(p->d_status, d_status, r, hipMemcpyDeviceToHost));
+    return RMJ_OK;
+}
+int rmj_determinize_order(uint64_t seed, uint64_t global_game, uint32_t seat, uint32_t m, uint32_t* perm) {
+    if (m > 256u || (m && !perm)) return fail(RMJ_ERR_ARG, "rmj_determinize_order: m <= 256 and a perm array");
+    const uint64_t base = det_base(seed, global_game);
+    std::vector<uint64_t> keys(m);
+    for (uint32_t i = 0; i < m; i++) keys[i] = det_key(base, seat, i);
+    for (uint32_t i = 0; i < m; i++) perm[det_rank(keys.data(), m, keys[i], i)] = i;
     return RMJ_OK;
 }
 // ---- PPO transition collector (rmj_ppo.hip.h) ------------------------------------------------------------------

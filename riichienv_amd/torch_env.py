@@ -388,6 +388,31 @@ class TorchVecEnv:
         # kernel must have read them before they are released (shared stream: torch's stream orders it)
         self.sync()
 
+    def determinize(self, index, seed, count=None, hold=None):
+        """rmj_determinize_device: re-deal, in place, what the rows index [k] int32 = game * 4 + seat (as obs_compact returns them; the
+        seat must be to act) cannot see - the opponents' concealed hands and the wall that can still be drawn or revealed - by the
+        permutation the header defines for (seed, global game, seat), and republish lists, masks, waits and status.  count: the device
+        count of obs_compact(sync_count=False) - rows at or behind it are left alone; hold: uint8 [k] (or one int for every row), bit r
+        set = opponent (seat + 1 + r) mod NP keeps its hand.  Returns the status tensor uint8 [k] on the device (abi.DET_*; rows behind
+        the count read 0).  Of several rows that name one game the lowest is carried out, the others read DET_DUPLICATE.  Stream
+        handling as in copy_games."""
+        t = self.torch
+        idx = index.to(device=self.device, dtype=t.int32).contiguous().reshape(-1)
+        k = int(idx.shape[0])
+        st = t.zeros((k,), dtype=t.uint8, device=self.device)
+        if not k:
+            return st
+        h = None
+        if hold is not None:
+            h = (hold.to(device=self.device, dtype=t.uint8) if t.is_tensor(hold) else t.as_tensor(hold, dtype=t.uint8, device=self.device)).expand(k).contiguous()
+        if not self.shared:
+            t.cuda.current_stream(self.device).synchronize()
+        d = abi.Determinize(int(seed) & 0xFFFFFFFFFFFFFFFF, None if h is None else h.data_ptr(), st.data_ptr())
+        vecenv._chk(self.env.L.rmj_determinize_device(self.env.h, C.c_void_p(idx.data_ptr()), k, None if count is None else C.c_void_p(count.data_ptr()),
+                                                      C.byref(d)))
+        self.sync()   # (own stream: the kernels have read idx / hold before torch's allocator may hand them out again)
+        return st
+
     def sample_ids(self, logits=None, seed=0, index=None, count=None):
         """One id per acting seat drawn from softmax(logits) over the seat's legal ids, -1 elsewhere, by ONE kernel of the
         library (rmj_sample_ids_device: Gumbel-max on the resident mask slab) - no torch indexing / multinomial in the loop.

@@ -96,6 +96,13 @@ def _opt(arr, dtype, shape):
     return a, a.ctypes.data
 
 
+def determinize_order(seed, global_game, seat, m):
+    """perm [m] of rmj_determinize's permutation for (seed, global game, seat), from the library's own code (host only, no GPU)"""
+    perm = np.zeros(int(m), np.uint32)
+    _chk(load_lib().rmj_determinize_order(int(seed) & 0xFFFFFFFFFFFFFFFF, int(global_game) & 0xFFFFFFFFFFFFFFFF, int(seat), int(m), perm.ctypes.data))
+    return perm
+
+
 class VecRiichiEnv:
     """N independent games on one GPU (one shard of a batch sharded by game index)."""
 
@@ -112,6 +119,7 @@ class VecRiichiEnv:
             reference_rng = seeds is not None or bool(rule_bits & abi.RULE_REFERENCE_RNG)
         rule_bits = (rule_bits | abi.RULE_REFERENCE_RNG) if reference_rng else (rule_bits & ~abi.RULE_REFERENCE_RNG)
         self.reference_rng = bool(reference_rng)
+        self.rule_bits = int(rule_bits)
         cfg = abi.Config()
         cfg.n_games = self.n
         cfg.game_mode = _mode_id(game_mode)
@@ -355,6 +363,21 @@ class VecRiichiEnv:
             b = abi.HiddenOut(*(out[f].ctypes.data for f in ("opp_hand", "opp_shanten", "opp_waits", "opp_flags")))
             _chk(self.L.rmj_hidden_targets(self.h, idx.ctypes.data, k, C.byref(b)))
         return out
+
+    def determinize(self, index, seed, hold=None):
+        """Re-deal, in place, what the seats `index` [k] = game * 4 + seat (one row per game; the seat must be to act) cannot see: their
+        opponents' concealed hands and the wall that can still be drawn or revealed, by the permutation the header defines for (seed,
+        global game, seat) - rmj_determinize.  hold [k] uint8: bit r set = opponent (seat + 1 + r) mod NP keeps its hand.  Returns status
+        uint8 [k]: abi.DET_OK (+ abi.DET_RIICHI_NOTEN << r: opponent r is in riichi and its new hand is not tenpai), DET_NOT_ACTING or
+        DET_CHANKAN (game untouched).  Two rows for one game raise."""
+        idx = np.ascontiguousarray(index, dtype=np.int32).reshape(-1)
+        k = int(idx.size)
+        st = np.zeros(k, np.uint8)
+        if k:
+            h = None if hold is None else np.ascontiguousarray(np.broadcast_to(np.asarray(hold, dtype=np.uint8), (k,)))
+            d = abi.Determinize(int(seed) & 0xFFFFFFFFFFFFFFFF, None if h is None else h.ctypes.data, st.ctypes.data)
+            _chk(self.L.rmj_determinize(self.h, idx.ctypes.data, k, C.byref(d)))
+        return st
 
     def mask(self):
         m = np.zeros((self.n, 4, 82), np.uint8)
