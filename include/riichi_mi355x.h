@@ -487,6 +487,33 @@ int rmj_hidden_targets_device(rmj_handle h, const int32_t* d_index, uint32_t row
 /* The same with host pointers (index and the four arrays of `out`): staged on the device, returns when the rows are there. */
 int rmj_hidden_targets(rmj_handle h, const int32_t* index, uint32_t rows, const RmjHiddenOut* out);
 
+/* Deal-in danger targets: for the pair (game g, hero seat a), every opponent r (seat (a + 1 + r) mod NP, as above) and every tile kind k,
+ * the points that opponent would win by ron if the hero discarded a tile of that kind now - the label of a danger head, a folding
+ * policy or a search leaf.  A wait of rmj_hidden_targets_device that is furiten, or whose hand has a win shape and no yaku, costs
+ * nothing; a live one costs what the hand evaluator says.  Kinds 0..33: tile type k as its non-red id 4 k + 1; kinds 34, 35, 36: ids
+ * 16, 52, 88 - copy 0 of the fives, the red ones where the mode has them (the mode is not consulted).
+ *   d_danger [rows][3][37] i32  0 unless seat s holds concealed + 3 x melds = 13, the type of k is among its waits, neither that type
+ *   nor any other wait of s is among s's own discards, neither missed_agari flag is set, and the hand wins (a yaku other than dora, or
+ *   a yakuman); then ron_agari of the evaluation under the seat's riichi / double riichi / ippatsu, houtei when drawable_count == 0 and
+ *   not is_rinshan, the seat's and the round's wind, the dora indicators revealed now, kita_count = n_kita in 3P and the table's honba,
+ *   with a double yakuman whose rule bit is off counted once: the ron branch of the claim generation, then the winner's part of the ron
+ *   settlement.  RMJ_DANGER_URA: a seat in riichi also counts its ura indicators, read from the wall (the settlement's indices).
+ * Not what the settlement moves in these respects: riichi sticks on the table are not part of the value (the winner takes them, the
+ * discarder does not pay them); a pao split is not applied (the value is the winner's gain; with a liable third seat the discarder
+ * pays less); of several simultaneous winners only the nearest takes honba, here every opponent is valued as the only winner; the
+ * sanchaho draw is ignored; a kan-dora indicator pending at the moment of the row (pending_kan_dora_count > 0) is revealed with the
+ * discard itself and is not counted.
+ * Index, d_count and the absent rows as in rmj_hidden_targets_device; only reads the state.  Asynchronous on the handle's stream.
+ * RMJ_ERR_ARG for a null handle / descriptor, an unknown flag, or null arrays with rows > 0. */
+#define RMJ_DANGER_URA 1u
+#define RMJ_DANGER_KINDS 37
+typedef struct RmjDangerOut {
+    int32_t* d_danger;   /* [rows][3][37] */
+} RmjDangerOut;
+int rmj_danger_targets_device(rmj_handle h, const int32_t* d_index, uint32_t rows, const uint32_t* d_count, uint32_t flags, const RmjDangerOut* out);
+/* The same with host pointers (index and the array of `out`): staged on the device, returns when the rows are there. */
+int rmj_danger_targets(rmj_handle h, const int32_t* index, uint32_t rows, uint32_t flags, const RmjDangerOut* out);
+
 /* Determinize: re-deal, in place, what seat a of game g cannot see - the concealed hands of its opponents and the part of the wall that can
  * still be drawn or revealed - so that the game becomes a position the seat could not tell from the one it was; lists, masks, waits and
  * status are republished and every call steps the game on (forks of rmj_copy_games_device become sampled worlds: PIMC, determinized
@@ -797,9 +824,10 @@ int rmj_logreplay_assign(const uint32_t* offsets, uint32_t n_logs, uint32_t n_sl
 #define RMJ_LOGREPLAY_INCLUDE_PASS 1u        /* the Pass of every seat that was offered a claim and let it go is a sample */
 #define RMJ_LOGREPLAY_SKIP_SINGLE_ACTION 2u  /* a decision over a list of at most one action is no sample (LogKyoku.steps' default) */
 #define RMJ_LOGREPLAY_HIDDEN 4u              /* every pool slot also keeps its hidden-hand record and event index: rmj_logreplay_emit_hidden_device */
+#define RMJ_LOGREPLAY_DANGER 8u              /* every pool slot also keeps its deal-in danger record: rmj_logreplay_emit_danger_device */
 typedef struct RmjLogReplayConfig {
     int32_t features;           /* RMJ_FEATURES_*: the rows the pool stores */
-    uint32_t capacity;          /* samples: capacity x (C x W x 4 + A + 52) bytes of device memory, + 152 with RMJ_LOGREPLAY_HIDDEN */
+    uint32_t capacity;          /* samples: capacity x (C x W x 4 + A + 52) bytes of device memory, + 152 with RMJ_LOGREPLAY_HIDDEN, + 224 with RMJ_LOGREPLAY_DANGER */
     uint32_t flags;             /* RMJ_LOGREPLAY_* */
     uint32_t n_powers;
     double gamma;
@@ -910,6 +938,18 @@ typedef struct RmjLogHiddenViews {
     const uint8_t* records;
 } RmjLogHiddenViews;
 int rmj_logreplay_hidden_views(rmj_logreplay_handle r, RmjLogHiddenViews* out);
+/* RMJ_LOGREPLAY_DANGER: every sample also gets the deal-in danger row of (its slot's game, the deciding seat) - d_danger of
+ * rmj_danger_targets_device without RMJ_DANGER_URA (logs carry no wall) - taken where the hidden record is: from the state before the
+ * step's event is applied, by a kernel of its own right behind the hidden one (without the flag the replay launches what it always did
+ * and allocates nothing more).  Independent of RMJ_LOGREPLAY_HIDDEN.  The records lie in an allocation of their own of capacity x 224
+ * bytes: per slot [3][37] u16 in hundreds of points (every ron value is a multiple of 100).  Meaningless on logs with masked tiles.
+ * The emit call widens the records of the samples rmj_logreplay_emit_device emits to i32 points, in the same rows in the same order;
+ * rows beyond `rows` are dropped like there.  RMJ_ERR_ARG for a builder made without the flag. */
+typedef struct RmjLogDangerBatch {
+    int32_t* d_danger;       /* [rows][3][37] */
+    uint32_t rows, reserved;
+} RmjLogDangerBatch;
+int rmj_logreplay_emit_danger_device(rmj_logreplay_handle r, const RmjLogDangerBatch* out);
 
 /* ------------------------------------------------------------------ log validation
  * A verdict for every log of a log set before samples are built from it (riichienv-ml validates a corpus one log at a time through

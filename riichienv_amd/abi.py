@@ -280,12 +280,19 @@ LOGTEXT_OK, LOGTEXT_UNSUPPORTED, LOGTEXT_ERR_JSON, LOGTEXT_ERR_KEY, LOGTEXT_ERR_
 LOGTEXT_STATUS_NAMES = ["OK", "UNSUPPORTED", "ERR_JSON", "ERR_KEY", "ERR_TEHAI", "ERR_TILE", "ERR_VALUE", "ERR_REPLAY"]
 LOGTEXT_ON_DEVICE, LOGTEXT_MASKED_OK = 1, 2
 
-LOGREPLAY_INCLUDE_PASS, LOGREPLAY_SKIP_SINGLE_ACTION, LOGREPLAY_HIDDEN = 1, 2, 4   # RMJ_LOGREPLAY_*
+LOGREPLAY_INCLUDE_PASS, LOGREPLAY_SKIP_SINGLE_ACTION, LOGREPLAY_HIDDEN, LOGREPLAY_DANGER = 1, 2, 4, 8   # RMJ_LOGREPLAY_*
 HIDDEN_PRESENT, HIDDEN_TENPAI, HIDDEN_RIICHI, HIDDEN_FURITEN, HIDDEN_MELDS_SHIFT = 1, 2, 4, 8, 4   # RMJ_HIDDEN_*: the bits of opp_flags
 
 
 class HiddenOut(C.Structure):        # RmjHiddenOut (rmj_hidden_targets_device)
     _fields_ = [(k, C.c_void_p) for k in ("opp_hand", "opp_shanten", "opp_waits", "opp_flags")]
+
+
+DANGER_URA, DANGER_KINDS = 1, 37   # RMJ_DANGER_*: the flag of rmj_danger_targets*, the tile kinds of a row (34 types + the three copy-0 fives)
+
+
+class DangerOut(C.Structure):        # RmjDangerOut (rmj_danger_targets_device)
+    _fields_ = [("danger", C.c_void_p)]
 
 
 DET_OK, DET_NOT_ACTING, DET_CHANKAN, DET_DUPLICATE, DET_RIICHI_NOTEN = 0, 1, 2, 3, 16   # RMJ_DET_*: determinize status (RIICHI_NOTEN << r, r = 0, 1, 2)
@@ -317,6 +324,10 @@ class LogHiddenBatch(C.Structure):   # RmjLogHiddenBatch (rmj_logreplay_emit_hid
 
 class LogHiddenViews(C.Structure):   # RmjLogHiddenViews
     _fields_ = [("capacity", C.c_uint32), ("record_bytes", C.c_uint32), ("records", C.c_void_p)]
+
+
+class LogDangerBatch(C.Structure):   # RmjLogDangerBatch (rmj_logreplay_emit_danger_device)
+    _fields_ = [("danger", C.c_void_p), ("rows", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class LogReplayCounts(C.Structure):  # RmjLogReplayCounts
@@ -423,6 +434,8 @@ PROTOTYPES = [
     ("rmj_step_sample_encode_batch_device", [vp, vp, u32, u64, cint, vp, P(ObsBatch)]),
     ("rmj_hidden_targets_device", [vp, vp, u32, vp, P(HiddenOut)]),
     ("rmj_hidden_targets", [vp, vp, u32, P(HiddenOut)]),
+    ("rmj_danger_targets_device", [vp, vp, u32, vp, u32, P(DangerOut)]),
+    ("rmj_danger_targets", [vp, vp, u32, u32, P(DangerOut)]),
     ("rmj_determinize_device", [vp, vp, u32, vp, P(Determinize)]),
     ("rmj_determinize", [vp, vp, u32, P(Determinize)]),
     ("rmj_determinize_order", [u64, u64, u32, u32, vp]),
@@ -466,6 +479,7 @@ PROTOTYPES = [
     ("rmj_logreplay_clear", [vp]),
     ("rmj_logreplay_emit_hidden_device", [vp, P(LogHiddenBatch)]),
     ("rmj_logreplay_hidden_views", [vp, P(LogHiddenViews)]),
+    ("rmj_logreplay_emit_danger_device", [vp, P(LogDangerBatch)]),
     # ---- log validation
     ("rmj_logcheck_name", [u32], C.c_char_p),
     ("rmj_logcheck_create", [vp, vp, u32, u32, P(vp)]),

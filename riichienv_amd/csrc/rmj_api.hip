@@ -56,6 +56,7 @@ using namespace rmj;
 #include "rmj_events.hip.h"
 #include "rmj_hidden.hip.h"
 #include "rmj_determinize.hip.h"
+#include "rmj_danger.hip.h"
 
 static inline dim3 step_grid(uint32_t n) { return dim3((n + RMJ_STEP_WPB - 1) / RMJ_STEP_WPB); }
 // smallest batch that a multi-step device rollout splits over several streams of a handle (rmj_step_random)
@@ -319,6 +320,7 @@ struct rmj_logreplay {
     LogRun R{};
     double* d_powers = nullptr;
     uint8_t* d_hid = nullptr;          // RMJ_LOGREPLAY_HIDDEN: [capacity][HID_SLOT_BYTES] hidden records, an allocation of its own (rmj_hidden.hip.h)
+    uint8_t* d_dng = nullptr;          // RMJ_LOGREPLAY_DANGER: [capacity][DNG_SLOT_BYTES] danger records, an allocation of its own (rmj_danger.hip.h)
     uint32_t n_powers = 0;
     rmjh::SlotChain chain;             // which slot replays which logs, the steps of a whole replay and the steps taken
 };
@@ -1950,6 +1952,37 @@ int rmj_hidden_targets(rmj_handle h, const int32_t* index, uint32_t rows, const 
     HIPCHK(hipMemcpy(out->d_opp_shanten, d.d_opp_shanten, r * 3, hipMemcpyDeviceToHost));
     return RMJ_OK;
 }
+// ---- deal-in danger targets (rmj_danger.hip.h) -------------------------------------------------------------------
+int rmj_danger_targets_device(rmj_handle h, const int32_t* d_index, uint32_t rows, const uint32_t* d_count, uint32_t flags, const RmjDangerOut* out) {
+    if (!h || !out) return fail(RMJ_ERR_ARG, "null argument");
+    if (flags & ~(uint32_t)RMJ_DANGER_URA) return fail(RMJ_ERR_ARG, "rmj_danger_targets_device: unknown flag");
+    if (!rows) return RMJ_OK;
+    if (!d_index || !out->d_danger) return fail(RMJ_ERR_ARG, "null argument");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    hipLaunchKernelGGL(k_danger_targets, dim3((rows + 3u) / 4u), dim3(256), 0, h->stream, h->d, d_index, rows, d_count, flags, out->d_danger);
+    HIPCHK(hipGetLastError());
+    return RMJ_OK;
+}
+int rmj_danger_targets(rmj_handle h, const int32_t* index, uint32_t rows, uint32_t flags, const RmjDangerOut* out) {
+    if (!h || !out) return fail(RMJ_ERR_ARG, "null argument");
+    if (flags & ~(uint32_t)RMJ_DANGER_URA) return fail(RMJ_ERR_ARG, "rmj_danger_targets: unknown flag");
+    if (!rows) return RMJ_OK;
+    if (!index || !out->d_danger) return fail(RMJ_ERR_ARG, "null argument");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const size_t r = rows, bytes = r * 3 * RMJ_DANGER_KINDS * 4;
+    int32_t* d_index;
+    RmjDangerOut d{};
+    rmjh::DevLayout L;
+    L.add(&d_index, r * 4); L.add(&d.d_danger, bytes);
+    int rc = scratch_for(h, L);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(d_index, index, r * 4, hipMemcpyHostToDevice));
+    if ((rc = rmj_danger_targets_device(h, d_index, rows, nullptr, flags, &d))) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(out->d_danger, d.d_danger, bytes, hipMemcpyDeviceToHost));
+    return RMJ_OK;
+}
 // ---- determinize (rmj_determinize.hip.h) ------------------------------------------------------------------------
 int rmj_determinize_device(rmj_handle h, const int32_t* d_index, uint32_t rows, const uint32_t* d_count, const RmjDeterminize* p) {
     if (!h || !p) return fail(RMJ_ERR_ARG, "null argument");
@@ -2411,7 +2444,7 @@ int rmj_logreplay_create(rmj_handle h, rmj_logset_handle set, const RmjLogReplay
     if (set->device != h->cfg.device) return fail(RMJ_ERR_ARG, "rmj_logreplay_create: the log set lives on another device");
     const uint32_t n = h->cfg.n_games;
     if (n > set->M) return fail(RMJ_ERR_ARG, "rmj_logreplay_create: more slots (the handle's games) than logs: n_slots <= M");
-    if (cfg->flags & ~(uint32_t)(RMJ_LOGREPLAY_INCLUDE_PASS | RMJ_LOGREPLAY_SKIP_SINGLE_ACTION | RMJ_LOGREPLAY_HIDDEN)) return fail(RMJ_ERR_ARG, "rmj_logreplay_create: unknown flag");
+    if (cfg->flags & ~(uint32_t)(RMJ_LOGREPLAY_INCLUDE_PASS | RMJ_LOGREPLAY_SKIP_SINGLE_ACTION | RMJ_LOGREPLAY_HIDDEN | RMJ_LOGREPLAY_DANGER)) return fail(RMJ_ERR_ARG, "rmj_logreplay_create: unknown flag");
     uint32_t ch, w, rs;
     float dummy;
     RmjObsBatch b{};
@@ -2465,12 +2498,20 @@ int rmj_logreplay_create(rmj_handle h, rmj_logset_handle set, const RmjLogReplay
         delete r;
         return fail(RMJ_ERR_HIP, "rmj_logreplay_create: no device memory for the hidden records (capacity x 152 bytes: choose a smaller capacity)");
     }
+    if ((cfg->flags & RMJ_LOGREPLAY_DANGER) && hipMalloc(&r->d_dng, (size_t)cap * DNG_SLOT_BYTES) != hipSuccess) {
+        (void)hipGetLastError();
+        hipFree(r->mem);
+        if (r->d_hid) hipFree(r->d_hid);
+        delete r;
+        return fail(RMJ_ERR_HIP, "rmj_logreplay_create: no device memory for the danger records (capacity x 224 bytes: choose a smaller capacity)");
+    }
     uint8_t* m = (uint8_t*)r->mem;
     L.bind(m);
     h->logreplay.push_back(r);
     // everything behind the feature rows starts as zeros (the views show defined values in slots that were never filled)
     if (hipMemsetAsync(m + o_packed, 0, off - o_packed, h->stream) != hipSuccess ||
-        (r->d_hid && hipMemsetAsync(r->d_hid, 0, (size_t)cap * HID_SLOT_BYTES, h->stream) != hipSuccess) || hipStreamSynchronize(h->stream) != hipSuccess ||
+        (r->d_hid && hipMemsetAsync(r->d_hid, 0, (size_t)cap * HID_SLOT_BYTES, h->stream) != hipSuccess) ||
+        (r->d_dng && hipMemsetAsync(r->d_dng, 0, (size_t)cap * DNG_SLOT_BYTES, h->stream) != hipSuccess) || hipStreamSynchronize(h->stream) != hipSuccess ||
         upload_chain(r->chain, M, R.slot_first, R.slot_logs) != hipSuccess ||
         hipMemcpy(r->d_powers, pw.data(), (size_t)r->n_powers * 8, hipMemcpyHostToDevice) != hipSuccess || (rc = logreplay_clear_impl(r))) {
         rmj_logreplay_destroy(r);
@@ -2488,6 +2529,7 @@ int rmj_logreplay_destroy(rmj_logreplay_handle r) {
         if (h->logreplay[i] == r) { h->logreplay.erase(h->logreplay.begin() + i); break; }
     hipFree(r->mem);
     if (r->d_hid) hipFree(r->d_hid);
+    if (r->d_dng) hipFree(r->d_dng);
     delete r;
     return RMJ_OK;
 }
@@ -2521,6 +2563,7 @@ int rmj_logreplay_run_device(rmj_logreplay_handle r, uint32_t n_steps, uint32_t*
         else RMJ_LAUNCH_RECORD(false, RMJ_FEATURES_BASE);
 #undef RMJ_LAUNCH_RECORD
         if (r->d_hid) hipLaunchKernelGGL(k_log_hidden, dim3(n * 4), dim3(64), 0, h->stream, h->d, R, r->d_hid);   // the state is still the one the rows were encoded from
+        if (r->d_dng) hipLaunchKernelGGL(k_log_danger, dim3(n * 4), dim3(64), 0, h->stream, h->d, R, r->d_dng);
         launch_log_apply(h, n, R.ev, R.apply_at);
     }
     r->chain.step += todo;
@@ -2563,6 +2606,18 @@ int rmj_logreplay_emit_hidden_device(rmj_logreplay_handle r, const RmjLogHiddenB
     LogHiddenOut O{RmjHiddenOut{out->d_opp_hand, out->d_opp_shanten, out->d_opp_waits, out->d_opp_flags}, out->d_event, out->rows};
     hipLaunchKernelGGL(k_log_emit_scan, dim3((cap + PPO_SCAN_BLOCK - 1) / PPO_SCAN_BLOCK), dim3(PPO_SCAN_BLOCK), 0, h->stream, r->R);
     hipLaunchKernelGGL(k_log_emit_hidden, ppo_wave_grid(cap), dim3(256), 0, h->stream, r->R, (const uint8_t*)r->d_hid, O);
+    HIPCHK(hipGetLastError());
+    return RMJ_OK;
+}
+int rmj_logreplay_emit_danger_device(rmj_logreplay_handle r, const RmjLogDangerBatch* out) {
+    if (!r || !out) return fail(RMJ_ERR_ARG, "null argument");
+    if (!r->d_dng) return fail(RMJ_ERR_ARG, "rmj_logreplay_emit_danger_device: the builder was made without RMJ_LOGREPLAY_DANGER");
+    if (out->rows && !out->d_danger) return fail(RMJ_ERR_ARG, "null argument");
+    rmj_env* h = r->env;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const uint32_t cap = r->R.capacity;
+    hipLaunchKernelGGL(k_log_emit_scan, dim3((cap + PPO_SCAN_BLOCK - 1) / PPO_SCAN_BLOCK), dim3(PPO_SCAN_BLOCK), 0, h->stream, r->R);
+    hipLaunchKernelGGL(k_log_emit_danger, ppo_wave_grid(cap), dim3(256), 0, h->stream, r->R, (const uint8_t*)r->d_dng, out->d_danger, out->rows);
     HIPCHK(hipGetLastError());
     return RMJ_OK;
 }

@@ -91,6 +91,9 @@ class LogSampleBuilder:
     [N, 3] i8, "opp_waits" [N, 3] i64, "opp_flags" [N, 3] u8 (the rows of TorchVecEnv.hidden_compact: the opponents (seat + 1 + r) mod NP
     at the moment of the decision) and "event" [N] i32, the index in the log of the event the decision precedes; 152 more bytes per pool
     slot.  ValueError over a log set made with masked_ok=True: "?" tiles make those targets meaningless.
+    danger=False: with True samples() gains "danger" [N, 3, 37] i32 - the points opponent (seat + 1 + r) mod NP would win by ron if the
+    deciding seat discarded a tile of kind c at the moment of the decision (the rows of TorchVecEnv.danger_compact without ura: logs
+    carry no wall); 224 more bytes per pool slot.  Independent of hidden, combinable with it, refused over masked sets like it.
     rewards: finalize(rewards) takes a float64 [K, 4] table by kyoku row (`kyoku_offsets[log] + kyoku - 1`; the GRP reward model's
     output) - default: the seat's score change of the kyoku times kyoku_scale.
     on_error (text): "raise" or "drop" as LogSet takes them; after a drop the `log` field of the samples counts set logs (`log_ids`)."""
@@ -125,7 +128,7 @@ class LogSampleBuilder:
         return self._attach(LogSet.from_device_text(text, offsets, self.n_players, masked_ok, device, on_error), True)
 
     def _settings(self, game_mode, on_error="raise", features="base", n_slots=None, capacity=None, gamma=0.99, include_pass=True, skip_single_action=True,
-                  rule=None, share_stream=True, kyoku_scale=1.0 / 1000.0, hidden=False):
+                  rule=None, share_stream=True, kyoku_scale=1.0 / 1000.0, hidden=False, danger=False):
         """validates and stores what every constructor shares (no device work)"""
         import torch
 
@@ -146,7 +149,7 @@ class LogSampleBuilder:
         self.n_slots, self.capacity = n_slots, capacity
         self.gamma, self.kyoku_scale = float(gamma), float(kyoku_scale)
         self.include_pass, self.skip_single_action = bool(include_pass), bool(skip_single_action)
-        self.shared, self.hidden = bool(share_stream), bool(hidden)
+        self.shared, self.hidden, self.danger = bool(share_stream), bool(hidden), bool(danger)
         self._finalized = False
         self._emitted = None    # what samples() returned last, until run() / finalize() / clear()
         self.h = self.env = self.logset = None
@@ -171,6 +174,8 @@ class LogSampleBuilder:
             assert self.n_players == logset.num_players, "the log set was made for another number of players"
             if self.hidden and getattr(logset, "masked_ok", False):
                 raise ValueError("hidden=True over a log set made with masked_ok=True: the masked seats' tiles are unknown, so are their hands, shanten and waits")
+            if self.danger and getattr(logset, "masked_ok", False):
+                raise ValueError("danger=True over a log set made with masked_ok=True: the masked seats' tiles are unknown, so is what they would win")
             for k in ("logs", "M", "device", "kyoku_offsets", "n_kyokus", "log_ids", "dropped", "lengths"):
                 setattr(self, k, getattr(logset, k))
             self.host_seconds = dict(logset.host_seconds)
@@ -185,7 +190,7 @@ class LogSampleBuilder:
                 vecenv._chk(L.rmj_set_stream(self.env.h, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream), 0))
             self._powers = gamma_powers(self.gamma, logset.longest_log + 1)
             flags = (abi.LOGREPLAY_INCLUDE_PASS if self.include_pass else 0) | (abi.LOGREPLAY_SKIP_SINGLE_ACTION if self.skip_single_action else 0) | \
-                (abi.LOGREPLAY_HIDDEN if self.hidden else 0)
+                (abi.LOGREPLAY_HIDDEN if self.hidden else 0) | (abi.LOGREPLAY_DANGER if self.danger else 0)
             cfg = abi.LogReplayConfig(self._feat, self.capacity, flags, len(self._powers), self.gamma, self._powers.ctypes.data)
             h = C.c_void_p()
             vecenv._chk(L.rmj_logreplay_create(self.env.h, logset.handle, C.byref(cfg), C.byref(h)))
@@ -317,7 +322,8 @@ class LogSampleBuilder:
         hid = {"opp_hand": t.empty((k, 3, 34), dtype=t.uint8, device=d), "opp_shanten": t.empty((k, 3), dtype=t.int8, device=d),
                "opp_waits": t.empty((k, 3), dtype=t.int64, device=d), "opp_flags": t.empty((k, 3), dtype=t.uint8, device=d),
                "event": t.empty((k,), dtype=t.int32, device=d)} if self.hidden else {}
-        return {**self._empty_plain(k), **hid}
+        dng = {"danger": t.empty((k, 3, abi.DANGER_KINDS), dtype=t.int32, device=d)} if self.danger else {}
+        return {**self._empty_plain(k), **hid, **dng}
 
     def _empty_plain(self, k):
         t, d = self.torch, self.device
@@ -330,7 +336,7 @@ class LogSampleBuilder:
     def samples(self):
         """The dataset: {"features" [N, C, W] f32, "action" [N] i64, "return" [N] f32, "return64" [N] f64, "mask" [N, A] u8, "rank" [N] i64,
         "packed" [N] i64 (the packed action's bits), "log", "kyoku", "seat", "t" [N] i32} - with hidden=True also "opp_hand", "opp_shanten",
-        "opp_waits", "opp_flags" and "event" (class docstring), same rows, same order - on the device, in pool order - the samples of the
+        "opp_waits", "opp_flags" and "event", with danger=True "danger" (class docstring), same rows, same order - on the device, in pool order - the samples of the
         logs replayed to their end, without the trajectories that lost a sample to a full pool (rmj_logreplay_emit_device).  Finalizes with
         the default rewards if finalize() was not called since the last run.  Reads the pool's fill on the host to size the tensors.  The
         result is kept (and returned again, the same tensors) until run(), finalize() or clear()."""
@@ -353,6 +359,9 @@ class LogSampleBuilder:
             hb = abi.LogHiddenBatch(out["opp_hand"].data_ptr(), out["opp_shanten"].data_ptr(), out["opp_waits"].data_ptr(), out["opp_flags"].data_ptr(),
                                     out["event"].data_ptr(), rows, 0)
             vecenv._chk(self.L.rmj_logreplay_emit_hidden_device(self.h, C.byref(hb)))
+        if self.danger:
+            db = abi.LogDangerBatch(out["danger"].data_ptr(), rows, 0)
+            vecenv._chk(self.L.rmj_logreplay_emit_danger_device(self.h, C.byref(db)))
         self._sync()
         k = int(cnt[0])
         self._emitted = {name: v[:k] for name, v in out.items()}

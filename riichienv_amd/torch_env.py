@@ -178,6 +178,26 @@ class TorchVecEnv:
             self.sync()
         return out
 
+    def danger_compact(self, index, count=None, ura=False, out=None):
+        """Deal-in danger of the rows of a compact batch: index [k] int32 = game * 4 + seat -> int32 [k, 3, 37] on the device, the points
+        opponent (seat + 1 + r) mod NP would win by ron if the seat discarded a tile of kind c now (kinds 0..33 tile types, 34..36 copy 0
+        of the fives; rmj_danger_targets_device).  count: the device count tensor of obs_compact(sync_count=False) - rows at or behind it
+        are left as they were; ura: opponents in riichi count their ura indicators; out: the tensor of an earlier call to write into."""
+        t = self.torch
+        idx = index.to(device=self.device, dtype=t.int32).contiguous().reshape(-1)
+        k = int(idx.shape[0])
+        if out is None:
+            out = t.zeros((k, 3, abi.DANGER_KINDS), dtype=t.int32, device=self.device)
+        assert out.shape[0] >= k and out.is_contiguous() and out.dtype == t.int32, "out is too small for the index"
+        if k:
+            if not self.shared:
+                t.cuda.current_stream(self.device).synchronize()   # the buffers were made on torch's stream
+            b = abi.DangerOut(out.data_ptr())
+            vecenv._chk(self.env.L.rmj_danger_targets_device(self.env.h, C.c_void_p(idx.data_ptr()), k, None if count is None else C.c_void_p(count.data_ptr()),
+                                                             abi.DANGER_URA if ura else 0, C.byref(b)))
+            self.sync()
+        return out
+
     def scores(self):
         vecenv._chk(self.env.L.rmj_scores_device(self.env.h, C.c_void_p(self._scores.data_ptr()), None))
         self.sync()

@@ -364,6 +364,19 @@ class VecRiichiEnv:
             _chk(self.L.rmj_hidden_targets(self.h, idx.ctypes.data, k, C.byref(b)))
         return out
 
+    def danger_targets(self, index, ura=False):
+        """Deal-in danger of the seats `index` [k] = game * 4 + seat: int32 [k, 3, 37], the points opponent (seat + 1 + r) mod NP would win
+        by ron if the seat discarded a tile of kind c now - kinds 0..33 the tile types (non-red), 34..36 copy 0 of the 5m / 5p / 5s (the
+        red ones where the mode has them); 0 for a tile that is no wait, a furiten opponent, a hand without yaku - rmj_danger_targets
+        (header: the definition and where it leaves the settlement).  ura: opponents in riichi count their ura indicators off the wall."""
+        idx = np.ascontiguousarray(index, dtype=np.int32).reshape(-1)
+        k = int(idx.size)
+        out = np.zeros((k, 3, abi.DANGER_KINDS), np.int32)
+        if k:
+            b = abi.DangerOut(out.ctypes.data)
+            _chk(self.L.rmj_danger_targets(self.h, idx.ctypes.data, k, abi.DANGER_URA if ura else 0, C.byref(b)))
+        return out
+
     def determinize(self, index, seed, hold=None):
         """Re-deal, in place, what the seats `index` [k] = game * 4 + seat (one row per game; the seat must be to act) cannot see: their
         opponents' concealed hands and the wall that can still be drawn or revealed, by the permutation the header defines for (seed,
