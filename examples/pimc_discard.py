@@ -3,7 +3,7 @@ each once per legal discard and K times per fork, re-deal what the seat cannot s
 rmj_determinize_device), make the discard, play every world to the end of the game with the device policy, and print the mean change
 of the seat's score per discard.  Positions where seats answer a discard (RMJ_WAIT_RESPONSE) are left out of this example.
 
-    python examples/pimc_discard.py --roots 4 --worlds 16
+    python examples/pimc_discard.py --roots 4 --worlds 16 [--riichi-tenpai]
 """
 import argparse
 import os
@@ -14,7 +14,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 TILES = [f"{n}{s}" for s in "mps" for n in range(1, 10)] + ["E", "S", "W", "N", "P", "F", "C"]
 
 
-def main(roots=4, worlds=16, games=64, steps=90, game_mode=2, max_steps=4000, seed=5):
+def main(roots=4, worlds=16, games=64, steps=90, game_mode=2, max_steps=4000, seed=5, riichi_tenpai=False):
     import torch
 
     from riichienv_amd import abi
@@ -35,7 +35,7 @@ def main(roots=4, worlds=16, games=64, steps=90, game_mode=2, max_steps=4000, se
     r_of, d_of = legal.nonzero(as_tuple=True)
     rows = root[r_of]
     ws = WorldSet(tenv, worlds=worlds, max_rows=max(1, int(rows.shape[0])))
-    status = ws.fork(rows, seed=seed)
+    status = ws.fork(rows, seed=seed, riichi_tenpai=riichi_tenpai)   # (--riichi-tenpai: sampled riichi hands are walked to tenpai)
     ids = torch.full((ws.env.n, 4), -1, dtype=torch.int32, device=ws.env.device)
     k = int(rows.shape[0]) * worlds
     ids[ws.slot, ws.hero] = d_of.repeat_interleave(worlds).to(torch.int32)
@@ -45,7 +45,8 @@ def main(roots=4, worlds=16, games=64, steps=90, game_mode=2, max_steps=4000, se
     torch.cuda.synchronize()
     ok = (status & 15) == abi.DET_OK
     print(f"{int(root.shape[0])} roots, {int(rows.shape[0])} discards x {worlds} worlds = {k} playouts of up to {made} steps, "
-          f"{int(done.sum())} finished, {int((~ok).sum())} not determinized, {int((status >> 4 != 0).sum())} with a riichi hand that is not tenpai")
+          f"{int(done.sum())} finished, {int((~ok).sum())} not determinized, {int((status >> 4 & 7 != 0).sum())} with a riichi hand that is not tenpai"
+          + (f", {int((status & abi.DET_SWAPPED != 0).sum())} repaired by exchanges" if riichi_tenpai else ""))
     out = []
     for i in range(int(root.shape[0])):
         sel = (r_of == i).nonzero().reshape(-1)
@@ -64,5 +65,6 @@ if __name__ == "__main__":
     ap.add_argument("--games", type=int, default=64)
     ap.add_argument("--steps", type=int, default=90)
     ap.add_argument("--mode", type=int, default=2)
+    ap.add_argument("--riichi-tenpai", action="store_true", help="walk the sampled hands of opponents in riichi to tenpai (RMJ_DETF_RIICHI_TENPAI)")
     a = ap.parse_args()
-    main(a.roots, a.worlds, a.games, a.steps, a.mode)
+    main(a.roots, a.worlds, a.games, a.steps, a.mode, riichi_tenpai=a.riichi_tenpai)

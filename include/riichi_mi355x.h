@@ -529,13 +529,36 @@ int rmj_danger_targets(rmj_handle h, const int32_t* index, uint32_t rows, uint32
  * list, mask row and waits stay byte for byte), player flags stay, claim lists kept from before an accepted call are dropped as
  * rmj_poke_state drops them, and salt / wall digest go on answering what they answered.  The event ring is NOT rewritten: the log of a
  * determinized game no longer describes the opponents' tiles.  The sample is uniform over tile placements, not over worlds consistent
- * with a riichi declaration (bits 4..6 of the status); weighting by tenpai is out of scope.
+ * with a riichi declaration (bits 4..6 of the status) - unless the repair below is asked for.
+ *
+ * RMJ_DETF_RIICHI_TENPAI (rmj_determinize_ex_device / rmj_determinize_ex): re-dealt riichi hands are walked to tenpai.  The repair runs
+ * after the permutation has been applied and before the re-dealt hands are sorted, on the pool and the canonical indices above.
+ *   Partners:  Q = the canonical indices whose location is not a hand slot of a seat that has declared riichi - the wall entries of the
+ *     pool and the hands of the re-dealt opponents that are not in riichi.
+ *   Seats:  r = 0, 1, 2 in that order, with r + 1 < NP and bit r of `hold` clear; seat s = (a + 1 + r) mod NP is repaired if it has declared
+ *     riichi and hand_len = n with n mod 3 = 1.  Any other riichi seat is left to its NOTEN bit.
+ *   The walk of one seat:  cur = shanten(hand) - calculate_shanten, in 3P calculate_shanten_3p, with len_div3 = n / 3 (rmj_shanten).
+ *     For k = 0 .. 11 while cur > 0:  over hand slots i < n (tile x, type d = x >> 2) and partners j in Q (tile y, type t = y >> 2) with
+ *     d != t let v = shanten(hand - d + t).  want = cur - 1 if any pair reaches it, otherwise want = cur (a sideways step); if no pair has
+ *     v == want the walk stops.  Among the pairs with v == want the one with the smallest (key, i, j) is taken,
+ *       key = mix(base + (1024 + ((((a * 4 + r) * 16 + k) * 16 + i) * 256 + j)) * 0x9E3779B97F4A7C15)      (rmj_determinize_swap_key)
+ *     with mix and base as for the permutation (the offset 1024 keeps these keys off the permutation's); x and y are exchanged in place,
+ *     nothing is sorted in between, and cur = want.
+ * Then everything goes on as without the flag: the re-dealt hands are sorted (a drawn-tile slot stays last), the waits cache is cleared,
+ * the claims are rebuilt, the outputs are published and the NOTEN bits are computed from the final hands (waits == 0).  RMJ_DET_SWAPPED
+ * is set in the status of a row in whose world at least one exchange was made.  Choosing over concrete (slot, partner) pairs weights a
+ * pair of types by its multiplicities; the sideways steps are what lets the walk leave a hand no single exchange improves.
+ * What this distribution is: the nearest tenpai hand by fewest exchanges from a uniform deal, with seeded ties.  It is NOT a posterior.
+ * Out of scope: furiten consistency with the seat's own discards or with passed tiles; weighting by discards or calls; rewriting the
+ * event ring; riichi seats with n mod 3 = 2 (a riichi seat holding its drawn tile).
  * d_status [rows] u8 (may be NULL): */
 #define RMJ_DET_OK 0u
 #define RMJ_DET_NOT_ACTING 1u    /* index out of range (negative too), seat >= NP, game done, or seat not in active_mask: game untouched */
 #define RMJ_DET_CHANKAN 2u       /* a robbed kan / kita is pending (pending_kan_pid set): its claims cannot be rebuilt; game untouched */
 #define RMJ_DET_DUPLICATE 3u     /* another row of the call that could be carried out names the same game and has a lower row number: of such rows exactly the lowest is carried out */
 #define RMJ_DET_RIICHI_NOTEN 16u /* << r: opponent r was re-dealt, has declared riichi and its 13 new tiles are not tenpai (with RMJ_DET_OK in the low bits) */
+#define RMJ_DET_SWAPPED 128u     /* RMJ_DETF_RIICHI_TENPAI made at least one exchange in the row's world (with RMJ_DET_OK in the low bits) */
+#define RMJ_DETF_RIICHI_TENPAI 1u /* flags of rmj_determinize_ex*: walk the re-dealt riichi hands to tenpai (above) */
 typedef struct RmjDeterminize {
     uint64_t seed;
     const uint8_t* d_hold;   /* [rows] or NULL: bit r set = opponent r (seat (a + 1 + r) mod NP) keeps its concealed hand */
@@ -550,6 +573,13 @@ int rmj_determinize_device(rmj_handle h, const int32_t* d_index, uint32_t rows, 
 int rmj_determinize(rmj_handle h, const int32_t* index, uint32_t rows, const RmjDeterminize* p);
 /* perm [m] of the permutation above for (seed, global game, seat, m <= 256), from the code the kernel runs; host only, needs no GPU. */
 int rmj_determinize_order(uint64_t seed, uint64_t global_game, uint32_t seat, uint32_t m, uint32_t* perm /*[m]*/);
+/* rmj_determinize_device / rmj_determinize with flags (RMJ_DETF_*): flags = 0 is the call above, byte for byte, and launches or allocates
+ * nothing else.  RMJ_ERR_ARG for an unknown flag bit as well. */
+int rmj_determinize_ex_device(rmj_handle h, const int32_t* d_index, uint32_t rows, const uint32_t* d_count, const RmjDeterminize* p, uint32_t flags);
+int rmj_determinize_ex(rmj_handle h, const int32_t* index, uint32_t rows, const RmjDeterminize* p, uint32_t flags);
+/* The key of the exchange (hand slot i < 16, partner j < 256) in step k < 16 of opponent r's (r < 3) walk for viewpoint seat < 4, from the
+ * code the kernel runs; host only, needs no GPU.  RMJ_ERR_ARG outside these ranges or for a null key. */
+int rmj_determinize_swap_key(uint64_t seed, uint64_t global_game, uint32_t seat, uint32_t r, uint32_t k, uint32_t i, uint32_t j, uint64_t* key);
 
 /* shanten.rs:244-261 calculate_shanten / :470-484 calculate_shanten_3p over raw 34-histograms
  * (len_div3 = tile count / 3; -1 = complete hand).  Tables are generated at first use, on the host. */

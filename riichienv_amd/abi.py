@@ -296,6 +296,8 @@ class DangerOut(C.Structure):        # RmjDangerOut (rmj_danger_targets_device)
 
 
 DET_OK, DET_NOT_ACTING, DET_CHANKAN, DET_DUPLICATE, DET_RIICHI_NOTEN = 0, 1, 2, 3, 16   # RMJ_DET_*: determinize status (RIICHI_NOTEN << r, r = 0, 1, 2)
+DET_SWAPPED = 128            # RMJ_DET_SWAPPED: the tenpai repair exchanged at least one tile in the row's world
+DETF_RIICHI_TENPAI = 1       # RMJ_DETF_RIICHI_TENPAI (rmj_determinize_ex*)
 
 
 class Determinize(C.Structure):      # RmjDeterminize (rmj_determinize_device)
@@ -439,6 +441,9 @@ PROTOTYPES = [
     ("rmj_determinize_device", [vp, vp, u32, vp, P(Determinize)]),
     ("rmj_determinize", [vp, vp, u32, P(Determinize)]),
     ("rmj_determinize_order", [u64, u64, u32, u32, vp]),
+    ("rmj_determinize_ex_device", [vp, vp, u32, vp, P(Determinize), u32]),
+    ("rmj_determinize_ex", [vp, vp, u32, P(Determinize), u32]),
+    ("rmj_determinize_swap_key", [u64, u64, u32, u32, u32, u32, u32, vp]),
     ("rmj_shanten", [cint, vp, u32, cint, vp]),
     ("rmj_effective_tiles", [cint, vp, u32, cint, vp]),
     ("rmj_best_ukeire", [cint, vp, vp, u32, cint, vp]),

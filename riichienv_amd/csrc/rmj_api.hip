@@ -1985,6 +1985,10 @@ int rmj_danger_targets(rmj_handle h, const int32_t* index, uint32_t rows, uint32
 }
 // ---- determinize (rmj_determinize.hip.h) ------------------------------------------------------------------------
 int rmj_determinize_device(rmj_handle h, const int32_t* d_index, uint32_t rows, const uint32_t* d_count, const RmjDeterminize* p) {
+    return rmj_determinize_ex_device(h, d_index, rows, d_count, p, 0u);
+}
+int rmj_determinize_ex_device(rmj_handle h, const int32_t* d_index, uint32_t rows, const uint32_t* d_count, const RmjDeterminize* p, uint32_t flags) {
+    if (flags & ~RMJ_DETF_RIICHI_TENPAI) return fail(RMJ_ERR_ARG, "rmj_determinize: unknown flag");
     if (!h || !p) return fail(RMJ_ERR_ARG, "null argument");
     if (!rows) return RMJ_OK;
     if (!d_index) return fail(RMJ_ERR_ARG, "null argument");
@@ -1997,12 +2001,18 @@ int rmj_determinize_device(rmj_handle h, const int32_t* d_index, uint32_t rows, 
     }
     DetArgs A{d_index, d_count, p->d_hold, p->d_status, (unsigned long long*)h->det_claim.p, p->seed, rows, ++h->det_epoch};
     hipLaunchKernelGGL(k_determinize_claim, dim3((rows + 255u) / 256u), dim3(256), 0, h->stream, h->d, A);
-    if (h->cfg.game_mode >= 3) hipLaunchKernelGGL(k_determinize<DetV3>, dim3((rows + WPB - 1u) / WPB), dim3(64 * WPB), 0, h->stream, (const Env*)h->d_env, A);
-    else hipLaunchKernelGGL(k_determinize<DetV4>, dim3((rows + WPB - 1u) / WPB), dim3(64 * WPB), 0, h->stream, (const Env*)h->d_env, A);
+    const dim3 grid((rows + WPB - 1u) / WPB), block(64 * WPB);
+    if (flags & RMJ_DETF_RIICHI_TENPAI) {
+        if (h->cfg.game_mode >= 3) hipLaunchKernelGGL((k_determinize<DetV3, true>), grid, block, 0, h->stream, (const Env*)h->d_env, A);
+        else hipLaunchKernelGGL((k_determinize<DetV4, true>), grid, block, 0, h->stream, (const Env*)h->d_env, A);
+    } else if (h->cfg.game_mode >= 3) hipLaunchKernelGGL(k_determinize<DetV3>, grid, block, 0, h->stream, (const Env*)h->d_env, A);
+    else hipLaunchKernelGGL(k_determinize<DetV4>, grid, block, 0, h->stream, (const Env*)h->d_env, A);
     HIPCHK(hipGetLastError());
     return RMJ_OK;
 }
-int rmj_determinize(rmj_handle h, const int32_t* index, uint32_t rows, const RmjDeterminize* p) {
+int rmj_determinize(rmj_handle h, const int32_t* index, uint32_t rows, const RmjDeterminize* p) { return rmj_determinize_ex(h, index, rows, p, 0u); }
+int rmj_determinize_ex(rmj_handle h, const int32_t* index, uint32_t rows, const RmjDeterminize* p, uint32_t flags) {
+    if (flags & ~RMJ_DETF_RIICHI_TENPAI) return fail(RMJ_ERR_ARG, "rmj_determinize: unknown flag");
     if (!h || !p) return fail(RMJ_ERR_ARG, "null argument");
     if (!rows) return RMJ_OK;
     if (!index) return fail(RMJ_ERR_ARG, "null argument");
@@ -2025,7 +2035,7 @@ int rmj_determinize(rmj_handle h, const int32_t* index, uint32_t rows, const Rmj
     HIPCHK(hipMemcpy(d_index, index, r * 4, hipMemcpyHostToDevice));
     if (p->d_hold) HIPCHK(hipMemcpy(d_hold, p->d_hold, r, hipMemcpyHostToDevice));
     RmjDeterminize d{p->seed, p->d_hold ? d_hold : nullptr, d_status};
-    if ((rc = rmj_determinize_device(h, d_index, rows, nullptr, &d))) return rc;
+    if ((rc = rmj_determinize_ex_device(h, d_index, rows, nullptr, &d, flags))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
     if (p->d_status) HIPCHK(hipMemcpy(p->d_status, d_status, r, hipMemcpyDeviceToHost));
     return RMJ_OK;
@@ -2036,6 +2046,11 @@ int rmj_determinize_order(uint64_t seed, uint64_t global_game, uint32_t seat, ui
     std::vector<uint64_t> keys(m);
     for (uint32_t i = 0; i < m; i++) keys[i] = det_key(base, seat, i);
     for (uint32_t i = 0; i < m; i++) perm[det_rank(keys.data(), m, keys[i], i)] = i;
+    return RMJ_OK;
+}
+int rmj_determinize_swap_key(uint64_t seed, uint64_t global_game, uint32_t seat, uint32_t r, uint32_t k, uint32_t i, uint32_t j, uint64_t* key) {
+    if (!key || seat >= 4u || r >= 3u || k >= 16u || i >= 16u || j >= 256u) return fail(RMJ_ERR_ARG, "rmj_determinize_swap_key: seat < 4, r < 3, k < 16, i < 16, j < 256 and a key");
+    *key = det_swap_key(det_base(seed, global_game), seat, r, k, i, j);
     return RMJ_OK;
 }
 // ---- PPO transition collector (rmj_ppo.hip.h) ------------------------------------------------------------------

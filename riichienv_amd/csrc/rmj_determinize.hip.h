@@ -32,7 +32,17 @@
 // tiles or the draws to come.
 // The sample is uniform over placements of the pool's tiles, NOT over worlds consistent with what the opponents did: in particular a seat
 // that has declared riichi may get 13 tiles that are not tenpai - status bits 4..6 report it per opponent, and the caller rejects the
-// world, resamples with another seed or holds that hand.  Weighting by tenpai (or by discards, calls, ...) is out of scope.
+// world, resamples with another seed, holds that hand or asks for the repair below.
+//
+// RMJ_DETF_RIICHI_TENPAI (k_determinize<V, true>; the definition is in include/riichi_mi355x.h): between the permutation and the sort the
+// hand of every re-dealt riichi seat with hand_len = 1 mod 3 walks to tenpai by exchanges of one hand slot with one PARTNER - a canonical
+// index whose location is no hand slot of a riichi seat: the pool's wall entries and the hands of the re-dealt opponents not in riichi.
+// A step (at most DET_FIX_STEPS per seat, while the shanten number is above 0) judges every (hand slot i, tile type t held by a partner)
+// with one per-lane shanten each (hid_shanten over the hand's histogram minus the slot's type plus t, lane = pair, verdicts in LDS),
+// takes the step down if a pair gives it and a sideways step otherwise, and among the concrete (slot, partner) pairs with that verdict
+// picks the least (det_swap_key, i, j) by a wave reduction.  The result is the nearest tenpai hand by fewest exchanges from a uniform
+// deal with seeded ties - not a posterior: no furiten consistency, no weighting by discards or calls, the event ring stays, and a riichi
+// seat with hand_len = 2 mod 3 is left to its NOTEN bit.  k_determinize<V, false> is the kernel as it was: no LDS, no code of the repair.
 //
 // Two launches: k_determinize_claim (one thread per row) judges every row from the untouched records, writes the status of the rows that
 // are not carried out and lets the eligible rows of a game compete for the game's claim word (atomic max of epoch << 32 | ~row: the lowest
@@ -60,6 +70,10 @@ __host__ __device__ __forceinline__ uint32_t det_rank(const uint64_t* keys, uint
         r += (kj < key || (kj == key && j < i)) ? 1u : 0u;
     }
     return r;
+}
+// the key of the exchange (hand slot i, partner j) in step k of opponent r's walk: offset 1024 keeps it off the permutation's keys
+__host__ __device__ __forceinline__ uint64_t det_swap_key(uint64_t base, uint32_t seat, uint32_t r, uint32_t k, uint32_t i, uint32_t j) {
+    return det_mix(base + (uint64_t)(1024u + ((((seat * 4u + r) * 16u + k) * 16u + i) * 256u + j)) * 0x9E3779B97F4A7C15ull);
 }
 __host__ __device__ __forceinline__ unsigned long long det_claim_word(uint32_t epoch, uint32_t row) { return ((unsigned long long)epoch << 32) | (0xFFFFFFFFu - row); }
 
@@ -128,7 +142,111 @@ struct DetPool {
     uint8_t loc[DET_POOL_CAP];   // where canonical slot i lives: seat * 16 + hand slot, or 64 + wall position
 };
 
+// ---- RMJ_DETF_RIICHI_TENPAI: the walk of the re-dealt riichi hands to tenpai
+#define DET_FIX_STEPS 12u
+#define DET_FIX_NONE 0xFFFFFFFFu
+struct DetFix {
+    uint8_t ver[14 * 34];   // shanten of the hand with slot i's tile replaced by type t, at i * 34 + t; 99 = no such pair
+    uint8_t qh[36];         // the partners' tiles by type (34 counts; updated a 32-bit word at a time)
+};
+// the histogram of P.hand[0 .. n), wave-uniform
+__device__ __forceinline__ PH det_hand_ph(const PState& P, uint32_t n) {
+    PH h{0u, 0u, 0u, 0u};
+    for (uint32_t i = 0; i < n; i++) ph_add(h, (int)min((uint32_t)P.hand[i] >> 2, 33u));
+    return h;
+}
+// All 64 lanes call with wave-uniform arguments, behind the permutation and a wave_sync; true if a tile was exchanged.
 template <class V>
+__device__ __forceinline__ bool det_repair(typename V::Ctx& c, GState& S, const DetPool& D, DetFix& F, const ShantenTables& T, uint64_t base,
+                                           uint32_t a, uint32_t hold, uint32_t m, int lane) {
+    constexpr bool sanma = V::NP == 3u;
+    uint32_t riichi = 0;
+    for (uint32_t s = 0; s < V::NP; s++) riichi |= (rmj4::U((int)S.p[s].flags) & PF_RIICHI_DECLARED) ? 1u << s : 0u;
+    riichi = (uint32_t)__builtin_amdgcn_readfirstlane((int)riichi);   // (the same in every lane: scalar from here on, like n and cur below)
+    bool swapped = false;
+    for (uint32_t r = 0; r + 1u < V::NP; r++) {
+        const uint32_t x = a + 1u + r, s = x >= V::NP ? x - V::NP : x;
+        if (((hold >> r) & 1u) || !((riichi >> s) & 1u)) continue;
+        PState& P = S.p[s];
+        const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)min((uint32_t)rmj4::U((int)P.hand_len), 14u));
+        if (n % 3u != 1u) continue;
+        PH h = det_hand_ph(P, n);
+        int cur = __builtin_amdgcn_readfirstlane(hid_shanten(h, (int)(n / 3u), sanma, T));
+        for (uint32_t k = 0; k < DET_FIX_STEPS && cur > 0; k++) {
+            // the partners of this lane (canonical indices lane, lane + 64, lane + 128) and the types they hold
+            uint32_t pt[3];
+            if (lane < 36) F.qh[lane] = 0;
+            wave_sync();
+#pragma unroll
+            for (uint32_t q = 0; q < 3u; q++) {
+                const uint32_t j = (uint32_t)lane + 64u * q;
+                pt[q] = DET_FIX_NONE;
+                if (j < m) {
+                    const uint32_t l = D.loc[j];
+                    if (l >= 64u || !((riichi >> (l >> 4)) & 1u)) {
+                        pt[q] = min((l < 64u ? (uint32_t)S.p[l >> 4].hand[l & 15u] : (uint32_t)c.X.tiles[l - 64u]) >> 2, 33u);
+                        atomicAdd(reinterpret_cast<uint32_t*>(F.qh) + (pt[q] >> 2), 1u << (8u * (pt[q] & 3u)));   // (at most 4 of a type: no carry)
+                    }
+                }
+            }
+            wave_sync();
+            // the verdict of every (slot, type) pair, lane = pair
+            bool down = false, side = false;
+            for (uint32_t p = (uint32_t)lane; p < n * 34u; p += 64u) {
+                const uint32_t i = p / 34u, t = p - i * 34u, d = min((uint32_t)P.hand[i] >> 2, 33u);
+                int v = 99;
+                if (d != t && F.qh[t] != 0) {
+                    PH y = h;
+                    ph_sub(y, (int)d);
+                    ph_add(y, (int)t);
+                    v = hid_shanten(y, (int)(n / 3u), sanma, T);
+                }
+                F.ver[p] = (uint8_t)v;
+                down |= v == cur - 1;
+                side |= v == cur;
+            }
+            wave_sync();
+            const bool dn = __ballot(down) != 0ull;
+            if (!dn && __ballot(side) == 0ull) break;
+            const int want = dn ? cur - 1 : cur;
+            // the least (key, i, j) over the concrete pairs with that verdict
+            uint64_t bk = ~0ull;
+            uint32_t bij = DET_FIX_NONE;
+#pragma unroll
+            for (uint32_t q = 0; q < 3u; q++) {
+                if (pt[q] == DET_FIX_NONE) continue;
+                const uint32_t j = (uint32_t)lane + 64u * q;
+                for (uint32_t i = 0; i < n; i++) {
+                    if ((int)F.ver[i * 34u + pt[q]] != want) continue;
+                    const uint64_t key = det_swap_key(base, a, r, k, i, j);
+                    const uint32_t ij = i * 256u + j;
+                    if (key < bk || (key == bk && ij < bij)) { bk = key; bij = ij; }
+                }
+            }
+            for (int off = 32; off >= 1; off >>= 1) {
+                const uint64_t ok = ((uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(bk >> 32), off, 64) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)bk, off, 64);
+                const uint32_t oij = (uint32_t)__shfl_xor((int)bij, off, 64);
+                if (ok < bk || (ok == bk && oij < bij)) { bk = ok; bij = oij; }
+            }
+            bij = (uint32_t)__builtin_amdgcn_readfirstlane((int)bij);
+            if (bij == DET_FIX_NONE) break;   // (a verdict without a pair: cannot happen, and nothing is touched if it does)
+            const uint32_t i = min(bij >> 8, n - 1u), l = D.loc[min(bij & 255u, DET_POOL_CAP - 1u)];
+            wave_sync();
+            if (lane == 0) {
+                const uint8_t mine = P.hand[i];
+                if (l < 64u) { P.hand[i] = S.p[l >> 4].hand[l & 15u]; S.p[l >> 4].hand[l & 15u] = mine; }
+                else { P.hand[i] = c.X.tiles[l - 64u]; c.X.tiles[l - 64u] = mine; }
+            }
+            wave_sync();
+            h = det_hand_ph(P, n);
+            cur = want;
+            swapped = true;
+        }
+    }
+    return swapped;
+}
+
+template <class V, bool FIX = false>
 __global__ __launch_bounds__(256, 4) void k_determinize(const Env* __restrict__ Ep, DetArgs A) {   // (the bounds of k_apply_event: the out-of-line functions both reach keep the register budget they had)
     CEnv& E = *(CEnv*)Ep;
     __shared__ BlockShared sh;
@@ -200,6 +318,13 @@ __global__ __launch_bounds__(256, 4) void k_determinize(const Env* __restrict__ 
     }
     wave_sync();
 
+    bool swapped = false;
+    if constexpr (FIX) {   // ---- RMJ_DETF_RIICHI_TENPAI: re-dealt riichi hands walk to tenpai before anything is sorted
+        __shared__ __attribute__((aligned(4))) DetFix fix[WPB];
+        const ShantenTables T = sh_tables_of(E);
+        swapped = det_repair<V>(c, S, D, fix[wave], T, base, a, hold, m, lane);
+    }
+
     // ---- the record as a step keeps it
     const uint32_t cp = (uint32_t)rmj4::U((int)S.current_player);
     for (uint32_t s = 0; s < V::NP; s++) {
@@ -220,7 +345,7 @@ __global__ __launch_bounds__(256, 4) void k_determinize(const Env* __restrict__ 
     wave_sync();
 
     // ---- status bits 4..6: a re-dealt seat in riichi whose 13 tiles wait on nothing
-    uint32_t st = RMJ_DET_OK;
+    uint32_t st = swapped ? RMJ_DET_SWAPPED : RMJ_DET_OK;
     for (uint32_t r = 0; r + 1u < V::NP; r++) {
         const uint32_t x = a + 1u + r, s = x >= V::NP ? x - V::NP : x;
         if (!((redeal >> s) & 1u) || (hold >> r) & 1u) continue;

@@ -10,7 +10,10 @@ Monte Carlo move evaluation (PIMC), determinized tree search and value targets o
     delta, rank, done = ws.values()                      # [rows, 16] each
 
 The sample is uniform over placements of the hidden tiles (header: rmj_determinize_device), not over worlds consistent with what the
-opponents did; fork() returns the per-world status, whose bits 4..6 name opponents in riichi whose sampled hand is not tenpai."""
+opponents did; fork() returns the per-world status, whose bits 4..6 name opponents in riichi whose sampled hand is not tenpai.
+fork(..., riichi_tenpai=True) walks those hands to tenpai on the device (RMJ_DETF_RIICHI_TENPAI): what comes out is the nearest tenpai
+hand by fewest exchanges from a uniform deal, with seeded ties - not a posterior: no furiten consistency with the seat's discards, no
+weighting by discards or calls, and a riichi seat that holds its drawn tile (14, 11, ... tiles) is left as dealt."""
 from __future__ import annotations
 
 from . import torch_env
@@ -30,11 +33,12 @@ class WorldSet:
         self.rows = 0
         self.hero = self.score0 = self.slot = None
 
-    def fork(self, index, count=None, seed=0, hold=None):
+    def fork(self, index, count=None, seed=0, hold=None, riichi_tenpai=False):
         """Row r of index [rows <= R] int32 = game * 4 + seat (an acting seat of the source, e.g. obs_compact's index): the source's
         game is copied into the worlds r * K .. r * K + K - 1 and each is determinized from the seat's view with `seed` (the world's
         slot is its global game: the same (seed, slot) gives the same world).  count: the device count of obs_compact(sync_count=False);
-        hold: as in TorchVecEnv.determinize, per row.  Remembers the hero seat and its score at the fork.  Returns the status uint8
+        hold and riichi_tenpai: as in TorchVecEnv.determinize, hold per row (with riichi_tenpai a world in which a tile was exchanged
+        carries abi.DET_SWAPPED, and bits 4..6 remain only where the walk found no way to tenpai).  Remembers the hero seat and its score at the fork.  Returns the status uint8
         [rows, K] (abi.DET_*)."""
         t, K = self.src.torch, self.K
         idx = index.to(device=self.env.device, dtype=t.int32).contiguous().reshape(-1)
@@ -53,7 +57,7 @@ class WorldSet:
         if hold is not None:
             h = (hold.to(device=self.env.device, dtype=t.uint8) if t.is_tensor(hold) else t.as_tensor(hold, dtype=t.uint8, device=self.env.device))
             h = h.expand(rows).repeat_interleave(K)
-        st = self.env.determinize(slot * 4 + seat, seed, count=cnt, hold=h)
+        st = self.env.determinize(slot * 4 + seat, seed, count=cnt, hold=h, riichi_tenpai=riichi_tenpai)
         self.slot, self.hero = slot.to(t.int64), seat.to(t.int64)
         sc = self.src.scores()
         self.score0 = sc[game.to(t.int64).clamp(0, self.src.n - 1), self.hero].clone()

@@ -408,14 +408,16 @@ class TorchVecEnv:
         # kernel must have read them before they are released (shared stream: torch's stream orders it)
         self.sync()
 
-    def determinize(self, index, seed, count=None, hold=None):
+    def determinize(self, index, seed, count=None, hold=None, riichi_tenpai=False):
         """rmj_determinize_device: re-deal, in place, what the rows index [k] int32 = game * 4 + seat (as obs_compact returns them; the
         seat must be to act) cannot see - the opponents' concealed hands and the wall that can still be drawn or revealed - by the
         permutation the header defines for (seed, global game, seat), and republish lists, masks, waits and status.  count: the device
         count of obs_compact(sync_count=False) - rows at or behind it are left alone; hold: uint8 [k] (or one int for every row), bit r
         set = opponent (seat + 1 + r) mod NP keeps its hand.  Returns the status tensor uint8 [k] on the device (abi.DET_*; rows behind
-        the count read 0).  Of several rows that name one game the lowest is carried out, the others read DET_DUPLICATE.  Stream
-        handling as in copy_games."""
+        the count read 0).  Of several rows that name one game the lowest is carried out, the others read DET_DUPLICATE.
+        riichi_tenpai: rmj_determinize_ex_device with abi.DETF_RIICHI_TENPAI - the re-dealt riichi hands walk to tenpai by seeded
+        exchanges (header: the nearest tenpai hand by fewest exchanges from a uniform deal, not a posterior); abi.DET_SWAPPED marks the
+        worlds in which a tile was exchanged.  Stream handling as in copy_games."""
         t = self.torch
         idx = index.to(device=self.device, dtype=t.int32).contiguous().reshape(-1)
         k = int(idx.shape[0])
@@ -428,8 +430,11 @@ class TorchVecEnv:
         if not self.shared:
             t.cuda.current_stream(self.device).synchronize()
         d = abi.Determinize(int(seed) & 0xFFFFFFFFFFFFFFFF, None if h is None else h.data_ptr(), st.data_ptr())
-        vecenv._chk(self.env.L.rmj_determinize_device(self.env.h, C.c_void_p(idx.data_ptr()), k, None if count is None else C.c_void_p(count.data_ptr()),
-                                                      C.byref(d)))
+        cnt = None if count is None else C.c_void_p(count.data_ptr())
+        if riichi_tenpai:
+            vecenv._chk(self.env.L.rmj_determinize_ex_device(self.env.h, C.c_void_p(idx.data_ptr()), k, cnt, C.byref(d), abi.DETF_RIICHI_TENPAI))
+        else:
+            vecenv._chk(self.env.L.rmj_determinize_device(self.env.h, C.c_void_p(idx.data_ptr()), k, cnt, C.byref(d)))
         self.sync()   # (own stream: the kernels have read idx / hold before torch's allocator may hand them out again)
         return st
 

@@ -103,6 +103,15 @@ def determinize_order(seed, global_game, seat, m):
     return perm
 
 
+def determinize_swap_key(seed, global_game, seat, r, k, i, j):
+    """the key of the exchange (hand slot i, partner j) in step k of opponent r's walk to tenpai (rmj_determinize_ex with
+    abi.DETF_RIICHI_TENPAI) for (seed, global game, viewpoint seat), from the library's own code (host only, no GPU)"""
+    key = C.c_uint64(0)
+    _chk(load_lib().rmj_determinize_swap_key(int(seed) & 0xFFFFFFFFFFFFFFFF, int(global_game) & 0xFFFFFFFFFFFFFFFF, int(seat), int(r), int(k), int(i), int(j),
+                                             C.addressof(key)))
+    return int(key.value)
+
+
 class VecRiichiEnv:
     """N independent games on one GPU (one shard of a batch sharded by game index)."""
 
@@ -377,19 +386,25 @@ class VecRiichiEnv:
             _chk(self.L.rmj_danger_targets(self.h, idx.ctypes.data, k, abi.DANGER_URA if ura else 0, C.byref(b)))
         return out
 
-    def determinize(self, index, seed, hold=None):
+    def determinize(self, index, seed, hold=None, riichi_tenpai=False):
         """Re-deal, in place, what the seats `index` [k] = game * 4 + seat (one row per game; the seat must be to act) cannot see: their
         opponents' concealed hands and the wall that can still be drawn or revealed, by the permutation the header defines for (seed,
         global game, seat) - rmj_determinize.  hold [k] uint8: bit r set = opponent (seat + 1 + r) mod NP keeps its hand.  Returns status
         uint8 [k]: abi.DET_OK (+ abi.DET_RIICHI_NOTEN << r: opponent r is in riichi and its new hand is not tenpai), DET_NOT_ACTING or
-        DET_CHANKAN (game untouched).  Two rows for one game raise."""
+        DET_CHANKAN (game untouched).  Two rows for one game raise.  riichi_tenpai: abi.DETF_RIICHI_TENPAI - the re-dealt riichi hands of
+        13, 10, ... tiles walk to tenpai by seeded exchanges with the wall and the hands not in riichi before anything is sorted (header:
+        the nearest tenpai hand by fewest exchanges from a uniform deal, not a posterior); abi.DET_SWAPPED in the status of a world in
+        which a tile was exchanged."""
         idx = np.ascontiguousarray(index, dtype=np.int32).reshape(-1)
         k = int(idx.size)
         st = np.zeros(k, np.uint8)
         if k:
             h = None if hold is None else np.ascontiguousarray(np.broadcast_to(np.asarray(hold, dtype=np.uint8), (k,)))
             d = abi.Determinize(int(seed) & 0xFFFFFFFFFFFFFFFF, None if h is None else h.ctypes.data, st.ctypes.data)
-            _chk(self.L.rmj_determinize(self.h, idx.ctypes.data, k, C.byref(d)))
+            if riichi_tenpai:
+                _chk(self.L.rmj_determinize_ex(self.h, idx.ctypes.data, k, C.byref(d), abi.DETF_RIICHI_TENPAI))
+            else:
+                _chk(self.L.rmj_determinize(self.h, idx.ctypes.data, k, C.byref(d)))
         return st
 
     def mask(self):
