@@ -59,15 +59,35 @@ using namespace rmj;
 #include "rmj_danger.hip.h"
 
 static inline dim3 step_grid(uint32_t n) { return dim3((n + RMJ_STEP_WPB - 1) / RMJ_STEP_WPB); }
-// smallest batch that a multi-step device rollout splits over several streams of a handle (rmj_step_random)
-#define RMJ_SPLIT_MIN_GAMES 16384u
-#define RMJ_SPLIT_MIN_PART 8192u   // games per part at least
-#define RMJ_MAX_ROLLOUT_STREAMS 8
-// games per wave by batch size (STEP_F_ROWS_SHIFT; profiles/r04_rows_sweep.txt, fused 4p-red-single rollouts, M env.step/s at 4 | 2 | 1 games
-// per wave: 2 048 games 226 | 254 | 278, 4 096: 435 | 478 | 456, 8 192: 814 | 770 | 522, 16 384: 1 288 | 882 | 599; round 5, profiles/r05_rows_sweep.txt:
-// 2 048: 236 | 272 | 301, 3 072: 345 | 373 | 416, 4 096: 455 | 505 | 492, 6 144: 632 | 692 | 589, 8 192: 845 | 823 | 567)
-#define RMJ_ROWS1_MAX_GAMES 3584u
-#define RMJ_ROWS2_MAX_GAMES 7168u
+static_assert(rmjh::kStepRowsShift == STEP_F_ROWS_SHIFT, "rmj_host.h states the step kernels' rows flag position");
+
+// The step kernels of one player count, as typed pointers: Env and HeavyOrder are shared by rmj3 and rmj4, so an instantiation has the
+// same type in both.  A handle points at its player count's table from create on (rmj_env::kern).
+struct StepKernels {
+    decltype(&rmj4::k_step) step;
+    decltype(&rmj4::k_step4<false, 0>) step4[2][2];   // [LOOP][POL]
+    decltype(&rmj4::k_step4_queue<0>) queue[2];       // [POL]
+    decltype(&rmj4::k_step4_fixup<0>) fixup[2];       // [POL]
+    decltype(&rmj4::k_step4_enc<0>) enc;
+    decltype(&rmj4::k_step4_queue_enc<0>) queue_enc;
+    decltype(&rmj4::k_step4_fixup_enc<0>) fixup_enc;
+    decltype(&rmj4::k_step4_act_enc) act_enc;
+    decltype(&rmj4::k_step4_sample_enc) sample_enc;
+};
+// Where a template kernel is first named decides its place in the code object, and two tables filled one after the other cannot name
+// rmj3 and rmj4 in turns: this list, which nothing reads, names the instantiations in the order the code object has always kept them.
+[[maybe_unused]] static const void* const kStepKernelOrder[] = {
+    (void*)rmj3::k_step4<false, 1>, (void*)rmj3::k_step4<false, 0>, (void*)rmj4::k_step4<false, 1>, (void*)rmj4::k_step4<false, 0>,
+    (void*)rmj3::k_step4_queue<1>, (void*)rmj4::k_step4_queue<1>, (void*)rmj3::k_step4_queue<0>, (void*)rmj4::k_step4_queue<0>,
+    (void*)rmj3::k_step4_fixup<1>, (void*)rmj3::k_step4_fixup<0>, (void*)rmj4::k_step4_fixup<1>, (void*)rmj4::k_step4_fixup<0>,
+    (void*)rmj3::k_step4<true, 1>, (void*)rmj3::k_step4<true, 0>, (void*)rmj4::k_step4<true, 1>, (void*)rmj4::k_step4<true, 0>,
+    (void*)rmj3::k_step4_queue_enc<0>, (void*)rmj4::k_step4_queue_enc<0>, (void*)rmj3::k_step4_fixup_enc<0>, (void*)rmj4::k_step4_fixup_enc<0>,
+    (void*)rmj3::k_step4_enc<0>, (void*)rmj4::k_step4_enc<0>};
+#define RMJ_STEP_KERNELS(NS)                                                                                                            \
+    {NS::k_step, {{NS::k_step4<false, 0>, NS::k_step4<false, 1>}, {NS::k_step4<true, 0>, NS::k_step4<true, 1>}},                         \
+     {NS::k_step4_queue<0>, NS::k_step4_queue<1>}, {NS::k_step4_fixup<0>, NS::k_step4_fixup<1>}, NS::k_step4_enc<0>,                     \
+     NS::k_step4_queue_enc<0>, NS::k_step4_fixup_enc<0>, NS::k_step4_act_enc, NS::k_step4_sample_enc}
+static const StepKernels kStepKernels3 = RMJ_STEP_KERNELS(rmj3), kStepKernels4 = RMJ_STEP_KERNELS(rmj4);
 
 // ================================================================= host side
 static thread_local std::string g_err;
@@ -129,23 +149,13 @@ struct rmj_env {
     uint32_t ring = 0;
     float* d_decay = nullptr;  // expf(-0.2f * age), age 0..31, computed on the host (encode_extended)
     Grown scratch{Grown::DEVICE};   // staging buffer of the host-copy entry points (grown on demand to the exact size, never per call): scratch_for
-    int want_streams = 4;      // parts a multi-step device rollout is cut into (rmj_set_rollout_streams; RMJ_STEP_STREAMS at create)
-    int quad = 2;              // device-policy steps: 0 = one game per wave (k_step), 1 = four games per wave (k_step4), 2 = and a
-                               // rollout of >= 2 steps is ONE launch in which every wave steps its own games (k_step4<true>); RMJ_STEP4 at create
-    // long fused rollouts hand the work out in (quad, chunk) tickets to a grid that fits the chip once (k_step4_queue)
-    int queue_chunk = 32;      // calls per ticket (round 5: a ticket is a number of calls of the step function, profiles/r05_ticket_schedule_sweep.txt); RMJ_QUEUE_CHUNK at create, 0 = off (every wave keeps one quad for the rollout)
+    rmjh::RolloutTuning tune;          // what the rollouts are tuned to: read from the environment at create, rmj_set_rollout_streams
+    const StepKernels* kern = nullptr; // the step kernels of the handle's player count
     hipEvent_t ev_time[2] = {nullptr, nullptr};   // rmj_time_rollout* / rmj_bench_rollout: created with the handle, so that a timed region holds no event create / destroy
-    uint32_t* d_qheads = nullptr;   // [8][RMJ_Q_STRIDE] ticket counters, one line per XCD
+    uint32_t* d_qheads = nullptr;   // the ticket rollouts' counter sets and progress words (ticket_counters)
     uint32_t q_slots_pol[2] = {0, 0};   // waves of k_step4_queue<policy> the device holds at once (the greedy instantiation is compiled for fewer)
-    int queue_force = 0;            // RMJ_QUEUE_FORCE at create (tests): tickets for every batch of >= 64 quads
-    uint32_t queue_skip_xcds = 0;   // test hook: XCDs whose waves leave the queue kernel at once (RMJ_QUEUE_TEST_SKIP_XCDS at create)
     void* d_heavy = nullptr;        // heavy-first launch order of whole-batch per-step launches (HeavyOrder): two counters, lists, flag arrays
     uint32_t heavy_phase = 0;       // which half the next launch reads
-    int heavy_first = 1;            // RMJ_HEAVY_FIRST at create (0: plain block order)
-    uint32_t rows_pw = 4;           // games per wave of the non-ticket four-games-per-wave kernels: 4, or 2 / 1 for batches that leave the chip
-                                    // latency bound (chosen at create from the batch size; RMJ_ROWS overrides)
-    int queue_tail = 0;             // ticket lengths descend towards the expected end of a quad's rollout (q_ticket_plan); RMJ_QUEUE_TAIL=0: equal tickets
-    int queue_min_chunk = 5;        // shortest ticket (steps): a rollout of >= 2 tickets per quad runs as tickets; RMJ_QUEUE_MIN_CHUNK at create
     uint32_t max_xcc_id = 0;        // largest HW_REG_XCC_ID seen by a probe launch at create: the ticket rollout assumes ids 0..7 (one L2 per queue)
     uint32_t* d_ev_lost = nullptr;  // [n_games] records a game's ring lost to a late drain (rmj_drain_events), cumulative
     std::vector<struct rmj_ppo*> ppo;   // transition collectors bound to this handle (rmj_ppo_create): destroyed with it
@@ -165,7 +175,6 @@ struct rmj_env {
     Grown txt_work{Grown::DEVICE};  // sizes, stops and scan of the text calls (text_format_device lays it out)
     Grown h_txt{Grown::PINNED, true};   // pinned text (host delivery): headroom
     Grown h_txt_offs{Grown::PINNED};    // pinned text offsets [games + 1], then the new cursors
-    int enc_fused = 1;              // RMJ_ENC_FUSED at create: the step + encode rollout as ONE launch (k_step4_enc / k_step4_queue_enc); 0 = parts on streams
     uint32_t q_slots_enc = 0;       // waves of k_step4_queue_enc the device holds at once
     Grown det_claim{Grown::DEVICE}; // rmj_determinize_device: [n_games] u64 claim words (epoch << 32 | ~row), allocated and cleared by the handle's first call
     uint32_t det_epoch = 0;         // the last call's epoch: a word of an earlier call loses against any word of this one
@@ -388,6 +397,40 @@ static std::array<EnvSlab, 10> env_slabs(Env& d, size_t B = 0, size_t ring = 0) 
              {(void**)&d.status, B * sizeof(uint32_t), EnvSlab::NEVER}, {(void**)&d.events, B * ring * sizeof(RmjEvent), EnvSlab::LATE},
              {(void**)&d.win, B * 4 * sizeof(RmjWinResult), EnvSlab::AT_ALLOC}, {(void**)&d.wall_dg, B * 32, EnvSlab::AT_ALLOC}}};
 }
+// A per-step rollout: fn(stream, g0, g1) issues one step of games [g0, g1), n_steps times for each of the plan's k parts.  Games are
+// independent: each part advances on a stream of its own (header: rmj_step_random), forked from the handle's and joined back into it.
+template <class Fn>
+static int run_parts(rmj_env* h, const rmjh::RolloutPlan& p, uint32_t n_steps, Fn fn) {
+    // Side streams (and their join events) of the paths that split a batch over k streams - the per-step rollouts of RMJ_STEP4=0/1 builds and the unfused
+    // step + encode rollout.  Round 6: created on first use, not in rmj_create: the default paths (fused rollouts, one stream) never touch them, and every live
+    // stream makes hipDeviceSynchronize slower - with seven idle side streams the synchronisation behind the driver's 20-step window took ~45 us of a 0.78 ms
+    // region (scripts/r06_window_order.py: the same window between stream synchronisations ran at 1.76 G env.step/s, between device synchronisations at 1.66 G).
+    for (int i = 0; i < p.k - 1; i++) {
+        if (!h->xstream[i]) HIPCHK(hipStreamCreateWithFlags(&h->xstream[i], hipStreamNonBlocking));
+        if (!h->ev_join[i]) HIPCHK(hipEventCreateWithFlags(&h->ev_join[i], hipEventDisableTiming));
+    }
+    if (p.k >= 2) HIPCHK(hipEventRecord(h->ev_fork, h->stream));
+    for (int i = 1; i < p.k; i++) HIPCHK(hipStreamWaitEvent(h->xstream[i - 1], h->ev_fork, 0));
+    for (uint32_t s = 0; s < n_steps; s++)
+        for (int i = 0; i < p.k; i++) fn(i ? h->xstream[i - 1] : h->stream, p.part(i), p.part(i + 1));
+    for (int i = 1; i < p.k; i++) {
+        HIPCHK(hipEventRecord(h->ev_join[i - 1], h->xstream[i - 1]));
+        HIPCHK(hipStreamWaitEvent(h->stream, h->ev_join[i - 1], 0));
+    }
+    return RMJ_OK;
+}
+// The plan of a rollout on this handle (rmjh::rollout_plan is the one place that decides how a rollout runs).  *slots caches the
+// waves of the rollout's ticket kernel the device holds at once: asked of the runtime at most once per handle and kernel, and only
+// by a call that would otherwise run as tickets.  A query that fails leaves need_slots set in the plan of the rollout without tickets.
+template <class Kernel>
+static rmjh::RolloutPlan plan_rollout(rmj_env* h, uint32_t n_steps, int pol, bool encode, int only_active, Kernel ticket_kernel, uint32_t* slots) {
+    const auto plan = [&] { return rmjh::rollout_plan(h->tune, h->cfg.n_games, n_steps, pol, encode, only_active, *slots, h->max_xcc_id); };
+    int per_cu = 0, cus = 0;
+    if (plan().need_slots && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ticket_kernel, 64, 0) == hipSuccess &&
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->cfg.device) == hipSuccess)
+        *slots = (uint32_t)(per_cu > 0 ? per_cu : 1) * (uint32_t)(cus > 0 ? cus : 1);
+    return plan();
+}
 // (defined in its section: ahead of rmj_step_random_encode it would put k_encode_base before the fused step kernels in the code object)
 static void launch_encode_base_range(rmj_env* h, hipStream_t st, int only_active, float* d_out, uint32_t g0, uint32_t g1);
 
@@ -407,23 +450,25 @@ static int create_impl(rmj_env* h, const RmjConfig* cfg, uint64_t** d_seeds_out)
     uint32_t r2 = 64;
     while (r2 < ring) r2 <<= 1;
     h->ring = r2;
-    if (const char* e = getenv("RMJ_STEP_STREAMS")) h->want_streams = atoi(e);
-    if (const char* e = getenv("RMJ_STEP4")) h->quad = atoi(e);
-    if (const char* e = getenv("RMJ_QUEUE_CHUNK")) h->queue_chunk = atoi(e);
-    if (const char* e = getenv("RMJ_QUEUE_FORCE")) h->queue_force = atoi(e);
-    if (const char* e = getenv("RMJ_QUEUE_TEST_SKIP_XCDS")) h->queue_skip_xcds = (uint32_t)strtoul(e, nullptr, 0) & 0xFFu;
-    if (const char* e = getenv("RMJ_QUEUE_TAIL")) h->queue_tail = atoi(e) != 0;
-    if (const char* e = getenv("RMJ_QUEUE_MIN_CHUNK")) h->queue_min_chunk = atoi(e) > 0 ? atoi(e) : 1;
-    if (const char* e = getenv("RMJ_HEAVY_FIRST")) h->heavy_first = atoi(e);
-    h->rows_pw = cfg->n_games <= RMJ_ROWS1_MAX_GAMES ? 1u : (cfg->n_games <= RMJ_ROWS2_MAX_GAMES ? 2u : 4u);
-    if (const char* e = getenv("RMJ_ROWS")) { const int r = atoi(e); if (r == 1 || r == 2 || r == 4) h->rows_pw = (uint32_t)r; }
-    if (const char* e = getenv("RMJ_ENC_FUSED")) h->enc_fused = atoi(e);
+    rmjh::RolloutTuning& t = h->tune;
+    if (const char* e = getenv("RMJ_STEP_STREAMS")) t.want_streams = atoi(e);
+    if (const char* e = getenv("RMJ_STEP4")) t.quad = atoi(e);
+    if (const char* e = getenv("RMJ_QUEUE_CHUNK")) t.queue_chunk = atoi(e);
+    if (const char* e = getenv("RMJ_QUEUE_FORCE")) t.queue_force = atoi(e);
+    if (const char* e = getenv("RMJ_QUEUE_TEST_SKIP_XCDS")) t.queue_skip_xcds = (uint32_t)strtoul(e, nullptr, 0) & 0xFFu;
+    if (const char* e = getenv("RMJ_QUEUE_TAIL")) t.queue_tail = atoi(e) != 0;
+    if (const char* e = getenv("RMJ_QUEUE_MIN_CHUNK")) t.queue_min_chunk = atoi(e) > 0 ? atoi(e) : 1;
+    if (const char* e = getenv("RMJ_HEAVY_FIRST")) t.heavy_first = atoi(e);
+    t.rows_pw = rmjh::rows_for_batch(cfg->n_games);
+    if (const char* e = getenv("RMJ_ROWS")) { const int r = atoi(e); if (r == 1 || r == 2 || r == 4) t.rows_pw = (uint32_t)r; }
+    if (const char* e = getenv("RMJ_ENC_FUSED")) t.enc_fused = atoi(e);
+    h->kern = cfg->game_mode >= 3 ? &kStepKernels3 : &kStepKernels4;
     const size_t B = cfg->n_games;
     Env& d = h->d;
     HIPCHK(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
     h->stream = h->own_stream;
     HIPCHK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-    // (the side streams of the split paths are created when such a path first runs: ensure_side_streams)
+    // (the side streams of the split paths are created when such a path first runs: run_parts)
     // the two events of rmj_time_rollout* / rmj_bench_rollout: here, not at their first use - the driver's timed region IS their first use, and two
     // hipEventCreate calls between its host timestamps cost the 20-step window ~4 % (round 6, scripts/r06_window_order.py: first window 1.65-1.69 G, later ones 1.76 G)
     for (int i = 0; i < 2; i++) HIPCHK(hipEventCreate(&h->ev_time[i]));
@@ -437,7 +482,7 @@ static int create_impl(rmj_env* h, const RmjConfig* cfg, uint64_t** d_seeds_out)
     {   // The ticket rollout (k_step4_queue) hands a quad from wave to wave through ONE XCD's L2 and keys its eight queues by
         // HW_REG_XCC_ID & 7: on a part or partition mode that reports ids >= 8 two XCDs would share a queue and the hand-over
         // would cross L2s without a write-back.  A probe launch (more blocks than any dispatcher keeps on one XCD) records the
-        // largest id; tickets are used only when it is <= 7 (rollout_queued), k_step4<true> otherwise.
+        // largest id; tickets are used only when it is <= 7 (rmjh::rollout_plan), k_step4<true> otherwise.
         HIPCHK(hipMemsetAsync(h->d_counter, 0, sizeof(unsigned long long), h->stream));
         hipLaunchKernelGGL(k_probe_xcc, dim3(4096), dim3(64), 0, h->stream, h->d_counter);
         HIPCHK(hipGetLastError());
@@ -509,8 +554,8 @@ int rmj_destroy(rmj_handle h) {
     hipSetDevice(h->cfg.device);
     if (h->stream) hipStreamSynchronize(h->stream);
     for (const EnvSlab& s : env_slabs(h->d)) hipFree(*s.p);
-    for (void* p : {(void*)h->d_decay, (void*)h->d_actions, (void*)h->d_counter, (void*)h->d_obs_offs, (void*)h->d_env, (void*)h->d_qheads /* (and d_qdone behind it) */,
-                    (void*)h->d_ev_lost, h->d_track, h->d_heavy})
+    for (void* p : {(void*)h->d_decay, (void*)h->d_actions, (void*)h->d_counter, (void*)h->d_obs_offs, (void*)h->d_env, (void*)h->d_qheads, (void*)h->d_ev_lost,
+                    h->d_track, h->d_heavy})
         hipFree(p);
     while (!h->ppo.empty()) rmj_ppo_destroy(h->ppo.back());
     while (!h->logreplay.empty()) rmj_logreplay_destroy(h->logreplay.back());
@@ -536,15 +581,7 @@ int rmj_clone(rmj_handle h, rmj_handle* out) {
     rmj_handle c = nullptr;
     int rc = rmj_create(&cfg, &c);
     if (rc) return rc;
-    c->want_streams = h->want_streams;
-    c->quad = h->quad;
-    c->queue_chunk = h->queue_chunk;
-    c->queue_force = h->queue_force;
-    c->queue_min_chunk = h->queue_min_chunk;
-    c->queue_tail = h->queue_tail;
-    c->rows_pw = h->rows_pw;
-    c->heavy_first = h->heavy_first;
-    c->enc_fused = h->enc_fused;
+    c->tune = h->tune;
     if (h->d.enc_stride != c->d.enc_stride) { int rc2 = rmj_set_encode_row_stride(c, h->d.enc_stride); if (rc2) { rmj_destroy(c); return rc2; } }
     const size_t B = h->cfg.n_games, ring = (size_t)h->d.ring_mask + 1u;
     const auto from = env_slabs(h->d, B, ring), to = env_slabs(c->d, B, ring);
@@ -621,46 +658,42 @@ int rmj_reset(rmj_handle h, const uint8_t* select, const uint8_t* walls, const u
     return RMJ_OK;
 }
 
+// Whole-batch per-step launches in heavy-first order (HeavyOrder): the previous launch's notes name the units that will end a round,
+// restart or may settle a Ron - they get the first blocks.  The order of the handle's next launch of `units` units; without the
+// buffer (allocated here on first use), the plain order.
+static const HeavyOrder kPlainOrder = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u};
+static HeavyOrder next_heavy_order(rmj_env* h, hipStream_t st, uint32_t units) {
+    HeavyOrder ho = kPlainOrder;
+    const uint32_t front = units / 4u;
+    const size_t o_list = 384, o_flag = o_list + 2 * (size_t)front * 4, bytes = o_flag + 2 * (size_t)units;   // three counters, a line each
+    if (!h->d_heavy) {
+        if (hipMalloc(&h->d_heavy, bytes) == hipSuccess) hipMemsetAsync(h->d_heavy, 0, bytes, st);
+        else h->d_heavy = nullptr;
+    }
+    if (h->d_heavy) {
+        uint8_t* b = (uint8_t*)h->d_heavy;
+        const uint32_t k = h->heavy_phase, in = k & 1u, out = in ^ 1u;
+        ho.in_cnt = (const uint32_t*)(b + 128 * (k % 3u)); ho.out_cnt = (uint32_t*)(b + 128 * ((k + 1u) % 3u)); ho.zero_cnt = (uint32_t*)(b + 128 * ((k + 2u) % 3u));
+        ho.in_list = (const uint32_t*)(b + o_list) + (size_t)front * in; ho.out_list = (uint32_t*)(b + o_list) + (size_t)front * out;
+        ho.in_flag = b + o_flag + (size_t)units * in; ho.out_flag = b + o_flag + (size_t)units * out;
+        ho.front = front;
+        h->heavy_phase = (k + 1u) % 6u;   // (period of the counter and the list rotation)
+    }
+    return ho;
+}
 // one k_step launch over games [g0, g1) of the handle
 static inline void launch_step_range(rmj_env* h, hipStream_t st, const uint64_t* d_actions, uint64_t policy_seed, uint32_t flags,
                                      uint32_t g0, uint32_t g1) {
-    const bool greedy = (flags & STEP_F_GREEDY) != 0u;   // (four-games-per-wave kernels only: the callers check h->quad)
-    if (h->quad) {   // four games per wave (device policy, packed actions or action ids); small batches: two or one (rows_pw)
-        const uint32_t rows = h->rows_pw;
-        flags |= (rows == 4u ? 0u : rows) << STEP_F_ROWS_SHIFT;
-        const uint32_t units = (g1 - g0 + rows - 1u) / rows;
-        // whole-batch launches in heavy-first order (HeavyOrder): the previous launch's notes name the units that will end a round,
-        // restart or may settle a Ron - they get the first blocks
-        HeavyOrder ho = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u};
-        if (h->heavy_first && g0 == 0u && g1 == h->cfg.n_games && units >= 2048u) {
-            const uint32_t front = units / 4u;
-            const size_t o_list = 384, o_flag = o_list + 2 * (size_t)front * 4, bytes = o_flag + 2 * (size_t)units;   // three counters, a line each
-            if (!h->d_heavy) {
-                if (hipMalloc(&h->d_heavy, bytes) == hipSuccess) hipMemsetAsync(h->d_heavy, 0, bytes, st);
-                else h->d_heavy = nullptr;
-            }
-            if (h->d_heavy) {
-                uint8_t* b = (uint8_t*)h->d_heavy;
-                const uint32_t k = h->heavy_phase, in = k & 1u, out = in ^ 1u;
-                ho.in_cnt = (const uint32_t*)(b + 128 * (k % 3u)); ho.out_cnt = (uint32_t*)(b + 128 * ((k + 1u) % 3u)); ho.zero_cnt = (uint32_t*)(b + 128 * ((k + 2u) % 3u));
-                ho.in_list = (const uint32_t*)(b + o_list) + (size_t)front * in; ho.out_list = (uint32_t*)(b + o_list) + (size_t)front * out;
-                ho.in_flag = b + o_flag + (size_t)units * in; ho.out_flag = b + o_flag + (size_t)units * out;
-                ho.front = front;
-                h->heavy_phase = (k + 1u) % 6u;   // (period of the counter and the list rotation)
-            }
-        }
-        const dim3 grid(units + ho.front);
-        if (h->cfg.game_mode >= 3) {
-            if (greedy) hipLaunchKernelGGL((rmj3::k_step4<false, 1>), grid, dim3(64), 0, st, (const Env*)h->d_env, policy_seed, flags, g0, g1, 1u, d_actions, ho);
-            else hipLaunchKernelGGL((rmj3::k_step4<false, 0>), grid, dim3(64), 0, st, (const Env*)h->d_env, policy_seed, flags, g0, g1, 1u, d_actions, ho);
-        } else {
-            if (greedy) hipLaunchKernelGGL((rmj4::k_step4<false, 1>), grid, dim3(64), 0, st, (const Env*)h->d_env, policy_seed, flags, g0, g1, 1u, d_actions, ho);
-            else hipLaunchKernelGGL((rmj4::k_step4<false, 0>), grid, dim3(64), 0, st, (const Env*)h->d_env, policy_seed, flags, g0, g1, 1u, d_actions, ho);
-        }
+    if (!h->tune.quad) {
+        hipLaunchKernelGGL(h->kern->step, step_grid(g1 - g0), dim3(64 * RMJ_STEP_WPB), 0, st, (const Env*)h->d_env, d_actions, policy_seed, flags, g0, g1);
         return;
     }
-    if (h->cfg.game_mode >= 3) hipLaunchKernelGGL(rmj3::k_step, step_grid(g1 - g0), dim3(64 * RMJ_STEP_WPB), 0, st, (const Env*)h->d_env, d_actions, policy_seed, flags, g0, g1);
-    else hipLaunchKernelGGL(rmj4::k_step, step_grid(g1 - g0), dim3(64 * RMJ_STEP_WPB), 0, st, (const Env*)h->d_env, d_actions, policy_seed, flags, g0, g1);
+    // four games per wave (device policy, packed actions or action ids); small batches: two or one (rows_pw)
+    const uint32_t rows = h->tune.rows_pw, units = (g1 - g0 + rows - 1u) / rows;
+    const HeavyOrder ho = h->tune.heavy_first && rmjh::heavy_first_eligible(h->cfg.n_games, rows, g0, g1) ? next_heavy_order(h, st, units) : kPlainOrder;
+    const int pol = (flags & STEP_F_GREEDY) != 0u;   // (four-games-per-wave kernels only: the callers check tune.quad)
+    hipLaunchKernelGGL(h->kern->step4[0][pol], dim3(units + ho.front), dim3(64), 0, st, (const Env*)h->d_env, policy_seed,
+                       flags | rmjh::rows_flag_bits(rows), g0, g1, 1u, d_actions, ho);
 }
 int rmj_step_device(rmj_handle h, const rmj_action_t* d_actions) {
     if (!h || !d_actions) return fail(RMJ_ERR_ARG, "null argument");
@@ -684,36 +717,35 @@ int rmj_step_ids_device(rmj_handle h, const int32_t* d_action_ids, int auto_rese
 // action ids, then Observation.encode() of the seats that are to act next into the resident tensor d_out [n][4][74][W].
 int rmj_step_ids_encode_device(rmj_handle h, const int32_t* d_action_ids, int auto_reset, float* d_out) {
     if (!h || !d_action_ids || !d_out) return fail(RMJ_ERR_ARG, "null argument");
-    if (!h->quad) return fail(RMJ_ERR_ARG, "rmj_step_ids_encode_device runs in the four-games-per-wave kernels (RMJ_STEP4=0 selects the one-game kernel)");
+    if (!h->tune.quad) return fail(RMJ_ERR_ARG, "rmj_step_ids_encode_device runs in the four-games-per-wave kernels (RMJ_STEP4=0 selects the one-game kernel)");
     HIPCHK(hipSetDevice(h->cfg.device));
     const uint32_t flags = STEP_F_IDS | (auto_reset ? STEP_F_AUTORESET : 0u);
     const uint32_t n = h->cfg.n_games;
-    const dim3 grid((n + 3u) / 4u);
-    if (h->cfg.game_mode >= 3) hipLaunchKernelGGL(rmj3::k_step4_act_enc, grid, dim3(64), 0, h->stream, (const Env*)h->d_env, flags, 0u, n, reinterpret_cast<const uint64_t*>(d_action_ids), d_out);
-    else hipLaunchKernelGGL(rmj4::k_step4_act_enc, grid, dim3(64), 0, h->stream, (const Env*)h->d_env, flags, 0u, n, reinterpret_cast<const uint64_t*>(d_action_ids), d_out);
+    hipLaunchKernelGGL(h->kern->act_enc, dim3((n + 3u) / 4u), dim3(64), 0, h->stream, (const Env*)h->d_env, flags, 0u, n, reinterpret_cast<const uint64_t*>(d_action_ids), d_out);
     HIPCHK(hipGetLastError());
     return RMJ_OK;
+}
+// the rows of the logits, where the caller gives any, hold the handle's whole action space
+static int check_logits_stride(const rmj_env* h, const float* d_logits, uint32_t stride) {
+    const uint32_t A = h->cfg.game_mode >= 3 ? RMJ_ACTION_SPACE_3P : RMJ_ACTION_SPACE_4P;
+    return d_logits && stride < A ? fail(RMJ_ERR_ARG, "logits row shorter than the action space") : RMJ_OK;
 }
 // rmj_sample_ids_device + rmj_step_ids_encode_device as ONE launch (k_step4_sample_enc): every wave draws the ids of its own four games
 // (the same keyed draw: identical ids, written to d_ids for the caller), steps them and encodes the seats that act next.
 int rmj_step_sample_encode_device(rmj_handle h, const float* d_logits, uint32_t stride, uint64_t seed, int auto_reset, int32_t* d_ids, float* d_out) {
     if (!h || !d_ids || !d_out) return fail(RMJ_ERR_ARG, "null argument");
-    if (!h->quad) return fail(RMJ_ERR_ARG, "rmj_step_sample_encode_device runs in the four-games-per-wave kernels (RMJ_STEP4=0 selects the one-game kernel)");
-    const uint32_t A = h->cfg.game_mode >= 3 ? RMJ_ACTION_SPACE_3P : RMJ_ACTION_SPACE_4P;
-    if (d_logits && stride < A) return fail(RMJ_ERR_ARG, "logits row shorter than the action space");
+    if (!h->tune.quad) return fail(RMJ_ERR_ARG, "rmj_step_sample_encode_device runs in the four-games-per-wave kernels (RMJ_STEP4=0 selects the one-game kernel)");
+    if (int rc = check_logits_stride(h, d_logits, stride)) return rc;
     HIPCHK(hipSetDevice(h->cfg.device));
     const uint32_t flags = STEP_F_IDS | (auto_reset ? STEP_F_AUTORESET : 0u);
     const uint32_t n = h->cfg.n_games;
-    const dim3 grid((n + 3u) / 4u);
-    if (h->cfg.game_mode >= 3) hipLaunchKernelGGL(rmj3::k_step4_sample_enc, grid, dim3(64), 0, h->stream, (const Env*)h->d_env, flags, 0u, n, d_logits, stride, seed, d_ids, d_out);
-    else hipLaunchKernelGGL(rmj4::k_step4_sample_enc, grid, dim3(64), 0, h->stream, (const Env*)h->d_env, flags, 0u, n, d_logits, stride, seed, d_ids, d_out);
+    hipLaunchKernelGGL(h->kern->sample_enc, dim3((n + 3u) / 4u), dim3(64), 0, h->stream, (const Env*)h->d_env, flags, 0u, n, d_logits, stride, seed, d_ids, d_out);
     HIPCHK(hipGetLastError());
     return RMJ_OK;
 }
 int rmj_sample_ids_device(rmj_handle h, const float* d_logits, uint32_t stride, uint64_t seed, int32_t* d_ids) {
     if (!h || !d_ids) return fail(RMJ_ERR_ARG, "null argument");
-    const uint32_t A = h->cfg.game_mode >= 3 ? RMJ_ACTION_SPACE_3P : RMJ_ACTION_SPACE_4P;
-    if (d_logits && stride < A) return fail(RMJ_ERR_ARG, "logits row shorter than the action space");
+    if (int rc = check_logits_stride(h, d_logits, stride)) return rc;
     HIPCHK(hipSetDevice(h->cfg.device));
     const uint32_t n = h->cfg.n_games;
     hipLaunchKernelGGL(k_sample_ids, dim3((n + 15) / 16), dim3(256), 0, h->stream, h->d, d_logits, stride, seed, d_ids);
@@ -722,8 +754,7 @@ int rmj_sample_ids_device(rmj_handle h, const float* d_logits, uint32_t stride, 
 }
 int rmj_select_ids_device(rmj_handle h, const float* d_logits, uint32_t stride, uint64_t seed, const uint8_t* d_hero, int32_t* d_ids) {
     if (!h || !d_ids) return fail(RMJ_ERR_ARG, "null argument");
-    const uint32_t A = h->cfg.game_mode >= 3 ? RMJ_ACTION_SPACE_3P : RMJ_ACTION_SPACE_4P;
-    if (d_logits && stride < A) return fail(RMJ_ERR_ARG, "logits row shorter than the action space");
+    if (int rc = check_logits_stride(h, d_logits, stride)) return rc;
     HIPCHK(hipSetDevice(h->cfg.device));
     const uint32_t n = h->cfg.n_games;
     hipLaunchKernelGGL(k_select_ids, dim3((n + 15) / 16), dim3(256), 0, h->stream, h->d, d_logits, stride, seed, d_hero, d_ids);
@@ -813,133 +844,52 @@ int rmj_step(rmj_handle h, const rmj_action_t* actions) {
     HIPCHK(hipMemcpy(h->d_actions, actions, (size_t)h->cfg.n_games * 4 * sizeof(uint64_t), hipMemcpyHostToDevice));
     return rmj_step_device(h, h->d_actions);
 }
-// streams a device rollout of n_steps steps uses (RMJ_STEP_STREAMS=1 keeps everything on one stream)
-static int rollout_streams(const rmj_env* h, uint32_t n_steps) {
-    const int want = h->want_streams;
-    if (h->quad >= 2 && n_steps >= 2 && want >= 2) return 1;   // the fused rollout: one launch, no parts
-    if (want < 2 || n_steps < 2 || h->cfg.n_games < RMJ_SPLIT_MIN_GAMES) return 1;
-    int k = want > RMJ_MAX_ROLLOUT_STREAMS ? RMJ_MAX_ROLLOUT_STREAMS : want;
-    const int fit = (int)(h->cfg.n_games / RMJ_SPLIT_MIN_PART);
-    return k > fit ? fit : k;
-}
-// Side streams (and their join events) of the paths that split a batch over k streams - the per-step rollouts of RMJ_STEP4=0/1 builds and the unfused
-// step + encode rollout.  Round 6: created on first use, not in rmj_create: the default paths (fused rollouts, one stream) never touch them, and every live
-// stream makes hipDeviceSynchronize slower - with seven idle side streams the synchronisation behind the driver's 20-step window took ~45 us of a 0.78 ms
-// region (scripts/r06_window_order.py: the same window between stream synchronisations ran at 1.76 G env.step/s, between device synchronisations at 1.66 G).
-static int ensure_side_streams(rmj_env* h, int k) {
-    for (int i = 0; i < k - 1 && i < RMJ_MAX_ROLLOUT_STREAMS - 1; i++) {
-        if (!h->xstream[i]) HIPCHK(hipStreamCreateWithFlags(&h->xstream[i], hipStreamNonBlocking));
-        if (!h->ev_join[i]) HIPCHK(hipEventCreateWithFlags(&h->ev_join[i], hipEventDisableTiming));
+// The ticket rollouts' counters, one allocation made and zeroed by the handle's first ticket rollout: three sets of ticket counters (one
+// line per XCD) + the quads' ticket counts, and behind them the games' step counts of the running rollout, carried from ticket to
+// ticket (*prog: written before it is read).  Set 0 is the step rollout's: zeroed once here and re-armed by every k_step4_fixup launch
+// behind its ticket launch, so no memset sits between rollouts and a captured rollout can be replayed (round 6; round 5 alternated two
+// sets from the host, which a graph replay of one launch found exhausted).  Set 2 is the step + encode rollout's, which memsets it in
+// front of every rollout.
+static int ticket_counters(rmj_env* h, int set, uint32_t** heads, uint32_t** done, uint32_t** prog) {
+    const size_t quads = (h->cfg.n_games + 3u) / 4u, set_words = 8 * RMJ_Q_STRIDE + quads;
+    if (!h->d_qheads) {
+        HIPCHK(hipMalloc(&h->d_qheads, (3 * set_words + quads * 4) * sizeof(uint32_t)));
+        HIPCHK(hipMemsetAsync(h->d_qheads, 0, 3 * set_words * sizeof(uint32_t), h->stream));
     }
+    *heads = h->d_qheads + set * set_words;
+    *done = *heads + 8 * RMJ_Q_STRIDE;
+    *prog = h->d_qheads + 3 * set_words;
+    if (set == 2) HIPCHK(hipMemsetAsync(*heads, 0, set_words * sizeof(uint32_t), h->stream));
     return RMJ_OK;
 }
-// Does a fused rollout of n_steps run as tickets (k_step4_queue)?  Worth it when the batch is more than one and fewer than eight
-// chip-fulls of waves: below, every quad is resident at once and there is no tail; far above, the tail is a small share and the
-// chunk hand-overs cost more than it (524 288 games: -2 %).
-// steps per ticket: the configured chunk, shorter for a short rollout (its tail is one chunk long: at least 16 chunks per quad)
-static uint32_t rollout_chunk(const rmj_env* h, uint32_t n_steps) {
-    uint32_t cap = (uint32_t)h->queue_chunk;
-    const uint32_t lo = (uint32_t)h->queue_min_chunk, fine = n_steps / 16u < lo ? lo : n_steps / 16u;
-    if (cap < (n_steps + 39u) / 40u) cap = (n_steps + 39u) / 40u;   // at most 64 tickets per quad (q_ticket_plan)
-    return fine < cap ? fine : cap;
-}
-static bool rollout_queued(rmj_env* h, uint32_t n_steps, int pol) {
-    const uint32_t quads = (h->cfg.n_games + 3u) / 4u;
-    if (!(h->quad >= 2 && n_steps >= 2 && h->want_streams >= 2) || h->queue_chunk <= 0 || n_steps < 2u * rollout_chunk(h, n_steps)) return false;
-    if (h->max_xcc_id > 7u) return false;   // more XCC ids than queues: no single L2 per queue (see rmj_create)
-    pol = pol == 1 ? 1 : 0;
-    if (h->q_slots_pol[pol] == 0) {
-        int per_cu = 0, cus = 0;
-        const bool sanma = h->cfg.game_mode >= 3;
-        const hipError_t e = pol == 1 ? (sanma ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rmj3::k_step4_queue<1>, 64, 0)
-                                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rmj4::k_step4_queue<1>, 64, 0))
-                                      : (sanma ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rmj3::k_step4_queue<0>, 64, 0)
-                                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rmj4::k_step4_queue<0>, 64, 0));
-        if (e != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->cfg.device) != hipSuccess) return false;
-        h->q_slots_pol[pol] = (uint32_t)(per_cu > 0 ? per_cu : 1) * (uint32_t)(cus > 0 ? cus : 1);
-    }
-    const uint32_t slots = h->q_slots_pol[pol];
-    if (h->queue_force) return quads >= 64u;   // RMJ_QUEUE_FORCE=1 (tests): any batch with a quad per XCD queue to spare
-    return quads > slots && quads < 8u * slots;
-}
-// device-policy rollout: pol 0 = RandomAgent (rmj_step_random), 1 = the greedy policy (rmj_step_greedy)
-#define RMJ_LAUNCH_POL(NS, KERNEL, POL, ...)                                              \
-    do {                                                                                  \
-        if ((POL) == 1) hipLaunchKernelGGL((NS::KERNEL<1>), __VA_ARGS__);                 \
-        else hipLaunchKernelGGL((NS::KERNEL<0>), __VA_ARGS__);                            \
-    } while (0)
-#define RMJ_LAUNCH_LOOP_POL(NS, POL, ...)                                                 \
-    do {                                                                                  \
-        if ((POL) == 1) hipLaunchKernelGGL((NS::k_step4<true, 1>), __VA_ARGS__);          \
-        else hipLaunchKernelGGL((NS::k_step4<true, 0>), __VA_ARGS__);                     \
-    } while (0)
-static int step_policy_impl(rmj_handle h, uint64_t policy_seed, uint32_t n_steps, int auto_reset, int pol, uint32_t call_rate) {
+// device-policy rollout: pol 0 = RandomAgent (rmj_step_random), 1 = the greedy policy (rmj_step_greedy); ran: the plan it executed
+static int step_policy_impl(rmj_handle h, uint64_t policy_seed, uint32_t n_steps, int auto_reset, int pol, uint32_t call_rate, rmjh::RolloutPlan* ran = nullptr) {
     if (!h) return fail(RMJ_ERR_ARG, "null handle");
     HIPCHK(hipSetDevice(h->cfg.device));
     uint32_t flags = STEP_F_RANDOM | (auto_reset ? STEP_F_AUTORESET : 0u);
     if (pol == 1) {
-        if (!h->quad) return fail(RMJ_ERR_ARG, "the greedy device policy runs in the four-games-per-wave kernels (RMJ_STEP4=0 selects the one-game kernel)");
+        if (!h->tune.quad) return fail(RMJ_ERR_ARG, "the greedy device policy runs in the four-games-per-wave kernels (RMJ_STEP4=0 selects the one-game kernel)");
         flags |= STEP_F_GREEDY | ((call_rate > 255u ? 255u : call_rate) << 8);
     }
+    const StepKernels& K = *h->kern;
+    const Env* const E = h->d_env;
     const uint32_t n = h->cfg.n_games;
-    const bool sanma = h->cfg.game_mode >= 3;
-    if (h->quad >= 2 && n_steps >= 2 && h->want_streams >= 2) {   // (rmj_set_rollout_streams(h, 1): one launch per step, one stream)
+    // (when the occupancy query fails the plan is the plain fused launch)
+    const rmjh::RolloutPlan p = plan_rollout(h, n_steps, pol, false, 0, K.queue[pol == 1], &h->q_slots_pol[pol == 1]);
+    if (p.how == rmjh::RolloutPlan::TICKETS) {
+        // a long rollout of a batch that does not fill the chip a whole number of times, in (quad, chunk) tickets
+        uint32_t *heads, *done, *prog;
+        if (int rc = ticket_counters(h, 0, &heads, &done, &prog)) return rc;
+        hipLaunchKernelGGL(K.queue[p.pol], dim3(p.grid_tickets), dim3(64), 0, h->stream, E, policy_seed, flags, n, n_steps, p.chunk, heads, done, h->tune.queue_skip_xcds, prog, (uint32_t)h->tune.queue_tail);
+        hipLaunchKernelGGL(K.fixup[p.pol], dim3(p.grid_fixup), dim3(64), 0, h->stream, E, policy_seed, flags, n, n_steps, done);
+    } else if (p.how == rmjh::RolloutPlan::FUSED) {
         // four games per wave, the whole rollout in ONE launch: every wave steps its own games n_steps times (k_step4<true>)
-        const dim3 grid((n + 3u) / 4u);
-        if (rollout_queued(h, n_steps, pol)) {
-            // ... or, for a long rollout of a batch that does not fill the chip a whole number of times, in (quad, chunk) tickets
-            // ticket counters (one line per XCD) + the quads' ticket counts: one set for this rollout - zeroed once here, re-armed by every
-            // k_step4_fixup launch behind its ticket launch, so no memset sits between rollouts and a captured rollout can be replayed (round 6;
-            // round 5 alternated two sets from the host, which a graph replay of one launch found exhausted) - and one for the step + encode
-            // rollout (which memsets its own); behind them the games' step counts of the running rollout, carried from ticket to ticket
-            const size_t set_words = 8 * RMJ_Q_STRIDE + (size_t)grid.x;
-            if (!h->d_qheads) {
-                HIPCHK(hipMalloc(&h->d_qheads, (3 * set_words + (size_t)grid.x * 4) * sizeof(uint32_t)));
-                HIPCHK(hipMemsetAsync(h->d_qheads, 0, 3 * set_words * sizeof(uint32_t), h->stream));
-            }
-            uint32_t* const heads = h->d_qheads;
-            uint32_t* const done = heads + 8 * RMJ_Q_STRIDE;
-            uint32_t* const d_qprog = h->d_qheads + 3 * set_words;   // (written before it is read)
-            const dim3 gq(grid.x < h->q_slots_pol[pol == 1 ? 1 : 0] ? grid.x : h->q_slots_pol[pol == 1 ? 1 : 0]);
-            const dim3 gfix((grid.x + 63u) / 64u);
-            const uint32_t chunk = rollout_chunk(h, n_steps);
-            if (sanma) {
-                RMJ_LAUNCH_POL(rmj3, k_step4_queue, pol, gq, dim3(64), 0, h->stream, (const Env*)h->d_env, policy_seed, flags, n, n_steps, chunk, heads, done, h->queue_skip_xcds, d_qprog, (uint32_t)h->queue_tail);
-                RMJ_LAUNCH_POL(rmj3, k_step4_fixup, pol, gfix, dim3(64), 0, h->stream, (const Env*)h->d_env, policy_seed, flags, n, n_steps, done);
-            } else {
-                RMJ_LAUNCH_POL(rmj4, k_step4_queue, pol, gq, dim3(64), 0, h->stream, (const Env*)h->d_env, policy_seed, flags, n, n_steps, chunk, heads, done, h->queue_skip_xcds, d_qprog, (uint32_t)h->queue_tail);
-                RMJ_LAUNCH_POL(rmj4, k_step4_fixup, pol, gfix, dim3(64), 0, h->stream, (const Env*)h->d_env, policy_seed, flags, n, n_steps, done);
-            }
-            HIPCHK(hipGetLastError());
-            return RMJ_OK;
-        }
-        const uint32_t rows = h->rows_pw;
-        const dim3 grid_r((n + rows - 1u) / rows);
-        flags |= (rows == 4u ? 0u : rows) << STEP_F_ROWS_SHIFT;
-        const HeavyOrder no_order = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u};
-        if (sanma) RMJ_LAUNCH_LOOP_POL(rmj3, pol, grid_r, dim3(64), 0, h->stream, (const Env*)h->d_env, policy_seed, flags, 0u, n, n_steps, (const uint64_t*)nullptr, no_order);
-        else RMJ_LAUNCH_LOOP_POL(rmj4, pol, grid_r, dim3(64), 0, h->stream, (const Env*)h->d_env, policy_seed, flags, 0u, n, n_steps, (const uint64_t*)nullptr, no_order);
-        HIPCHK(hipGetLastError());
-        return RMJ_OK;
-    }
-    const int k = rollout_streams(h, n_steps);
-    if (k >= 2) {
-        // games are independent: each part advances n_steps steps on its own stream (header: rmj_step_random)
-        if (int rc = ensure_side_streams(h, k)) return rc;
-        HIPCHK(hipEventRecord(h->ev_fork, h->stream));
-        for (int i = 1; i < k; i++) HIPCHK(hipStreamWaitEvent(h->xstream[i - 1], h->ev_fork, 0));
-        for (uint32_t s = 0; s < n_steps; s++)
-            for (int i = 0; i < k; i++)
-                launch_step_range(h, i ? h->xstream[i - 1] : h->stream, nullptr, policy_seed, flags,
-                                  (uint32_t)((uint64_t)n * i / k), (uint32_t)((uint64_t)n * (i + 1) / k));
-        for (int i = 1; i < k; i++) {
-            HIPCHK(hipEventRecord(h->ev_join[i - 1], h->xstream[i - 1]));
-            HIPCHK(hipStreamWaitEvent(h->stream, h->ev_join[i - 1], 0));
-        }
-    } else {
-        for (uint32_t s = 0; s < n_steps; s++) launch_step_range(h, h->stream, nullptr, policy_seed, flags, 0u, n);
+        hipLaunchKernelGGL(K.step4[1][p.pol], dim3(p.grid_plain), dim3(64), 0, h->stream, E, policy_seed, flags | p.row_flags, 0u, n, n_steps, (const uint64_t*)nullptr, kPlainOrder);
+    } else if (int rc = run_parts(h, p, n_steps, [&](hipStream_t st, uint32_t g0, uint32_t g1) { launch_step_range(h, st, nullptr, policy_seed, flags, g0, g1); })) {
+        return rc;
     }
     HIPCHK(hipGetLastError());
+    if (ran) *ran = p;
     return RMJ_OK;
 }
 int rmj_step_random(rmj_handle h, uint64_t policy_seed, uint32_t n_steps, int auto_reset) {
@@ -952,83 +902,40 @@ int rmj_step_greedy(rmj_handle h, uint64_t policy_seed, uint32_t n_steps, int au
 // of the seats that are to act, written into the resident tensor d_out [n][4][74][W] (only_active as in rmj_encode_device).
 // Same results as n_steps x (rmj_step_random(h, seed, 1, auto_reset); rmj_encode_device(h, only_active, d_out)); issued like
 // rmj_step_random as up to four parts of the batch on as many streams, each part running step, encode, step, encode ...
-int rmj_step_random_encode(rmj_handle h, uint64_t policy_seed, uint32_t n_steps, int auto_reset, int only_active, float* d_out) {
+static int step_encode_impl(rmj_handle h, uint64_t policy_seed, uint32_t n_steps, int auto_reset, int only_active, float* d_out, rmjh::RolloutPlan* ran = nullptr) {
     if (!h || !d_out) return fail(RMJ_ERR_ARG, "null argument");
     HIPCHK(hipSetDevice(h->cfg.device));
     const uint32_t flags = STEP_F_RANDOM | (auto_reset ? STEP_F_AUTORESET : 0u);
+    const StepKernels& K = *h->kern;
+    const Env* const E = h->d_env;
     const uint32_t n = h->cfg.n_games;
-    if (h->enc_fused && h->quad >= 2 && h->want_streams >= 2 && n_steps >= 2 && only_active == 2) {
-        // Round 3: ONE launch - every wave steps its four games and writes the rows of the seats that are to act, step after step
-        // (k_step4_enc); as (quad, chunk) tickets when the batch is between one and eight chip-fulls of waves (k_step4_queue_enc)
-        const bool sanma = h->cfg.game_mode >= 3;
-        const dim3 grid((n + 3u) / 4u);
-        if (h->q_slots_enc == 0) {
-            int per_cu = 0, cus = 0;
-            if ((sanma ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rmj3::k_step4_queue_enc<0>, 64, 0)
-                       : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rmj4::k_step4_queue_enc<0>, 64, 0)) != hipSuccess ||
-                hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->cfg.device) != hipSuccess)
-                return fail(RMJ_ERR_HIP, "occupancy query failed");
-            h->q_slots_enc = (uint32_t)(per_cu > 0 ? per_cu : 1) * (uint32_t)(cus > 0 ? cus : 1);
-        }
-        const uint32_t chunk = rollout_chunk(h, n_steps);
-        const bool queued = h->queue_chunk > 0 && h->max_xcc_id <= 7u && n_steps >= 2u * chunk &&
-                            (h->queue_force ? grid.x >= 64u : (grid.x > h->q_slots_enc && grid.x < 8u * h->q_slots_enc));
-        if (queued) {
-            // ticket counters (one line per XCD) + the quads' chunk counts: one allocation, zeroed by ONE memset in front of every rollout
-            const size_t set_words = 8 * RMJ_Q_STRIDE + (size_t)grid.x;   // (three counter sets, the third is this rollout's: step_policy_impl)
-            if (!h->d_qheads) {
-                HIPCHK(hipMalloc(&h->d_qheads, (3 * set_words + (size_t)grid.x * 4) * sizeof(uint32_t)));
-                HIPCHK(hipMemsetAsync(h->d_qheads, 0, 3 * set_words * sizeof(uint32_t), h->stream));
-            }
-            uint32_t* const e_heads = h->d_qheads + 2 * set_words;
-            uint32_t* const e_done = e_heads + 8 * RMJ_Q_STRIDE;
-            HIPCHK(hipMemsetAsync(e_heads, 0, set_words * sizeof(uint32_t), h->stream));
-            const dim3 gq(grid.x < h->q_slots_enc ? grid.x : h->q_slots_enc);
-            if (sanma) {
-                hipLaunchKernelGGL((rmj3::k_step4_queue_enc<0>), gq, dim3(64), 0, h->stream, (const Env*)h->d_env, policy_seed, flags, n, n_steps, chunk, e_heads, e_done, h->queue_skip_xcds, d_out);
-                hipLaunchKernelGGL((rmj3::k_step4_fixup_enc<0>), grid, dim3(64), 0, h->stream, (const Env*)h->d_env, policy_seed, flags, n, n_steps, (const uint32_t*)e_done, d_out);
-            } else {
-                hipLaunchKernelGGL((rmj4::k_step4_queue_enc<0>), gq, dim3(64), 0, h->stream, (const Env*)h->d_env, policy_seed, flags, n, n_steps, chunk, e_heads, e_done, h->queue_skip_xcds, d_out);
-                hipLaunchKernelGGL((rmj4::k_step4_fixup_enc<0>), grid, dim3(64), 0, h->stream, (const Env*)h->d_env, policy_seed, flags, n, n_steps, (const uint32_t*)e_done, d_out);
-            }
-        } else if (sanma) {
-            hipLaunchKernelGGL((rmj3::k_step4_enc<0>), grid, dim3(64), 0, h->stream, (const Env*)h->d_env, policy_seed, flags, 0u, n, n_steps, d_out);
-        } else {
-            hipLaunchKernelGGL((rmj4::k_step4_enc<0>), grid, dim3(64), 0, h->stream, (const Env*)h->d_env, policy_seed, flags, 0u, n, n_steps, d_out);
-        }
-        HIPCHK(hipGetLastError());
-        return RMJ_OK;
-    }
-    // The encoder is bound by its stores, the step by instruction issue: parts of the batch on k streams put the step of one
-    // part under the encoder of another (measured, 65 536 3P games: one stream 283 M env.step/s, four parts 383 M with the
-    // four-game kernel and 323 M with the one-game kernel).
-    int k = h->want_streams;
-    if (k > RMJ_MAX_ROLLOUT_STREAMS) k = RMJ_MAX_ROLLOUT_STREAMS;
-    if ((int)(n / RMJ_SPLIT_MIN_PART) < k) k = (int)(n / RMJ_SPLIT_MIN_PART);
-    if (n_steps < 2 || n < RMJ_SPLIT_MIN_GAMES || k < 2) k = 1;
-    if (k >= 2) {
-        if (int rc = ensure_side_streams(h, k)) return rc;
-        HIPCHK(hipEventRecord(h->ev_fork, h->stream));
-        for (int i = 1; i < k; i++) HIPCHK(hipStreamWaitEvent(h->xstream[i - 1], h->ev_fork, 0));
-        for (uint32_t s = 0; s < n_steps; s++)
-            for (int i = 0; i < k; i++) {
-                hipStream_t st = i ? h->xstream[i - 1] : h->stream;
-                const uint32_t g0 = (uint32_t)((uint64_t)n * i / k), g1 = (uint32_t)((uint64_t)n * (i + 1) / k);
+    const rmjh::RolloutPlan p = plan_rollout(h, n_steps, 0, true, only_active, K.queue_enc, &h->q_slots_enc);
+    if (p.need_slots) return fail(RMJ_ERR_HIP, "occupancy query failed");
+    if (p.how == rmjh::RolloutPlan::TICKETS) {
+        // ... as (quad, chunk) tickets when the batch is between one and eight chip-fulls of waves (k_step4_queue_enc)
+        uint32_t *heads, *done, *prog;
+        if (int rc = ticket_counters(h, 2, &heads, &done, &prog)) return rc;
+        hipLaunchKernelGGL(K.queue_enc, dim3(p.grid_tickets), dim3(64), 0, h->stream, E, policy_seed, flags, n, n_steps, p.chunk, heads, done, h->tune.queue_skip_xcds, d_out);
+        hipLaunchKernelGGL(K.fixup_enc, dim3(p.grid_fixup), dim3(64), 0, h->stream, E, policy_seed, flags, n, n_steps, (const uint32_t*)done, d_out);
+    } else if (p.how == rmjh::RolloutPlan::FUSED) {
+        // Round 3: ONE launch - every wave steps its four games and writes the rows of the seats that are to act, step after step (k_step4_enc)
+        hipLaunchKernelGGL(K.enc, dim3(p.grid_plain), dim3(64), 0, h->stream, E, policy_seed, flags, 0u, n, n_steps, d_out);
+    } else {
+        // The encoder is bound by its stores, the step by instruction issue: parts of the batch on k streams put the step of one
+        // part under the encoder of another (measured, 65 536 3P games: one stream 283 M env.step/s, four parts 383 M with the
+        // four-game kernel and 323 M with the one-game kernel).
+        if (int rc = run_parts(h, p, n_steps, [&](hipStream_t st, uint32_t g0, uint32_t g1) {
                 launch_step_range(h, st, nullptr, policy_seed, flags, g0, g1);
                 launch_encode_base_range(h, st, only_active, d_out, g0, g1);
-            }
-        for (int i = 1; i < k; i++) {
-            HIPCHK(hipEventRecord(h->ev_join[i - 1], h->xstream[i - 1]));
-            HIPCHK(hipStreamWaitEvent(h->stream, h->ev_join[i - 1], 0));
-        }
-    } else {
-        for (uint32_t s = 0; s < n_steps; s++) {
-            launch_step_range(h, h->stream, nullptr, policy_seed, flags, 0u, n);
-            launch_encode_base_range(h, h->stream, only_active, d_out, 0u, n);
-        }
+            }))
+            return rc;
     }
     HIPCHK(hipGetLastError());
+    if (ran) *ran = p;
     return RMJ_OK;
+}
+int rmj_step_random_encode(rmj_handle h, uint64_t policy_seed, uint32_t n_steps, int auto_reset, int only_active, float* d_out) {
+    return step_encode_impl(h, policy_seed, n_steps, auto_reset, only_active, d_out);
 }
 int rmj_random_actions(rmj_handle h, uint64_t policy_seed, rmj_action_t* actions) {
     if (!h || !actions) return fail(RMJ_ERR_ARG, "null argument");
@@ -2838,7 +2745,8 @@ static int bench_rollout_impl(rmj_handle h, uint64_t policy_seed, uint32_t warmu
         if (!h->ev_time[i]) HIPCHK(hipEventCreate(&h->ev_time[i]));
     hipEvent_t e0 = h->ev_time[0], e1 = h->ev_time[1];
     HIPCHK(hipEventRecord(e0, h->stream));
-    if ((rc = step_policy_impl(h, policy_seed, steps, 1, pol, rate))) return rc;
+    rmjh::RolloutPlan ran;
+    if ((rc = step_policy_impl(h, policy_seed, steps, 1, pol, rate, &ran))) return rc;
     HIPCHK(hipEventRecord(e1, h->stream));
     // (polling, not hipEventSynchronize: a blocked host thread is woken 10-20 us after the event completes - 2 % of the driver's 20-step window, which ends with this wait)
     for (;;) {
@@ -2850,14 +2758,12 @@ static int bench_rollout_impl(rmj_handle h, uint64_t policy_seed, uint32_t warmu
     HIPCHK(hipEventElapsedTime(&ms, e0, e1));
     if (count && ((rc = rmj_total_steps(h, &after)) || (rc = rmj_total_full_path(h, &full1)))) return rc;
     out->total_ms = ms;
-    const uint32_t fl = (uint32_t)rollout_streams(h, steps);
-    const bool fused = h->quad >= 2 && steps >= 2 && h->want_streams >= 2;
-    out->launches = fused ? 1u : steps * fl;
+    out->launches = ran.launches;
     out->step_kernel_ms = steps ? ms / steps : 0.0;  // each stream runs `steps` launches back to back during `ms`
     out->env_steps = after - before;
-    out->launches_in_flight = fl;
+    out->launches_in_flight = ran.launches_in_flight;
     out->full_path_steps = full1 - full0;
-    out->queued = rollout_queued(h, steps, pol) ? 1u : 0u;
+    out->queued = ran.queued;
     out->reserved = 0u;
     return RMJ_OK;
 }
@@ -2880,21 +2786,19 @@ int rmj_time_rollout_encode(rmj_handle h, uint64_t policy_seed, uint32_t steps, 
     HIPCHK(tmp.event(&e0));
     HIPCHK(tmp.event(&e1));
     HIPCHK(hipEventRecord(e0, h->stream));
-    int rc = rmj_step_random_encode(h, policy_seed, steps, 1, 2, d_out);
+    rmjh::RolloutPlan ran;
+    int rc = step_encode_impl(h, policy_seed, steps, 1, 2, d_out, &ran);
     if (rc) return rc;
     HIPCHK(hipEventRecord(e1, h->stream));
     HIPCHK(hipEventSynchronize(e1));
     float ms = 0.f;
     HIPCHK(hipEventElapsedTime(&ms, e0, e1));
     memset(out, 0, sizeof(*out));
-    const bool fused = h->enc_fused && h->quad >= 2 && h->want_streams >= 2 && steps >= 2;
-    const uint32_t quads = (h->cfg.n_games + 3u) / 4u, chunk = rollout_chunk(h, steps);
     out->total_ms = ms;
     out->step_kernel_ms = steps ? ms / steps : 0.0;
-    out->launches = fused ? 1u : 2u * steps;
-    out->launches_in_flight = 1u;
-    out->queued = (fused && h->queue_chunk > 0 && h->max_xcc_id <= 7u && steps >= 2u * chunk && h->q_slots_enc &&
-                   (h->queue_force ? quads >= 64u : (quads > h->q_slots_enc && quads < 8u * h->q_slots_enc))) ? 1u : 0u;
+    out->launches = ran.launches;
+    out->launches_in_flight = ran.launches_in_flight;
+    out->queued = ran.queued;
     return RMJ_OK;
 }
 // the same around rmj_step_greedy(h, policy_seed, steps, 1, call_rate_256)
@@ -2903,7 +2807,7 @@ int rmj_time_rollout_greedy(rmj_handle h, uint64_t policy_seed, uint32_t steps, 
 }
 int rmj_set_rollout_streams(rmj_handle h, int k) {
     if (!h || k < 1 || k > RMJ_MAX_ROLLOUT_STREAMS) return fail(RMJ_ERR_ARG, "rollout streams must be 1..8");
-    h->want_streams = k;
+    h->tune.want_streams = k;
     return RMJ_OK;
 }
 // device memory / synchronisation for a harness that has no other way to HIP (bench.py runs one GPU without torch)

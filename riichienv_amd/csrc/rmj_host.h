@@ -403,6 +403,103 @@ private:
     size_t total_ = 0, step_;
 };
 
+// ---------------------------------------------------------------- device-policy rollouts: what a handle is tuned to, how one runs
+// smallest batch that a multi-step device rollout splits over several streams of a handle (rmj_step_random)
+#define RMJ_SPLIT_MIN_GAMES 16384u
+#define RMJ_SPLIT_MIN_PART 8192u   // games per part at least
+#define RMJ_MAX_ROLLOUT_STREAMS 8
+// games per wave by batch size (STEP_F_ROWS_SHIFT; profiles/r04_rows_sweep.txt, fused 4p-red-single rollouts, M env.step/s at 4 | 2 | 1 games
+// per wave: 2 048 games 226 | 254 | 278, 4 096: 435 | 478 | 456, 8 192: 814 | 770 | 522, 16 384: 1 288 | 882 | 599; round 5, profiles/r05_rows_sweep.txt:
+// 2 048: 236 | 272 | 301, 3 072: 345 | 373 | 416, 4 096: 455 | 505 | 492, 6 144: 632 | 692 | 589, 8 192: 845 | 823 | 567)
+#define RMJ_ROWS1_MAX_GAMES 3584u
+#define RMJ_ROWS2_MAX_GAMES 7168u
+inline uint32_t rows_for_batch(uint32_t n_games) { return n_games <= RMJ_ROWS1_MAX_GAMES ? 1u : (n_games <= RMJ_ROWS2_MAX_GAMES ? 2u : 4u); }
+// the step flags that tell a four-games-per-wave kernel its games per wave (bit position: STEP_F_ROWS_SHIFT of the step kernels)
+constexpr uint32_t kStepRowsShift = 20;
+inline uint32_t rows_flag_bits(uint32_t rows) { return (rows == 4u ? 0u : rows) << kStepRowsShift; }
+// Is the per-step launch over games [g0, g1) of a batch one that may run in heavy-first order (HeavyOrder)?  Whole-batch launches of
+// at least 2 048 units (waves) only.
+inline bool heavy_first_eligible(uint32_t n_games, uint32_t rows, uint32_t g0, uint32_t g1) {
+    return g0 == 0u && g1 == n_games && (g1 - g0 + rows - 1u) / rows >= 2048u;
+}
+
+// What rmj_create reads from the environment (and rmj_set_rollout_streams sets): a clone takes its source's with one assignment.
+struct RolloutTuning {
+    int want_streams = 4;      // parts a multi-step device rollout is cut into (rmj_set_rollout_streams; RMJ_STEP_STREAMS at create)
+    int quad = 2;              // device-policy steps: 0 = one game per wave (k_step), 1 = four games per wave (k_step4), 2 = and a
+                               // rollout of >= 2 steps is ONE launch in which every wave steps its own games (k_step4<true>); RMJ_STEP4 at create
+    // long fused rollouts hand the work out in (quad, chunk) tickets to a grid that fits the chip once (k_step4_queue)
+    int queue_chunk = 32;      // calls per ticket (round 5: a ticket is a number of calls of the step function, profiles/r05_ticket_schedule_sweep.txt); RMJ_QUEUE_CHUNK at create, 0 = off (every wave keeps one quad for the rollout)
+    int queue_force = 0;       // RMJ_QUEUE_FORCE at create (tests): tickets for every batch of >= 64 quads
+    int queue_min_chunk = 5;   // shortest ticket (steps): a rollout of >= 2 tickets per quad runs as tickets; RMJ_QUEUE_MIN_CHUNK at create
+    int queue_tail = 0;        // ticket lengths descend towards the expected end of a quad's rollout (q_ticket_plan); RMJ_QUEUE_TAIL=0: equal tickets
+    uint32_t queue_skip_xcds = 0;   // test hook: XCDs whose waves leave the queue kernel at once (RMJ_QUEUE_TEST_SKIP_XCDS at create)
+    uint32_t rows_pw = 4;      // games per wave of the non-ticket four-games-per-wave kernels: 4, or 2 / 1 for batches that leave the chip
+                               // latency bound (chosen at create from the batch size; RMJ_ROWS overrides)
+    int heavy_first = 1;       // RMJ_HEAVY_FIRST at create (0: plain block order)
+    int enc_fused = 1;         // RMJ_ENC_FUSED at create: the step + encode rollout as ONE launch (k_step4_enc / k_step4_queue_enc); 0 = parts on streams
+};
+
+// How one device-policy rollout runs, decided once (rollout_plan): the entry point executes it, the timers report from it.
+struct RolloutPlan {
+    enum How { PER_STEP, FUSED, TICKETS };
+    How how = PER_STEP;        // one launch per step on k streams | ONE launch (k_step4<true> / k_step4_enc) | one launch handed out as tickets + its fix-up
+    bool need_slots = false;   // every condition for tickets that does not ask for the ticket kernel's resident waves holds, and they
+                               // are unknown: the caller asks the runtime and plans again (what stands here is the rollout without them)
+    int pol = 0;               // 0 = RandomAgent, 1 = the greedy policy: the instantiation of the step kernels
+    int k = 1;                 // streams of a per-step rollout; part i of the batch is games [part(i), part(i + 1))
+    uint32_t n_games = 0;
+    uint32_t rows = 4, row_flags = 0;   // games per wave of the k_step4 launches (fused and per step) and the flag bits that say so
+    uint32_t chunk = 0;        // steps per ticket
+    uint32_t grid_tickets = 0, grid_fixup = 0, grid_plain = 0;   // blocks of the ticket launch (0 unless TICKETS), its fix-up, the fused launch
+    bool heavy = false;        // per step: the launches cover the whole batch and may run in heavy-first order
+    uint32_t launches = 0, launches_in_flight = 0, queued = 0;   // what RmjBenchResult reports of the rollout
+    uint32_t part(int i) const { return (uint32_t)((uint64_t)n_games * i / k); }
+};
+// pol: 1 = greedy (step rollout only); encode: the step + encode rollout (rmj_step_random_encode) with its only_active; slots: waves of
+// the rollout's ticket kernel the device holds at once, 0 = not known; max_xcc_id: the largest XCC id the device reported at create.
+inline RolloutPlan rollout_plan(const RolloutTuning& t, uint32_t n_games, uint32_t n_steps, int pol, bool encode, int only_active, uint32_t slots,
+                                uint32_t max_xcc_id) {
+    RolloutPlan p;
+    p.pol = !encode && pol == 1 ? 1 : 0;
+    p.n_games = n_games;
+    p.rows = t.rows_pw;
+    p.row_flags = rows_flag_bits(t.rows_pw);
+    const uint32_t quads = (n_games + 3u) / 4u;
+    {   // steps per ticket: the configured chunk, shorter for a short rollout (its tail is one chunk long: at least 16 chunks per quad)
+        uint32_t cap = (uint32_t)t.queue_chunk;
+        const uint32_t lo = (uint32_t)t.queue_min_chunk, fine = n_steps / 16u < lo ? lo : n_steps / 16u;
+        if (cap < (n_steps + 39u) / 40u) cap = (n_steps + 39u) / 40u;   // at most 64 tickets per quad (q_ticket_plan)
+        p.chunk = fine < cap ? fine : cap;
+    }
+    p.grid_plain = encode ? quads : (n_games + p.rows - 1u) / p.rows;
+    p.grid_fixup = encode ? quads : (quads + 63u) / 64u;   // (k_step4_fixup looks at 64 quads per wave, k_step4_fixup_enc at one)
+    // (rmj_set_rollout_streams(h, 1): one launch per step, one stream)
+    if (t.quad >= 2 && n_steps >= 2 && t.want_streams >= 2 && (!encode || (t.enc_fused && only_active == 2))) {
+        p.how = RolloutPlan::FUSED;
+        // Tickets are worth it when the batch is more than one and fewer than eight chip-fulls of waves: below, every quad is resident
+        // at once and there is no tail; far above, the tail is a small share and the chunk hand-overs cost more than it (524 288
+        // games: -2 %).  Never with more XCC ids than queues: no single L2 per queue (see rmj_create).
+        // RMJ_QUEUE_FORCE=1 (tests): any batch with a quad per XCD queue to spare.
+        const bool wanted = t.queue_chunk > 0 && n_steps >= 2u * p.chunk && max_xcc_id <= 7u && (!t.queue_force || quads >= 64u);
+        p.need_slots = wanted && slots == 0u;
+        if (wanted && slots != 0u && (t.queue_force || (quads > slots && quads < 8u * slots))) {
+            p.how = RolloutPlan::TICKETS;
+            p.grid_tickets = quads < slots ? quads : slots;
+        }
+    } else if (t.want_streams >= 2 && n_steps >= 2 && n_games >= RMJ_SPLIT_MIN_GAMES) {
+        const int fit = (int)(n_games / RMJ_SPLIT_MIN_PART);
+        p.k = t.want_streams > RMJ_MAX_ROLLOUT_STREAMS ? RMJ_MAX_ROLLOUT_STREAMS : t.want_streams;
+        if (p.k > fit) p.k = fit;
+    }
+    p.heavy = p.how == RolloutPlan::PER_STEP && t.quad && t.heavy_first && heavy_first_eligible(n_games, p.rows, p.part(0), p.part(1));
+    // the step + encode rollout reports a step and an encode launch per step and one launch in flight, on its split path too
+    p.launches = p.how != RolloutPlan::PER_STEP ? 1u : (encode ? 2u * n_steps : n_steps * (uint32_t)p.k);
+    p.launches_in_flight = encode ? 1u : (uint32_t)p.k;
+    p.queued = p.how == RolloutPlan::TICKETS ? 1u : 0u;
+    return p;
+}
+
 // ---------------------------------------------------------------- chains of logs in replay slots
 // the assignment of logs to slots (see the head of rmj_logreplay.hip.h)
 inline uint32_t lr_assign(const uint32_t* off, uint32_t M, uint32_t n, uint32_t* slot_of_log, uint32_t* slot_logs, uint32_t* slot_first) {

@@ -2912,7 +2912,7 @@ __global__ __launch_bounds__(64, (LOOP && POL == 1) ? RMJ_STEP4_WAVES_GREEDY : R
 // count with an agent-scope atomic", the pick-up "poll it, invalidate this CU's L1 (acquire), load".  No cross-XCD traffic, no
 // L2 write-back.  Results are those of k_step4<true>: every game steps n_steps times with the same policy keys.
 // The queue keys (HW_REG_XCC_ID & 7, quad % 8) assume at most eight XCC ids: rmj_create probes the ids the device reports and the
-// host uses this kernel only when none exceeds 7 (rollout_queued), otherwise every wave keeps its quad (k_step4<true>).
+// host uses this kernel only when none exceeds 7 (rmjh::rollout_plan), otherwise every wave keeps its quad (k_step4<true>).
 #define RMJ_Q_STRIDE 32u   /* u32 words per XCD queue head (its own 128-byte line) */
 // (out of line: inlined into the ticket loop, the one-lane branches below were restructured into a loop nest that re-used a stale
 // ticket - the kernel then ran quads twice at once)

@@ -414,3 +414,62 @@ def test_ragged_batch_sizes(n):
                     assert enc[g, s].tobytes() == o.encode(s, mode >= 3).tobytes(), (n, mode, g, s)
             assert env.mjai_log(g) == o.log(), (n, mode, g)
         env.close()
+
+
+def _env_created_with(env_vars, n, mode, seed):
+    """an environment created under `env_vars` (the library reads its knobs at rmj_create), reset"""
+    from riichienv_amd import vecenv
+
+    old = {k: os.environ.get(k) for k in env_vars}
+    os.environ.update(env_vars)
+    try:
+        env = vecenv.VecRiichiEnv(n, game_mode=mode, seed=seed, event_ring=64)
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+    env.reset()
+    return env
+
+
+@pytest.mark.parametrize("mode", [5, 2])
+def test_encode_rollout_reports_the_path_it_ran(mode):
+    """rmj_time_rollout_encode reports how its step + encode rollout ran: 259 games are 65 quads with a ragged last one, so under
+    RMJ_QUEUE_FORCE=1 a 20-step rollout is one launch handed out as tickets (launches 1, queued 1) and a 9-step one - fewer than two
+    tickets of 5 steps - the one fused launch (queued 0); an environment created with RMJ_ENC_FUSED=0 runs a step and an encode launch
+    per step (launches 40, queued 0).  Whichever path ran, the tensor and the games' step counts are those of a twin driven by
+    step_random(1) + rmj_encode_device(only_active = 2) per step."""
+    import ctypes as C
+
+    import torch
+
+    from riichienv_amd import vecenv
+
+    n, seed, pseed = 259, 77, 0xE2C
+    w = 27 if mode >= 3 else 34
+    fused = os.environ.get("RMJ_STEP4", "2") == "2"     # (RMJ_STEP4=0 / 1 select the per-step kernels: no fused rollout, no tickets)
+
+    def twin_steps(env, out, steps):
+        for _ in range(steps):
+            env.step_random(pseed, 1, auto_reset=True)
+            vecenv._chk(env.L.rmj_encode_device(env.h, 2, C.c_void_p(out.data_ptr())))
+        env.sync()
+
+    for env_vars, runs in (({"RMJ_QUEUE_FORCE": "1"}, ((20, 1, 1), (9, 1, 0))), ({"RMJ_ENC_FUSED": "0"}, ((20, 40, 0),))):
+        env = _env_created_with(env_vars, n, mode, seed)
+        twin = _env_created_with({}, n, mode, seed)
+        out = torch.zeros((n, 4, 74, w), dtype=torch.float32, device="cuda:0")
+        ref = torch.zeros((n, 4, 74, w), dtype=torch.float32, device="cuda:0")
+        torch.cuda.synchronize()      # torch's stream is not the handles' stream
+        for steps, launches, queued in runs:
+            r = env.time_rollout_encode(pseed, steps, out.data_ptr())
+            if fused or "RMJ_ENC_FUSED" in env_vars:
+                assert (int(r.launches), int(r.queued)) == (launches, queued), (env_vars, steps)
+            twin_steps(twin, ref, steps)
+            env.sync()
+            assert torch.equal(out, ref) and float(out.abs().sum()) > 0, (env_vars, steps)
+            assert (env.step_counts() == twin.step_counts()).all(), (env_vars, steps)
+        env.close()
+        twin.close()
