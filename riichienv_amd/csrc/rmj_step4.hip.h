@@ -126,6 +126,7 @@ struct R4 {
 #ifdef RMJ_CENSUS
     int why;          // the R4BAIL site that made the row bail
 #endif
+    int tend;         // the row's turn ends in this call (r4_turn_end, run once behind both phase branches): 1 after a discard nobody can claim, 2 after claims that were all passed
     int evn;          // staged events
     uint32_t dirty;
     bool gf;          // the group-residue tests in front of the table shanten (r4_group_residues): a compile-time constant of the instantiation, see step4_body
@@ -555,6 +556,28 @@ __device__ __forceinline__ void r4_deal_next(R4& q, int pf) {
         G->is_rinshan = 0;
     }
 }
+// The end of a turn nobody claimed (q.tend): the tail of _resolve_discard (state/mod.rs:1397-1412) for a discard without claims (1) and
+// of the all-pass answer (state/mod.rs:1299-1313) (2) - riichi accepted, [abortive draws: only the discard's own tail checks them],
+// turn counter and current player advanced, next tile dealt, first turn over.  One copy for the rows of both phase branches:
+// a wave whose rows left through both used to run it twice, each time with part of its rows masked off.
+// current_player is still the discarder on both paths (and in pass 2, which resumes the discard pass 1 paused).
+__device__ __forceinline__ void r4_turn_end(R4& q, int pf) {
+    GState* G = q.G;
+    r4_accept_riichi(q);
+    if (q.tend == 1) r4_check_abortive(q);
+    if (q.bail) return;
+    const uint32_t tc = G->turn_count + 1u;
+    const int pid = G->current_player;
+    if (q.r == 0) {
+        G->turn_count = tc;
+        G->current_player = (uint8_t)(pid + 1 == KNP ? 0 : pid + 1);
+    }
+    wave_sync();
+    r4_deal_next(q, pf);
+    if (q.bail) return;
+    if (q.r == 0 && tc >= (uint32_t)KNP) G->is_first_turn = 0;
+    wave_sync();
+}
 
 // stage one list entry together with its action id (Action::encode / encode_3p, action.rs:158-346) in the free top byte:
 // where an entry is generated its kind is known, so the id is a constant or one shift - the publication does not decode
@@ -739,7 +762,7 @@ __device__ __forceinline__ uint32_t r4_yaku_check(uint32_t on, uint32_t seat, ui
 // RESUME (pass 2): the discard itself - bookkeeping, indicators, the dahai event, the wait-cache refills - was done in pass 1, which
 // paused at the Ron check (R4_RE_YAKU_CLAIMS); the function picks up there with the evaluator's answers (q.yk)
 template <bool RICH, bool LOOP, bool RESUME = false>
-__device__ __forceinline__ void r4_resolve_discard(R4& q, int pid, int tile, bool tsumogiri, int pf, int& nl_mine, uint64_t& w_mine, int known_sh = 99) {
+__device__ __forceinline__ void r4_resolve_discard(R4& q, int pid, int tile, bool tsumogiri, int& nl_mine, uint64_t& w_mine, int known_sh = 99) {
     GState* G = q.G;
     PState* P = &G->p[pid];
     const int r = q.r, rb = q.rb;
@@ -867,10 +890,12 @@ __device__ __forceinline__ void r4_resolve_discard(R4& q, int pid, int tile, boo
     auto nl_set = [&](int i, int v) {
         nl0 = i == 0 ? v : nl0; nl1 = i == 1 ? v : nl1; nl2 = i == 2 ? v : nl2; nl3 = i == 3 ? v : nl3;
     };
-    // ---- C: Pon / Daiminkan material, seat by seat (lane = hand slot)
+    // ---- C: Pon / Daiminkan material (lane = hand slot), by seat RELATIVE to the discarder: each row walks its own KNP - 1 opponents
+    //      (by absolute seat the wave ran all KNP iterations: each seat is the discarder - skipped - in some rows only).  The seats'
+    //      lists are independent: the order changes nothing
 #pragma unroll
-    for (int i = 0; i < KNP; i++) {
-        if (i == pid) continue;
+    for (int k = 1; k < KNP; k++) {
+        const int i = pid + k >= KNP ? pid + k - KNP : pid + k;
         const PState* Q = &G->p[i];
         const int hl = Q->hand_len;
         const int ht = r < hl ? (int)Q->hand[r] : 0xFF;
@@ -966,19 +991,7 @@ __device__ __forceinline__ void r4_resolve_discard(R4& q, int pid, int tile, boo
         }
         wave_sync();
     } else {
-        r4_accept_riichi(q);
-        r4_check_abortive(q);
-        if (q.bail) return;
-        const uint32_t tc = G->turn_count + 1u;
-        if (r == 0) {
-            G->turn_count = tc;
-            G->current_player = (uint8_t)(pid + 1 == KNP ? 0 : pid + 1);
-        }
-        wave_sync();
-        r4_deal_next(q, pf);
-        if (q.bail) return;
-        if (r == 0 && tc >= (uint32_t)KNP) G->is_first_turn = 0;
-        wave_sync();
+        q.tend = 1;   // nobody can claim it: the turn ends (r4_turn_end, behind both phase branches; the phase stays WaitAct until then)
     }
 }
 
@@ -1226,7 +1239,7 @@ __device__ __noinline__ void r4_round_end(const Env* Ep, uint32_t g0) {
     GState* G = &sh.st[row];
     R4 q;
     q.G = G; q.T = &sh.u.t; q.E = &E; q.lane = lane; q.r = r; q.rb = rb; q.row = row; q.g = g0 + (uint32_t)row;
-    q.live = mode != 0u; q.bail = false; q.cont = 0; q.rend = mode; q.evn = 0; q.dirty = 0xFu; q.pause_ok = false; q.yk = 0u; q.yk_mode = 0u; q.gf = false;
+    q.live = mode != 0u; q.bail = false; q.cont = 0; q.rend = mode; q.tend = 0; q.evn = 0; q.dirty = 0xFu; q.pause_ok = false; q.yk = 0u; q.yk_mode = 0u; q.gf = false;
     const bool draw = mode == R4_RE_DRAW, restart = mode == R4_RE_RESTART;
     const bool win_t = mode == R4_RE_WIN_TSUMO, win_r = mode == R4_RE_WIN_RON, win = win_t || win_r;
     bool newround = restart;            // the row's game starts a round below, with these parameters (row-uniform)
@@ -2048,7 +2061,7 @@ __device__ __forceinline__ uint32_t step4_body(const Env* Ep, Quad4Shared& sh, u
     q.live = pass2 ? ((uint32_t)row < n_here && sh.rmode[row] != 0u) : ((uint32_t)row < n_here && (!INLR || left != 0u));
     GState* G = q.G;
     const uint64_t* Lg = E.legal + (size_t)g * 4 * RMJ_MAX_LEGAL;
-    q.bail = false; q.cont = 0; q.rend = 0u; q.evn = 0; q.dirty = 0xFu;
+    q.bail = false; q.cont = 0; q.rend = 0u; q.tend = 0; q.evn = 0; q.dirty = 0xFu;
 #ifdef RMJ_CENSUS
     q.why = 0;
 #endif
@@ -2225,7 +2238,7 @@ __device__ __forceinline__ uint32_t step4_body(const Env* Ep, Quad4Shared& sh, u
                     if (r == 0) P->hand_len = (uint8_t)(hl - 1);
                     wave_sync();
                     R4M(42);
-                    r4_resolve_discard<RICH, LOOP>(q, pid, tile, tsumogiri, pf, nl_mine, w_mine, (POL == 1 && pol_seat == pid) ? pol_sh : 99);
+                    r4_resolve_discard<RICH, LOOP>(q, pid, tile, tsumogiri, nl_mine, w_mine, (POL == 1 && pol_seat == pid) ? pol_sh : 99);
                     R4M(56);
                 }
             } else if (KSANMA && ty == RMJ_KITA) {
@@ -2577,39 +2590,31 @@ __device__ __forceinline__ uint32_t step4_body(const Env* Ep, Quad4Shared& sh, u
                         }
                         if (r < 4) G->stale_n[r] = 0;   // current_claims.clear() (state/mod.rs:1299)
                         wave_sync();
-                        r4_accept_riichi(q);
-                        const uint32_t tc = G->turn_count + 1u;
-                        const int np_ = (G->current_player + 1) % KNP;
-                        if (r == 0) {
-                            G->turn_count = tc;
-                            G->current_player = (uint8_t)np_;
-                        }
-                        wave_sync();
-                        r4_deal_next(q, pf);
-                        if (!q.bail) {
-                            if (r == 0 && tc >= (uint32_t)KNP) G->is_first_turn = 0;
-                            wave_sync();
-                        }
+                        q.tend = 2;   // everybody passed: the turn ends (r4_turn_end below, without the abortive check - the reference has none here)
                     }
                 }
             }
         }
         R4M(43);
     }
+    const bool resumed = pass2 && RICH && t0 && q.yk_mode == R4_RE_YAKU_CLAIMS;
+    if (pass2 && RICH && __ballot(resumed)) {
+        // pass 2 of a row that paused at its discard's Ron check: the rest of _resolve_discard with the evaluator's answers
+        if (resumed) r4_resolve_discard<RICH, LOOP, true>(q, G->last_discard_pid, G->last_discard_tile, false, nl_mine, w_mine);
+    }
+    // ---- the end of the turn, once for the rows of both branches and of the resumed discard (r4_turn_end; q.tend is set only by rows
+    //      that are live and have not bailed).  A no-claim row's phase stays WaitAct until here, so `second` above read it as before
+    if (q.tend != 0) r4_turn_end(q, pf);
+    // Whatever makes a resumed row leave tier 0 continues in the full path from HERE (the claims of the discard already made:
+    // STEP_F_CONT_CLAIMS), an exhaustive draw at the exhaustive draw (STEP_F_CONT_RYU, set by r4_deal_next).  Behind the shared tail, because
+    // the tail is the end of the resumed _resolve_discard: its abortive check bails like the claim sections do (-> 3), its draw sets 1 itself
+    if (resumed && q.bail && q.cont == 0) q.cont = 3;
+    R4M(44);
     R4T(2);
     // rows whose round ended (an exhaustive draw above, a finished game under auto-reset) stop here in pass 1: ryukyoku, next round or end
     // of game and the deal happen between the passes (r4_round_end), their observation is pass 2's
     bool wait_deal = !pass2 && t0 && !q.bail && q.rend != 0u;
     if (q.rend) q.dirty = 0xFu;
-    if (pass2 && RICH && __ballot(t0 && q.yk_mode == R4_RE_YAKU_CLAIMS)) {
-        // pass 2 of a row that paused at its discard's Ron check: the rest of _resolve_discard with the evaluator's answers.  Whatever makes
-        // it leave tier 0 now continues in the full path from HERE (the claims of the discard already made: STEP_F_CONT_CLAIMS), an
-        // exhaustive draw at the exhaustive draw (STEP_F_CONT_RYU, set by r4_deal_next)
-        if (t0 && q.yk_mode == R4_RE_YAKU_CLAIMS) {
-            r4_resolve_discard<RICH, LOOP, true>(q, G->last_discard_pid, G->last_discard_tile, false, pf, nl_mine, w_mine);
-            if (q.bail && q.cont == 0) q.cont = 3;
-        }
-    }
     if (t0 && !wait_deal) {
         // ---- the next observation: a WaitAct state needs the acting seat's list
         if (!q.bail && G->phase == RMJ_WAIT_ACT && !(q.rend && G->is_done)) {

@@ -7,7 +7,7 @@ then:            python3 scripts/valu_sections4.py report gpurun_out/cuts4
 
 The marks end the WAVE (all four rows) where the first row reaches them: marks inside the WaitAct branch (42, 50..56) give
 the cost of the discard path up to there for a wave whose rows are in that branch, marks at the convergence points (40,
-41, 43, 45, 46, 47) the cost of everything before them.  Nothing is stored by a cut launch: every launch sees the same
+41, 43, 44, 45, 46, 47) the cost of everything before them.  Nothing is stored by a cut launch: every launch sees the same
 game states (the rollout is warmed up with the uncut kernel)."""
 import csv
 import ctypes as C
@@ -18,10 +18,11 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-CUTS = [40, 41, 42, 50, 51, 52, 53, 54, 55, 56, 43, 60, 61, 45, 46, 47]
+CUTS = [40, 41, 42, 50, 51, 52, 53, 54, 55, 56, 43, 44, 60, 61, 45, 46, 47]
 NAMES = {40: "records loaded", 41: "policy pick", 42: "discard: find + sort", 50: "discard: bookkeeping + dahai event", 51: "claims A: wait-cache refill",
          52: "claims B: ron eligibility", 53: "claims C: pon / kan lists", 54: "claims D: chi lists", 55: "claims E: pass / lengths",
-         56: "no claims: riichi accept, abortive check, next draw", 43: "both phase branches done (incl. WaitResponse)",
+         56: "discard resolved: claims offered or turn end flagged", 43: "both phase branches done (incl. WaitResponse)",
+         44: "shared turn end: riichi accept, abortive check, next draw",
          60: "act list: tsumo check", 61: "act list: discards + riichi bound", 45: "act list: kan / kyushu / kita", 46: "publication: lists, masks, status, events",
          47: "records stored"}
 GAMES = 65536
