@@ -514,6 +514,45 @@ int rmj_danger_targets_device(rmj_handle h, const int32_t* d_index, uint32_t row
 /* The same with host pointers (index and the array of `out`): staged on the device, returns when the rows are there. */
 int rmj_danger_targets(rmj_handle h, const int32_t* index, uint32_t rows, uint32_t flags, const RmjDangerOut* out);
 
+/* Discard efficiency table: for a hand, the shanten after every discard, the draws that then lower it and how many of them are live -
+ * the attack value of each of the 34 tile types, next to the defence cost rmj_danger_targets_device gives; what rmj_best_ukeire and
+ * rmj_effective_tiles fold to one number.  For a hand histogram c[34] of n tiles and a visible histogram v[34]:
+ *   valid types   all 34 in 4P; type 0 and types 8..33 in 3P
+ *   sh(x)         rmj_shanten of x (calculate_shanten / calculate_shanten_3p with tiles / 3 groups)
+ *   for a hand x of 3k+1 tiles:  A(x) = { t valid : x[t] < 4 and sh(x + t) < sh(x) },  accept(x) = |A(x)|,
+ *                 ukeire(x) = sum over t in A of max(0, max(0, 4 - v[t]) - x[t]),  mask(x) = the bits of A
+ *   column t < 34 if n % 3 == 2 and c[t] > 0: with x = c - e_t, shanten[t] = sh(x), accept[t], ukeire[t], mask[t] - discards that raise
+ *                 the shanten too; otherwise shanten[t] = RMJ_DTAB_NONE and the rest 0.  A held 2m..8m of a raw 3P histogram gets its
+ *                 column like any other type.
+ *   column 34     the hand itself: shanten[34] = sh(c).  n % 3 == 1: accept and mask of c.  n % 3 == 2: accept[34] and ukeire[34]
+ *                 are, separately, the maxima over the t with shanten[t] <= shanten[34] (rmj_effective_tiles, rmj_best_ukeire),
+ *                 mask[34] = 0.  n % 3 == 0: the shanten only.
+ *                 ukeire[34] of a 3n+1 hand is rmj_best_ukeire of it as well, NOT ukeire(c): calculate_best_ukeire walks the discards
+ *                 of a hand of any size - the maximum of ukeire(c - e_d) over the held d with sh(c - e_d) <= sh(c), the 3n hands
+ *                 judged with (n - 1) / 3 groups.  So column 34 is, for every hand, what rmj_shanten, rmj_effective_tiles and
+ *                 rmj_best_ukeire answer and what channels 78..80 of the extended features carry (x 8, x 34 or 27, x 80).
+ *   d_shanten [rows][35] i8,  d_accept [rows][35] u8,  d_ukeire [rows][35] u8 (at most 136),  d_mask [rows][35] u64 (may be NULL)
+ * An absent row (index out of range, seat >= the number of players) has every shanten RMJ_DTAB_NONE and the rest 0.
+ * The row of (game g, seat a): c = the seat's concealed tiles by type, v = the histogram the efficiency channels of the extended
+ * features count - every seat's discards, every seat's meld tiles (4 for kans) and the revealed dora indicators.  By tile type: red
+ * fives are fives.
+ * Index, d_count and the untouched tail as in rmj_hidden_targets_device; only reads the state (no cache is written back).  Asynchronous
+ * on the handle's stream.  flags must be 0.  RMJ_ERR_ARG for a null handle / descriptor, a flag, or null arrays with rows > 0. */
+#define RMJ_DTAB_NONE 127
+#define RMJ_DTAB_COLS 35
+typedef struct RmjDiscardTableOut {
+    int8_t* d_shanten;    /* [rows][35] */
+    uint8_t* d_accept;    /* [rows][35] */
+    uint8_t* d_ukeire;    /* [rows][35] */
+    uint64_t* d_mask;     /* [rows][35], may be NULL */
+} RmjDiscardTableOut;
+int rmj_discard_table_device(rmj_handle h, const int32_t* d_index, uint32_t rows, const uint32_t* d_count, uint32_t flags, const RmjDiscardTableOut* out);
+/* The same with host pointers (index and the arrays of `out`): staged on the device, returns when the rows are there. */
+int rmj_discard_table(rmj_handle h, const int32_t* index, uint32_t rows, uint32_t flags, const RmjDiscardTableOut* out);
+/* The table of raw histograms on the host, like rmj_best_ukeire: counts [n][34] u8, visible [n][34] u8 or NULL (nothing visible), host
+ * arrays in `out` ([n][35]; the mask may be NULL).  A hand of more than 14 tiles, or a count above 4, gives an absent row. */
+int rmj_discard_table_hands(int device, const uint8_t* counts, const uint8_t* visible, uint32_t n, int sanma, const RmjDiscardTableOut* out);
+
 /* Determinize: re-deal, in place, what seat a of game g cannot see - the concealed hands of its opponents and the part of the wall that can
  * still be drawn or revealed - so that the game becomes a position the seat could not tell from the one it was; lists, masks, waits and
  * status are republished and every call steps the game on (forks of rmj_copy_games_device become sampled worlds: PIMC, determinized
@@ -855,9 +894,10 @@ int rmj_logreplay_assign(const uint32_t* offsets, uint32_t n_logs, uint32_t n_sl
 #define RMJ_LOGREPLAY_SKIP_SINGLE_ACTION 2u  /* a decision over a list of at most one action is no sample (LogKyoku.steps' default) */
 #define RMJ_LOGREPLAY_HIDDEN 4u              /* every pool slot also keeps its hidden-hand record and event index: rmj_logreplay_emit_hidden_device */
 #define RMJ_LOGREPLAY_DANGER 8u              /* every pool slot also keeps its deal-in danger record: rmj_logreplay_emit_danger_device */
+#define RMJ_LOGREPLAY_DTABLE 16u             /* every pool slot also keeps its discard efficiency record: rmj_logreplay_emit_dtable_device */
 typedef struct RmjLogReplayConfig {
     int32_t features;           /* RMJ_FEATURES_*: the rows the pool stores */
-    uint32_t capacity;          /* samples: capacity x (C x W x 4 + A + 52) bytes of device memory, + 152 with RMJ_LOGREPLAY_HIDDEN, + 224 with RMJ_LOGREPLAY_DANGER */
+    uint32_t capacity;          /* samples: capacity x (C x W x 4 + A + 52) bytes of device memory, + 152 with RMJ_LOGREPLAY_HIDDEN, + 224 with RMJ_LOGREPLAY_DANGER, + 112 with RMJ_LOGREPLAY_DTABLE */
     uint32_t flags;             /* RMJ_LOGREPLAY_* */
     uint32_t n_powers;
     double gamma;
@@ -980,6 +1020,21 @@ typedef struct RmjLogDangerBatch {
     uint32_t rows, reserved;
 } RmjLogDangerBatch;
 int rmj_logreplay_emit_danger_device(rmj_logreplay_handle r, const RmjLogDangerBatch* out);
+/* RMJ_LOGREPLAY_DTABLE: every sample also gets the discard efficiency row of (its slot's game, the deciding seat) - d_shanten, d_accept
+ * and d_ukeire of rmj_discard_table_device - taken where the hidden record is: from the state before the step's event is applied, by a
+ * kernel of its own behind the hidden and danger ones (without the flag the replay launches what it always did and allocates nothing
+ * more).  Independent of the other record flags.  The records lie in an allocation of their own of capacity x 112 bytes: per slot three
+ * byte arrays of 35 (shanten i8, accept u8, ukeire u8) and 7 spare bytes.  The masks are left out of the pool: 280 more bytes per slot
+ * buy nothing a trainer needs (accept counts them; rmj_discard_table_device has them for a live row).  Meaningful only where the deciding
+ * seat's own hand is known.  The emit call copies the records of the samples rmj_logreplay_emit_device emits to the same rows in the
+ * same order; rows beyond `rows` are dropped like there.  RMJ_ERR_ARG for a builder made without the flag. */
+typedef struct RmjLogDtableBatch {
+    int8_t* d_shanten;       /* [rows][35] */
+    uint8_t* d_accept;       /* [rows][35] */
+    uint8_t* d_ukeire;       /* [rows][35] */
+    uint32_t rows, reserved;
+} RmjLogDtableBatch;
+int rmj_logreplay_emit_dtable_device(rmj_logreplay_handle r, const RmjLogDtableBatch* out);
 
 /* ------------------------------------------------------------------ log validation
  * A verdict for every log of a log set before samples are built from it (riichienv-ml validates a corpus one log at a time through

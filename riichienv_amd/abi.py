@@ -280,7 +280,7 @@ LOGTEXT_OK, LOGTEXT_UNSUPPORTED, LOGTEXT_ERR_JSON, LOGTEXT_ERR_KEY, LOGTEXT_ERR_
 LOGTEXT_STATUS_NAMES = ["OK", "UNSUPPORTED", "ERR_JSON", "ERR_KEY", "ERR_TEHAI", "ERR_TILE", "ERR_VALUE", "ERR_REPLAY"]
 LOGTEXT_ON_DEVICE, LOGTEXT_MASKED_OK = 1, 2
 
-LOGREPLAY_INCLUDE_PASS, LOGREPLAY_SKIP_SINGLE_ACTION, LOGREPLAY_HIDDEN, LOGREPLAY_DANGER = 1, 2, 4, 8   # RMJ_LOGREPLAY_*
+LOGREPLAY_INCLUDE_PASS, LOGREPLAY_SKIP_SINGLE_ACTION, LOGREPLAY_HIDDEN, LOGREPLAY_DANGER, LOGREPLAY_DTABLE = 1, 2, 4, 8, 16   # RMJ_LOGREPLAY_*
 HIDDEN_PRESENT, HIDDEN_TENPAI, HIDDEN_RIICHI, HIDDEN_FURITEN, HIDDEN_MELDS_SHIFT = 1, 2, 4, 8, 4   # RMJ_HIDDEN_*: the bits of opp_flags
 
 
@@ -293,6 +293,13 @@ DANGER_URA, DANGER_KINDS = 1, 37   # RMJ_DANGER_*: the flag of rmj_danger_target
 
 class DangerOut(C.Structure):        # RmjDangerOut (rmj_danger_targets_device)
     _fields_ = [("danger", C.c_void_p)]
+
+
+DTAB_NONE, DTAB_COLS = 127, 35     # RMJ_DTAB_*: the shanten of an absent column, the columns of a row (34 discards + the hand itself)
+
+
+class DiscardTableOut(C.Structure):  # RmjDiscardTableOut (rmj_discard_table_device); mask may be NULL
+    _fields_ = [(k, C.c_void_p) for k in ("shanten", "accept", "ukeire", "mask")]
 
 
 DET_OK, DET_NOT_ACTING, DET_CHANKAN, DET_DUPLICATE, DET_RIICHI_NOTEN = 0, 1, 2, 3, 16   # RMJ_DET_*: determinize status (RIICHI_NOTEN << r, r = 0, 1, 2)
@@ -330,6 +337,10 @@ class LogHiddenViews(C.Structure):   # RmjLogHiddenViews
 
 class LogDangerBatch(C.Structure):   # RmjLogDangerBatch (rmj_logreplay_emit_danger_device)
     _fields_ = [("danger", C.c_void_p), ("rows", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class LogDtableBatch(C.Structure):   # RmjLogDtableBatch (rmj_logreplay_emit_dtable_device)
+    _fields_ = [(k, C.c_void_p) for k in ("shanten", "accept", "ukeire")] + [("rows", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class LogReplayCounts(C.Structure):  # RmjLogReplayCounts
@@ -438,6 +449,9 @@ PROTOTYPES = [
     ("rmj_hidden_targets", [vp, vp, u32, P(HiddenOut)]),
     ("rmj_danger_targets_device", [vp, vp, u32, vp, u32, P(DangerOut)]),
     ("rmj_danger_targets", [vp, vp, u32, u32, P(DangerOut)]),
+    ("rmj_discard_table_device", [vp, vp, u32, vp, u32, P(DiscardTableOut)]),
+    ("rmj_discard_table", [vp, vp, u32, u32, P(DiscardTableOut)]),
+    ("rmj_discard_table_hands", [cint, vp, vp, u32, cint, P(DiscardTableOut)]),
     ("rmj_determinize_device", [vp, vp, u32, vp, P(Determinize)]),
     ("rmj_determinize", [vp, vp, u32, P(Determinize)]),
     ("rmj_determinize_order", [u64, u64, u32, u32, vp]),
@@ -485,6 +499,7 @@ PROTOTYPES = [
     ("rmj_logreplay_emit_hidden_device", [vp, P(LogHiddenBatch)]),
     ("rmj_logreplay_hidden_views", [vp, P(LogHiddenViews)]),
     ("rmj_logreplay_emit_danger_device", [vp, P(LogDangerBatch)]),
+    ("rmj_logreplay_emit_dtable_device", [vp, P(LogDtableBatch)]),
     # ---- log validation
     ("rmj_logcheck_name", [u32], C.c_char_p),
     ("rmj_logcheck_create", [vp, vp, u32, u32, P(vp)]),

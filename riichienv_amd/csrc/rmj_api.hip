@@ -57,6 +57,12 @@ using namespace rmj;
 #include "rmj_hidden.hip.h"
 #include "rmj_determinize.hip.h"
 #include "rmj_danger.hip.h"
+#include "rmj_dtable.hip.h"
+// the launches of the discard table's kernels, defined at the end of this file: there the kernels are named for the first time (rmj_dtable.hip.h)
+static void dt_launch_rows(hipStream_t st, const Env& E, const int32_t* d_index, uint32_t rows, const uint32_t* d_count, const RmjDiscardTableOut& O);
+static void dt_launch_hands(const ShantenTables& T, const uint8_t* counts, const uint8_t* visible, uint32_t n, int sanma, const RmjDiscardTableOut& O);
+static void dt_launch_log(hipStream_t st, const Env& E, const LogRun& R, uint8_t* dtb);
+static void dt_launch_log_emit(hipStream_t st, const LogRun& R, const uint8_t* dtb, const LogDtableOut& O);
 
 static inline dim3 step_grid(uint32_t n) { return dim3((n + RMJ_STEP_WPB - 1) / RMJ_STEP_WPB); }
 static_assert(rmjh::kStepRowsShift == STEP_F_ROWS_SHIFT, "rmj_host.h states the step kernels' rows flag position");
@@ -329,6 +335,7 @@ struct rmj_logreplay {
     LogRun R{};
     double* d_powers = nullptr;
     uint8_t* d_hid = nullptr;          // RMJ_LOGREPLAY_HIDDEN: [capacity][HID_SLOT_BYTES] hidden records, an allocation of its own (rmj_hidden.hip.h)
+    uint8_t* d_dtb = nullptr;          // RMJ_LOGREPLAY_DTABLE: [capacity][DT_SLOT_BYTES] discard efficiency records, an allocation of its own (rmj_dtable.hip.h)
     uint8_t* d_dng = nullptr;          // RMJ_LOGREPLAY_DANGER: [capacity][DNG_SLOT_BYTES] danger records, an allocation of its own (rmj_danger.hip.h)
     uint32_t n_powers = 0;
     rmjh::SlotChain chain;             // which slot replays which logs, the steps of a whole replay and the steps taken
@@ -1890,6 +1897,41 @@ int rmj_danger_targets(rmj_handle h, const int32_t* index, uint32_t rows, uint32
     HIPCHK(hipMemcpy(out->d_danger, d.d_danger, bytes, hipMemcpyDeviceToHost));
     return RMJ_OK;
 }
+// ---- discard efficiency table (rmj_dtable.hip.h) -----------------------------------------------------------------
+int rmj_discard_table_device(rmj_handle h, const int32_t* d_index, uint32_t rows, const uint32_t* d_count, uint32_t flags, const RmjDiscardTableOut* out) {
+    if (!h || !out) return fail(RMJ_ERR_ARG, "null argument");
+    if (flags) return fail(RMJ_ERR_ARG, "rmj_discard_table_device: unknown flag");
+    if (!rows) return RMJ_OK;
+    if (!d_index || !out->d_shanten || !out->d_accept || !out->d_ukeire) return fail(RMJ_ERR_ARG, "null argument");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    dt_launch_rows(h->stream, h->d, d_index, rows, d_count, *out);
+    HIPCHK(hipGetLastError());
+    return RMJ_OK;
+}
+int rmj_discard_table(rmj_handle h, const int32_t* index, uint32_t rows, uint32_t flags, const RmjDiscardTableOut* out) {
+    if (!h || !out) return fail(RMJ_ERR_ARG, "null argument");
+    if (flags) return fail(RMJ_ERR_ARG, "rmj_discard_table: unknown flag");
+    if (!rows) return RMJ_OK;
+    if (!index || !out->d_shanten || !out->d_accept || !out->d_ukeire) return fail(RMJ_ERR_ARG, "null argument");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const size_t cells = (size_t)rows * RMJ_DTAB_COLS;
+    int32_t* d_index;
+    RmjDiscardTableOut d{};
+    rmjh::DevLayout L;
+    L.add(&d_index, (size_t)rows * 4); L.add(&d.d_shanten, cells); L.add(&d.d_accept, cells); L.add(&d.d_ukeire, cells);
+    if (out->d_mask) L.add(&d.d_mask, cells * 8);
+    int rc = scratch_for(h, L);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(d_index, index, (size_t)rows * 4, hipMemcpyHostToDevice));
+    if ((rc = rmj_discard_table_device(h, d_index, rows, nullptr, flags, &d))) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(out->d_shanten, d.d_shanten, cells, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out->d_accept, d.d_accept, cells, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out->d_ukeire, d.d_ukeire, cells, hipMemcpyDeviceToHost));
+    if (out->d_mask) HIPCHK(hipMemcpy(out->d_mask, d.d_mask, cells * 8, hipMemcpyDeviceToHost));
+    return RMJ_OK;
+}
 // ---- determinize (rmj_determinize.hip.h) ------------------------------------------------------------------------
 int rmj_determinize_device(rmj_handle h, const int32_t* d_index, uint32_t rows, const uint32_t* d_count, const RmjDeterminize* p) {
     return rmj_determinize_ex_device(h, d_index, rows, d_count, p, 0u);
@@ -2366,7 +2408,7 @@ int rmj_logreplay_create(rmj_handle h, rmj_logset_handle set, const RmjLogReplay
     if (set->device != h->cfg.device) return fail(RMJ_ERR_ARG, "rmj_logreplay_create: the log set lives on another device");
     const uint32_t n = h->cfg.n_games;
     if (n > set->M) return fail(RMJ_ERR_ARG, "rmj_logreplay_create: more slots (the handle's games) than logs: n_slots <= M");
-    if (cfg->flags & ~(uint32_t)(RMJ_LOGREPLAY_INCLUDE_PASS | RMJ_LOGREPLAY_SKIP_SINGLE_ACTION | RMJ_LOGREPLAY_HIDDEN | RMJ_LOGREPLAY_DANGER)) return fail(RMJ_ERR_ARG, "rmj_logreplay_create: unknown flag");
+    if (cfg->flags & ~(uint32_t)(RMJ_LOGREPLAY_INCLUDE_PASS | RMJ_LOGREPLAY_SKIP_SINGLE_ACTION | RMJ_LOGREPLAY_HIDDEN | RMJ_LOGREPLAY_DANGER | RMJ_LOGREPLAY_DTABLE)) return fail(RMJ_ERR_ARG, "rmj_logreplay_create: unknown flag");
     uint32_t ch, w, rs;
     float dummy;
     RmjObsBatch b{};
@@ -2427,13 +2469,22 @@ int rmj_logreplay_create(rmj_handle h, rmj_logset_handle set, const RmjLogReplay
         delete r;
         return fail(RMJ_ERR_HIP, "rmj_logreplay_create: no device memory for the danger records (capacity x 224 bytes: choose a smaller capacity)");
     }
+    if ((cfg->flags & RMJ_LOGREPLAY_DTABLE) && hipMalloc(&r->d_dtb, (size_t)cap * DT_SLOT_BYTES) != hipSuccess) {
+        (void)hipGetLastError();
+        hipFree(r->mem);
+        if (r->d_hid) hipFree(r->d_hid);
+        if (r->d_dng) hipFree(r->d_dng);
+        delete r;
+        return fail(RMJ_ERR_HIP, "rmj_logreplay_create: no device memory for the discard efficiency records (capacity x 112 bytes: choose a smaller capacity)");
+    }
     uint8_t* m = (uint8_t*)r->mem;
     L.bind(m);
     h->logreplay.push_back(r);
     // everything behind the feature rows starts as zeros (the views show defined values in slots that were never filled)
     if (hipMemsetAsync(m + o_packed, 0, off - o_packed, h->stream) != hipSuccess ||
         (r->d_hid && hipMemsetAsync(r->d_hid, 0, (size_t)cap * HID_SLOT_BYTES, h->stream) != hipSuccess) ||
-        (r->d_dng && hipMemsetAsync(r->d_dng, 0, (size_t)cap * DNG_SLOT_BYTES, h->stream) != hipSuccess) || hipStreamSynchronize(h->stream) != hipSuccess ||
+        (r->d_dng && hipMemsetAsync(r->d_dng, 0, (size_t)cap * DNG_SLOT_BYTES, h->stream) != hipSuccess) ||
+        (r->d_dtb && hipMemsetAsync(r->d_dtb, 0, (size_t)cap * DT_SLOT_BYTES, h->stream) != hipSuccess) || hipStreamSynchronize(h->stream) != hipSuccess ||
         upload_chain(r->chain, M, R.slot_first, R.slot_logs) != hipSuccess ||
         hipMemcpy(r->d_powers, pw.data(), (size_t)r->n_powers * 8, hipMemcpyHostToDevice) != hipSuccess || (rc = logreplay_clear_impl(r))) {
         rmj_logreplay_destroy(r);
@@ -2452,6 +2503,7 @@ int rmj_logreplay_destroy(rmj_logreplay_handle r) {
     hipFree(r->mem);
     if (r->d_hid) hipFree(r->d_hid);
     if (r->d_dng) hipFree(r->d_dng);
+    if (r->d_dtb) hipFree(r->d_dtb);
     delete r;
     return RMJ_OK;
 }
@@ -2486,6 +2538,7 @@ int rmj_logreplay_run_device(rmj_logreplay_handle r, uint32_t n_steps, uint32_t*
 #undef RMJ_LAUNCH_RECORD
         if (r->d_hid) hipLaunchKernelGGL(k_log_hidden, dim3(n * 4), dim3(64), 0, h->stream, h->d, R, r->d_hid);   // the state is still the one the rows were encoded from
         if (r->d_dng) hipLaunchKernelGGL(k_log_danger, dim3(n * 4), dim3(64), 0, h->stream, h->d, R, r->d_dng);
+        if (r->d_dtb) dt_launch_log(h->stream, h->d, R, r->d_dtb);
         launch_log_apply(h, n, R.ev, R.apply_at);
     }
     r->chain.step += todo;
@@ -2540,6 +2593,19 @@ int rmj_logreplay_emit_danger_device(rmj_logreplay_handle r, const RmjLogDangerB
     const uint32_t cap = r->R.capacity;
     hipLaunchKernelGGL(k_log_emit_scan, dim3((cap + PPO_SCAN_BLOCK - 1) / PPO_SCAN_BLOCK), dim3(PPO_SCAN_BLOCK), 0, h->stream, r->R);
     hipLaunchKernelGGL(k_log_emit_danger, ppo_wave_grid(cap), dim3(256), 0, h->stream, r->R, (const uint8_t*)r->d_dng, out->d_danger, out->rows);
+    HIPCHK(hipGetLastError());
+    return RMJ_OK;
+}
+int rmj_logreplay_emit_dtable_device(rmj_logreplay_handle r, const RmjLogDtableBatch* out) {
+    if (!r || !out) return fail(RMJ_ERR_ARG, "null argument");
+    if (!r->d_dtb) return fail(RMJ_ERR_ARG, "rmj_logreplay_emit_dtable_device: the builder was made without RMJ_LOGREPLAY_DTABLE");
+    if (out->rows && (!out->d_shanten || !out->d_accept || !out->d_ukeire)) return fail(RMJ_ERR_ARG, "null argument");
+    rmj_env* h = r->env;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const uint32_t cap = r->R.capacity;
+    LogDtableOut O{out->d_shanten, out->d_accept, out->d_ukeire, out->rows};
+    hipLaunchKernelGGL(k_log_emit_scan, dim3((cap + PPO_SCAN_BLOCK - 1) / PPO_SCAN_BLOCK), dim3(PPO_SCAN_BLOCK), 0, h->stream, r->R);
+    dt_launch_log_emit(h->stream, r->R, (const uint8_t*)r->d_dtb, O);
     HIPCHK(hipGetLastError());
     return RMJ_OK;
 }
@@ -2715,6 +2781,36 @@ int rmj_effective_tiles(int device, const uint8_t* counts, uint32_t n, int sanma
 }
 int rmj_best_ukeire(int device, const uint8_t* counts, const uint8_t* visible, uint32_t n, int sanma, uint32_t* out) {
     return run_ukeire(device, counts, visible, n, sanma, 1, out);
+}
+int rmj_discard_table_hands(int device, const uint8_t* counts, const uint8_t* visible, uint32_t n, int sanma, const RmjDiscardTableOut* out) {
+    DevTmp tmp;
+    if (!counts || !out || !out->d_shanten || !out->d_accept || !out->d_ukeire) return fail(RMJ_ERR_ARG, "null argument");
+    int rc = ensure_device(device);
+    if (rc) return rc;
+    if (n == 0) return RMJ_OK;
+    ShantenTables T;
+    if ((rc = shanten_tables_for(device, &T))) return rc;
+    const size_t cells = (size_t)n * RMJ_DTAB_COLS;
+    uint8_t *d_c = nullptr, *d_v = nullptr;
+    RmjDiscardTableOut d{};
+    HIPCHK(tmp.alloc(&d_c, (size_t)n * 34));
+    HIPCHK(tmp.alloc(&d.d_shanten, cells));
+    HIPCHK(tmp.alloc(&d.d_accept, cells));
+    HIPCHK(tmp.alloc(&d.d_ukeire, cells));
+    if (out->d_mask) HIPCHK(tmp.alloc(&d.d_mask, cells * 8));
+    HIPCHK(hipMemcpy(d_c, counts, (size_t)n * 34, hipMemcpyHostToDevice));
+    if (visible) {
+        HIPCHK(tmp.alloc(&d_v, (size_t)n * 34));
+        HIPCHK(hipMemcpy(d_v, visible, (size_t)n * 34, hipMemcpyHostToDevice));
+    }
+    dt_launch_hands(T, d_c, d_v, n, sanma, d);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out->d_shanten, d.d_shanten, cells, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out->d_accept, d.d_accept, cells, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out->d_ukeire, d.d_ukeire, cells, hipMemcpyDeviceToHost));
+    if (out->d_mask) HIPCHK(hipMemcpy(out->d_mask, d.d_mask, cells * 8, hipMemcpyDeviceToHost));
+    return RMJ_OK;
 }
 
 // ---- MJAI event ingestion (row N1) --------------------------------------------------------------
@@ -3039,3 +3135,17 @@ int rmj_prof_fetch(uint32_t n_games, uint64_t* cyc, uint64_t* cnt, int reset) {
 #endif
 
 }  // extern "C"
+
+// ---- the discard table's launches: the first naming of its kernels, behind everything else in the code object (rmj_dtable.hip.h)
+static void dt_launch_rows(hipStream_t st, const Env& E, const int32_t* d_index, uint32_t rows, const uint32_t* d_count, const RmjDiscardTableOut& O) {
+    hipLaunchKernelGGL(k_dtable_rows<0>, dim3((rows + 3u) / 4u), dim3(256), 0, st, E, d_index, rows, d_count, O);
+}
+static void dt_launch_hands(const ShantenTables& T, const uint8_t* counts, const uint8_t* visible, uint32_t n, int sanma, const RmjDiscardTableOut& O) {
+    hipLaunchKernelGGL(k_dtable_hands<0>, dim3((n + 3) / 4), dim3(256), 0, 0, T, counts, visible, n, sanma, O);
+}
+static void dt_launch_log(hipStream_t st, const Env& E, const LogRun& R, uint8_t* dtb) {
+    hipLaunchKernelGGL(k_log_dtable<0>, dim3(R.n * 4), dim3(64), 0, st, E, R, dtb);
+}
+static void dt_launch_log_emit(hipStream_t st, const LogRun& R, const uint8_t* dtb, const LogDtableOut& O) {
+    hipLaunchKernelGGL(k_log_emit_dtable<0>, ppo_wave_grid(R.capacity), dim3(256), 0, st, R, dtb, O);
+}

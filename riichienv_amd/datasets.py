@@ -94,6 +94,12 @@ class LogSampleBuilder:
     danger=False: with True samples() gains "danger" [N, 3, 37] i32 - the points opponent (seat + 1 + r) mod NP would win by ron if the
     deciding seat discarded a tile of kind c at the moment of the decision (the rows of TorchVecEnv.danger_compact without ura: logs
     carry no wall); 224 more bytes per pool slot.  Independent of hidden, combinable with it, refused over masked sets like it.
+    efficiency=False: with True samples() gains "dt_shanten" [N, 35] i8, "dt_accept" [N, 35] u8, "dt_ukeire" [N, 35] u8 - the discard efficiency
+    table of the deciding seat at the moment of the decision (the rows of TorchVecEnv.discard_table_compact without the masks: column t <
+    34 the shanten after discarding type t, abi.DTAB_NONE where there is no such discard, the types that then lower it and their live
+    tiles; column 34 the hand itself); 112 more bytes per pool slot.  Independent of hidden and danger, combinable with them.  The table
+    needs only the deciding seat's own hand, but a set made with masked_ok=True does not say per sample whether that seat's tiles were
+    masked, so it is refused over such sets like danger.
     rewards: finalize(rewards) takes a float64 [K, 4] table by kyoku row (`kyoku_offsets[log] + kyoku - 1`; the GRP reward model's
     output) - default: the seat's score change of the kyoku times kyoku_scale.
     on_error (text): "raise" or "drop" as LogSet takes them; after a drop the `log` field of the samples counts set logs (`log_ids`)."""
@@ -128,7 +134,7 @@ class LogSampleBuilder:
         return self._attach(LogSet.from_device_text(text, offsets, self.n_players, masked_ok, device, on_error), True)
 
     def _settings(self, game_mode, on_error="raise", features="base", n_slots=None, capacity=None, gamma=0.99, include_pass=True, skip_single_action=True,
-                  rule=None, share_stream=True, kyoku_scale=1.0 / 1000.0, hidden=False, danger=False):
+                  rule=None, share_stream=True, kyoku_scale=1.0 / 1000.0, hidden=False, danger=False, efficiency=False):
         """validates and stores what every constructor shares (no device work)"""
         import torch
 
@@ -149,7 +155,7 @@ class LogSampleBuilder:
         self.n_slots, self.capacity = n_slots, capacity
         self.gamma, self.kyoku_scale = float(gamma), float(kyoku_scale)
         self.include_pass, self.skip_single_action = bool(include_pass), bool(skip_single_action)
-        self.shared, self.hidden, self.danger = bool(share_stream), bool(hidden), bool(danger)
+        self.shared, self.hidden, self.danger, self.efficiency = bool(share_stream), bool(hidden), bool(danger), bool(efficiency)
         self._finalized = False
         self._emitted = None    # what samples() returned last, until run() / finalize() / clear()
         self.h = self.env = self.logset = None
@@ -176,6 +182,9 @@ class LogSampleBuilder:
                 raise ValueError("hidden=True over a log set made with masked_ok=True: the masked seats' tiles are unknown, so are their hands, shanten and waits")
             if self.danger and getattr(logset, "masked_ok", False):
                 raise ValueError("danger=True over a log set made with masked_ok=True: the masked seats' tiles are unknown, so is what they would win")
+            if self.efficiency and getattr(logset, "masked_ok", False):
+                raise ValueError("efficiency=True over a log set made with masked_ok=True: the set does not tell which seats' tiles are masked, and a "
+                                 "masked deciding seat has no hand to tabulate")
             for k in ("logs", "M", "device", "kyoku_offsets", "n_kyokus", "log_ids", "dropped", "lengths"):
                 setattr(self, k, getattr(logset, k))
             self.host_seconds = dict(logset.host_seconds)
@@ -190,7 +199,8 @@ class LogSampleBuilder:
                 vecenv._chk(L.rmj_set_stream(self.env.h, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream), 0))
             self._powers = gamma_powers(self.gamma, logset.longest_log + 1)
             flags = (abi.LOGREPLAY_INCLUDE_PASS if self.include_pass else 0) | (abi.LOGREPLAY_SKIP_SINGLE_ACTION if self.skip_single_action else 0) | \
-                (abi.LOGREPLAY_HIDDEN if self.hidden else 0) | (abi.LOGREPLAY_DANGER if self.danger else 0)
+                (abi.LOGREPLAY_HIDDEN if self.hidden else 0) | (abi.LOGREPLAY_DANGER if self.danger else 0) | \
+                (abi.LOGREPLAY_DTABLE if self.efficiency else 0)
             cfg = abi.LogReplayConfig(self._feat, self.capacity, flags, len(self._powers), self.gamma, self._powers.ctypes.data)
             h = C.c_void_p()
             vecenv._chk(L.rmj_logreplay_create(self.env.h, logset.handle, C.byref(cfg), C.byref(h)))
@@ -323,7 +333,9 @@ class LogSampleBuilder:
                "opp_waits": t.empty((k, 3), dtype=t.int64, device=d), "opp_flags": t.empty((k, 3), dtype=t.uint8, device=d),
                "event": t.empty((k,), dtype=t.int32, device=d)} if self.hidden else {}
         dng = {"danger": t.empty((k, 3, abi.DANGER_KINDS), dtype=t.int32, device=d)} if self.danger else {}
-        return {**self._empty_plain(k), **hid, **dng}
+        eff = {"dt_shanten": t.empty((k, abi.DTAB_COLS), dtype=t.int8, device=d), "dt_accept": t.empty((k, abi.DTAB_COLS), dtype=t.uint8, device=d),
+               "dt_ukeire": t.empty((k, abi.DTAB_COLS), dtype=t.uint8, device=d)} if self.efficiency else {}
+        return {**self._empty_plain(k), **hid, **dng, **eff}
 
     def _empty_plain(self, k):
         t, d = self.torch, self.device
@@ -336,7 +348,7 @@ class LogSampleBuilder:
     def samples(self):
         """The dataset: {"features" [N, C, W] f32, "action" [N] i64, "return" [N] f32, "return64" [N] f64, "mask" [N, A] u8, "rank" [N] i64,
         "packed" [N] i64 (the packed action's bits), "log", "kyoku", "seat", "t" [N] i32} - with hidden=True also "opp_hand", "opp_shanten",
-        "opp_waits", "opp_flags" and "event", with danger=True "danger" (class docstring), same rows, same order - on the device, in pool order - the samples of the
+        "opp_waits", "opp_flags" and "event", with danger=True "danger", with efficiency=True "dt_shanten", "dt_accept", "dt_ukeire" (class docstring), same rows, same order - on the device, in pool order - the samples of the
         logs replayed to their end, without the trajectories that lost a sample to a full pool (rmj_logreplay_emit_device).  Finalizes with
         the default rewards if finalize() was not called since the last run.  Reads the pool's fill on the host to size the tensors.  The
         result is kept (and returned again, the same tensors) until run(), finalize() or clear()."""
@@ -362,6 +374,9 @@ class LogSampleBuilder:
         if self.danger:
             db = abi.LogDangerBatch(out["danger"].data_ptr(), rows, 0)
             vecenv._chk(self.L.rmj_logreplay_emit_danger_device(self.h, C.byref(db)))
+        if self.efficiency:
+            eb = abi.LogDtableBatch(out["dt_shanten"].data_ptr(), out["dt_accept"].data_ptr(), out["dt_ukeire"].data_ptr(), rows, 0)
+            vecenv._chk(self.L.rmj_logreplay_emit_dtable_device(self.h, C.byref(eb)))
         self._sync()
         k = int(cnt[0])
         self._emitted = {name: v[:k] for name, v in out.items()}

@@ -198,6 +198,31 @@ class TorchVecEnv:
             self.sync()
         return out
 
+    def discard_table_compact(self, index, count=None, out=None):
+        """Discard efficiency table of the rows of a compact batch: index [k] int32 = game * 4 + seat -> {"shanten" int8 [k, 35], "accept"
+        uint8 [k, 35], "ukeire" uint8 [k, 35], "mask" int64 [k, 35] (bit t = tile type t)} on the device - column t < 34: the shanten
+        after discarding type t (abi.DTAB_NONE: no such discard), the types that then lower it and their live tiles; column 34: the hand
+        itself (rmj_discard_table_device).  count: the device count tensor of obs_compact(sync_count=False) - rows at or behind it are
+        left as they were; out: the dict of an earlier call to write into (no allocation)."""
+        t = self.torch
+        idx = index.to(device=self.device, dtype=t.int32).contiguous().reshape(-1)
+        k = int(idx.shape[0])
+        names = ("shanten", "accept", "ukeire", "mask")
+        if out is None:
+            out = {"shanten": t.full((k, abi.DTAB_COLS), abi.DTAB_NONE, dtype=t.int8, device=self.device),
+                   "accept": t.zeros((k, abi.DTAB_COLS), dtype=t.uint8, device=self.device),
+                   "ukeire": t.zeros((k, abi.DTAB_COLS), dtype=t.uint8, device=self.device),
+                   "mask": t.zeros((k, abi.DTAB_COLS), dtype=t.int64, device=self.device)}
+        assert all(out[f].shape[0] >= k and out[f].is_contiguous() for f in names), "out is too small for the index"
+        if k:
+            if not self.shared:
+                t.cuda.current_stream(self.device).synchronize()   # the buffers were made on torch's stream
+            b = abi.DiscardTableOut(*(out[f].data_ptr() for f in names))
+            vecenv._chk(self.env.L.rmj_discard_table_device(self.env.h, C.c_void_p(idx.data_ptr()), k, None if count is None else C.c_void_p(count.data_ptr()),
+                                                            0, C.byref(b)))
+            self.sync()
+        return out
+
     def scores(self):
         vecenv._chk(self.env.L.rmj_scores_device(self.env.h, C.c_void_p(self._scores.data_ptr()), None))
         self.sync()

@@ -386,6 +386,20 @@ class VecRiichiEnv:
             _chk(self.L.rmj_danger_targets(self.h, idx.ctypes.data, k, abi.DANGER_URA if ura else 0, C.byref(b)))
         return out
 
+    def discard_table(self, index):
+        """Discard efficiency table of the seats `index` [k] = game * 4 + seat (any seat, acting or not): {"shanten" int8 [k, 35],
+        "accept" uint8 [k, 35], "ukeire" uint8 [k, 35], "mask" uint64 [k, 35]} - column t < 34: the shanten after discarding a tile of
+        type t from a 3n+2 hand (abi.DTAB_NONE: not held, or no discard to make), the tile types that then lower it (count and bits)
+        and how many of them are not visible; column 34: the hand itself, with the maxima rmj_effective_tiles / rmj_best_ukeire give
+        - rmj_discard_table (header: the definition).  An index out of range, or seat 3 in 3P, gives an absent row."""
+        idx = np.ascontiguousarray(index, dtype=np.int32).reshape(-1)
+        k = int(idx.size)
+        out = _dtable_arrays(k)
+        if k:
+            b = abi.DiscardTableOut(*(out[f].ctypes.data for f in ("shanten", "accept", "ukeire", "mask")))
+            _chk(self.L.rmj_discard_table(self.h, idx.ctypes.data, k, 0, C.byref(b)))
+        return out
+
     def determinize(self, index, seed, hold=None, riichi_tenpai=False):
         """Re-deal, in place, what the seats `index` [k] = game * 4 + seat (one row per game; the seat must be to act) cannot see: their
         opponents' concealed hands and the wall that can still be drawn or revealed, by the permutation the header defines for (seed,
@@ -810,6 +824,26 @@ def best_ukeire(counts, visible, sanma=False, device=0):
     assert counts.shape == visible.shape
     out = np.zeros(counts.shape[0], np.uint32)
     _chk(L.rmj_best_ukeire(device, counts.ctypes.data, visible.ctypes.data, counts.shape[0], int(sanma), out.ctypes.data))
+    return out
+
+
+def _dtable_arrays(k):
+    return {"shanten": np.full((k, abi.DTAB_COLS), abi.DTAB_NONE, np.int8), "accept": np.zeros((k, abi.DTAB_COLS), np.uint8),
+            "ukeire": np.zeros((k, abi.DTAB_COLS), np.uint8), "mask": np.zeros((k, abi.DTAB_COLS), np.uint64)}
+
+
+def discard_table(counts, visible=None, sanma=False, device=0):
+    """Discard efficiency table of [n][34] hand type histograms against [n][34] visible histograms (None: nothing visible): the dict of
+    VecRiichiEnv.discard_table - rmj_discard_table_hands.  A hand of more than 14 tiles, or a count above 4, gives an absent row."""
+    L = load_lib()
+    counts = np.ascontiguousarray(counts, dtype=np.uint8).reshape(-1, 34)
+    n = counts.shape[0]
+    if visible is not None:
+        visible = np.ascontiguousarray(visible, dtype=np.uint8).reshape(-1, 34)
+        assert counts.shape == visible.shape
+    out = _dtable_arrays(n)
+    b = abi.DiscardTableOut(*(out[f].ctypes.data for f in ("shanten", "accept", "ukeire", "mask")))
+    _chk(L.rmj_discard_table_hands(device, counts.ctypes.data, None if visible is None else visible.ctypes.data, n, int(sanma), C.byref(b)))
     return out
 
 
