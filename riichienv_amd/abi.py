@@ -8,6 +8,7 @@ the test-only oracle binding (oracle/oracle.py).
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 
 NP = 4
@@ -300,6 +301,39 @@ DTAB_NONE, DTAB_COLS = 127, 35     # RMJ_DTAB_*: the shanten of an absent column
 
 class DiscardTableOut(C.Structure):  # RmjDiscardTableOut (rmj_discard_table_device); mask may be NULL
     _fields_ = [(k, C.c_void_p) for k in ("shanten", "accept", "ukeire", "mask")]
+
+
+# The row targets (index[k] = game * 4 + seat -> fixed-shape rows): the out-struct of the C entries and, in the struct's order, every
+# field's name, numpy dtype, shape behind the row axis and the value of a row the call leaves alone.  torch has no arithmetic on uint64:
+# there a uint64 field is int64 (torch_dtype).  The one place that states these shapes: VecRiichiEnv, TorchVecEnv, LogSampleBuilder and
+# the benchmarks of the targets allocate from it.
+RowField = collections.namedtuple("RowField", "name dtype shape fill")
+RowTarget = collections.namedtuple("RowTarget", "struct fields")
+ROW_TARGETS = {
+    "hidden": RowTarget(HiddenOut, (RowField("opp_hand", "uint8", (3, 34), 0), RowField("opp_shanten", "int8", (3,), 0),
+                                    RowField("opp_waits", "int64", (3,), 0), RowField("opp_flags", "uint8", (3,), 0))),
+    "danger": RowTarget(DangerOut, (RowField("danger", "int32", (3, DANGER_KINDS), 0),)),
+    "discard_table": RowTarget(DiscardTableOut, (RowField("shanten", "int8", (DTAB_COLS,), DTAB_NONE), RowField("accept", "uint8", (DTAB_COLS,), 0),
+                                                 RowField("ukeire", "uint8", (DTAB_COLS,), 0), RowField("mask", "uint64", (DTAB_COLS,), 0))),
+}
+
+
+def torch_dtype(torch, name):
+    """the torch dtype of a RowField's numpy dtype name"""
+    return getattr(torch, "int64" if name == "uint64" else name)
+
+
+def row_arrays(target, k):
+    """{field: numpy array [k, ...]} of a row target, every row as a call leaves an absent one"""
+    import numpy as np
+
+    return {f.name: np.full((k,) + f.shape, f.fill, f.dtype) for f in ROW_TARGETS[target].fields}
+
+
+def row_struct(target, arrays):
+    """the out-struct of a row target over {field: numpy array or torch tensor}"""
+    t = ROW_TARGETS[target]
+    return t.struct(*(a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data for a in (arrays[f.name] for f in t.fields)))
 
 
 DET_OK, DET_NOT_ACTING, DET_CHANKAN, DET_DUPLICATE, DET_RIICHI_NOTEN = 0, 1, 2, 3, 16   # RMJ_DET_*: determinize status (RIICHI_NOTEN << r, r = 0, 1, 2)

@@ -62,7 +62,24 @@ using namespace rmj;
 static void dt_launch_rows(hipStream_t st, const Env& E, const int32_t* d_index, uint32_t rows, const uint32_t* d_count, const RmjDiscardTableOut& O);
 static void dt_launch_hands(const ShantenTables& T, const uint8_t* counts, const uint8_t* visible, uint32_t n, int sanma, const RmjDiscardTableOut& O);
 static void dt_launch_log(hipStream_t st, const Env& E, const LogRun& R, uint8_t* dtb);
+static void hid_launch_log(hipStream_t st, const Env& E, const LogRun& R, uint8_t* hid);
+static void dng_launch_log(hipStream_t st, const Env& E, const LogRun& R, uint8_t* dng);
 static void dt_launch_log_emit(hipStream_t st, const LogRun& R, const uint8_t* dtb, const LogDtableOut& O);
+
+// The extra records a log sample builder's pool can keep, in the order a replay step launches their kernels: the RMJ_LOGREPLAY_* flag
+// that asks for them (and its name), the bytes of a slot's record, what the messages call them, and the launch of the kernel that
+// records a step's rows from the state before the step's event (`records`: [capacity][slot_bytes], an allocation of its own).
+struct LogExtra {
+    uint32_t flag;
+    const char* flag_name;
+    size_t slot_bytes;
+    const char* noun;
+    void (*launch)(hipStream_t st, const Env& E, const LogRun& R, uint8_t* records);
+};
+enum { LX_HIDDEN, LX_DANGER, LX_DTABLE, LX_COUNT };
+static const LogExtra kLogExtras[LX_COUNT] = {{RMJ_LOGREPLAY_HIDDEN, "RMJ_LOGREPLAY_HIDDEN", HID_SLOT_BYTES, "hidden", hid_launch_log},
+                                              {RMJ_LOGREPLAY_DANGER, "RMJ_LOGREPLAY_DANGER", DNG_SLOT_BYTES, "danger", dng_launch_log},
+                                              {RMJ_LOGREPLAY_DTABLE, "RMJ_LOGREPLAY_DTABLE", DT_SLOT_BYTES, "discard efficiency", dt_launch_log}};
 
 static inline dim3 step_grid(uint32_t n) { return dim3((n + RMJ_STEP_WPB - 1) / RMJ_STEP_WPB); }
 static_assert(rmjh::kStepRowsShift == STEP_F_ROWS_SHIFT, "rmj_host.h states the step kernels' rows flag position");
@@ -280,6 +297,31 @@ static int encode_seq_host(rmj_env* h, int game_style, const Buffers* out, const
     }
     return RMJ_OK;
 }
+// The same for the per-row calls (index[i] = game * 4 + seat): the index and the row arrays at 256-byte steps of the handle's scratch.  An
+// array is where its device pointer lives, the caller's host array, its bytes per row and whether it goes UP to the device before the call or
+// comes DOWN after it; a NULL host array - the entries have refused every one that is not optional - is not staged and its pointer stays NULL.
+struct RowArray { void* slot; void* host; size_t row_bytes; enum { DOWN, UP } dir = DOWN; };
+template <class Call>
+static int row_call_host(rmj_env* h, const int32_t* index, uint32_t rows, std::initializer_list<RowArray> arrays, Call call) {
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const size_t r = rows;
+    int32_t* d_index;
+    rmjh::DevLayout L;
+    L.add(&d_index, r * 4);
+    for (const RowArray& a : arrays)
+        if (a.host) L.add((char**)a.slot, r * a.row_bytes);
+    int rc = scratch_for(h, L);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(d_index, index, r * 4, hipMemcpyHostToDevice));
+    for (const RowArray& a : arrays)
+        if (a.host && a.dir == RowArray::UP) HIPCHK(hipMemcpy(*(char**)a.slot, a.host, r * a.row_bytes, hipMemcpyHostToDevice));
+    if ((rc = call(d_index))) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (const RowArray& a : arrays)
+        if (a.host && a.dir == RowArray::DOWN) HIPCHK(hipMemcpy(a.host, *(char**)a.slot, r * a.row_bytes, hipMemcpyDeviceToHost));
+    return RMJ_OK;
+}
 // Average ms of one `launch` (returns an RMJ code): a warm-up, then `reps` launches between two events on `st`; settle: the warm-up is waited for
 template <class Launch>
 static int time_launches(hipStream_t st, uint32_t reps, bool settle, double* avg_ms, Launch launch) {
@@ -334,9 +376,7 @@ struct rmj_logreplay {
     void* mem = nullptr;
     LogRun R{};
     double* d_powers = nullptr;
-    uint8_t* d_hid = nullptr;          // RMJ_LOGREPLAY_HIDDEN: [capacity][HID_SLOT_BYTES] hidden records, an allocation of its own (rmj_hidden.hip.h)
-    uint8_t* d_dtb = nullptr;          // RMJ_LOGREPLAY_DTABLE: [capacity][DT_SLOT_BYTES] discard efficiency records, an allocation of its own (rmj_dtable.hip.h)
-    uint8_t* d_dng = nullptr;          // RMJ_LOGREPLAY_DANGER: [capacity][DNG_SLOT_BYTES] danger records, an allocation of its own (rmj_danger.hip.h)
+    uint8_t* d_extra[LX_COUNT] = {};   // the records of kLogExtras[i], [capacity][slot_bytes] in an allocation of its own; NULL: made without its flag
     uint32_t n_powers = 0;
     rmjh::SlotChain chain;             // which slot replays which logs, the steps of a whole replay and the steps taken
 };
@@ -437,6 +477,21 @@ static rmjh::RolloutPlan plan_rollout(rmj_env* h, uint32_t n_steps, int pol, boo
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->cfg.device) == hipSuccess)
         *slots = (uint32_t)(per_cu > 0 ? per_cu : 1) * (uint32_t)(cus > 0 ? cus : 1);
     return plan();
+}
+// An emit entry of the extra records `which` (entry: its name): the checks, then `emit(stream, records)` behind the scan k_log_emit runs behind;
+// no_array: the batch has rows and lacks an array
+template <class Emit>
+static int logreplay_emit_extra(rmj_logreplay* r, int which, const char* entry, const void* out, bool no_array, Emit emit) {
+    if (!r || !out) return fail(RMJ_ERR_ARG, "null argument");
+    const uint8_t* records = r->d_extra[which];
+    if (!records) return fail(RMJ_ERR_ARG, std::string(entry) + ": the builder was made without " + kLogExtras[which].flag_name);
+    if (no_array) return fail(RMJ_ERR_ARG, "null argument");
+    rmj_env* h = r->env;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    hipLaunchKernelGGL(k_log_emit_scan, dim3((r->R.capacity + PPO_SCAN_BLOCK - 1) / PPO_SCAN_BLOCK), dim3(PPO_SCAN_BLOCK), 0, h->stream, r->R);
+    emit(h->stream, records);
+    HIPCHK(hipGetLastError());
+    return RMJ_OK;
 }
 // (defined in its section: ahead of rmj_step_random_encode it would put k_encode_base before the fused step kernels in the code object)
 static void launch_encode_base_range(rmj_env* h, hipStream_t st, int only_active, float* d_out, uint32_t g0, uint32_t g1);
@@ -1847,24 +1902,10 @@ int rmj_hidden_targets(rmj_handle h, const int32_t* index, uint32_t rows, const 
     if (!h || !out) return fail(RMJ_ERR_ARG, "null argument");
     if (!rows) return RMJ_OK;
     if (!index || !out->d_opp_hand || !out->d_opp_shanten || !out->d_opp_waits || !out->d_opp_flags) return fail(RMJ_ERR_ARG, "null argument");
-    HIPCHK(hipSetDevice(h->cfg.device));
-    // the index and the four arrays at 256-byte steps of the handle's scratch
-    const size_t r = rows;
-    int32_t* d_index;
     RmjHiddenOut d{};
-    rmjh::DevLayout L;
-    L.add(&d_index, r * 4); L.add(&d.d_opp_waits, r * 24); L.add(&d.d_opp_hand, r * 102); L.add(&d.d_opp_flags, r * 3); L.add(&d.d_opp_shanten, r * 3);
-    int rc = scratch_for(h, L);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(d_index, index, r * 4, hipMemcpyHostToDevice));
-    if ((rc = rmj_hidden_targets_device(h, d_index, rows, nullptr, &d))) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(out->d_opp_waits, d.d_opp_waits, r * 24, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out->d_opp_hand, d.d_opp_hand, r * 102, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out->d_opp_flags, d.d_opp_flags, r * 3, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out->d_opp_shanten, d.d_opp_shanten, r * 3, hipMemcpyDeviceToHost));
-    return RMJ_OK;
+    return row_call_host(h, index, rows,
+                         {{&d.d_opp_waits, out->d_opp_waits, 24}, {&d.d_opp_hand, out->d_opp_hand, 102}, {&d.d_opp_flags, out->d_opp_flags, 3}, {&d.d_opp_shanten, out->d_opp_shanten, 3}},
+                         [&](const int32_t* d_index) { return rmj_hidden_targets_device(h, d_index, rows, nullptr, &d); });
 }
 // ---- deal-in danger targets (rmj_danger.hip.h) -------------------------------------------------------------------
 int rmj_danger_targets_device(rmj_handle h, const int32_t* d_index, uint32_t rows, const uint32_t* d_count, uint32_t flags, const RmjDangerOut* out) {
@@ -1882,20 +1923,9 @@ int rmj_danger_targets(rmj_handle h, const int32_t* index, uint32_t rows, uint32
     if (flags & ~(uint32_t)RMJ_DANGER_URA) return fail(RMJ_ERR_ARG, "rmj_danger_targets: unknown flag");
     if (!rows) return RMJ_OK;
     if (!index || !out->d_danger) return fail(RMJ_ERR_ARG, "null argument");
-    HIPCHK(hipSetDevice(h->cfg.device));
-    const size_t r = rows, bytes = r * 3 * RMJ_DANGER_KINDS * 4;
-    int32_t* d_index;
     RmjDangerOut d{};
-    rmjh::DevLayout L;
-    L.add(&d_index, r * 4); L.add(&d.d_danger, bytes);
-    int rc = scratch_for(h, L);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(d_index, index, r * 4, hipMemcpyHostToDevice));
-    if ((rc = rmj_danger_targets_device(h, d_index, rows, nullptr, flags, &d))) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(out->d_danger, d.d_danger, bytes, hipMemcpyDeviceToHost));
-    return RMJ_OK;
+    return row_call_host(h, index, rows, {{&d.d_danger, out->d_danger, 3 * RMJ_DANGER_KINDS * 4}},
+                         [&](const int32_t* d_index) { return rmj_danger_targets_device(h, d_index, rows, nullptr, flags, &d); });
 }
 // ---- discard efficiency table (rmj_dtable.hip.h) -----------------------------------------------------------------
 int rmj_discard_table_device(rmj_handle h, const int32_t* d_index, uint32_t rows, const uint32_t* d_count, uint32_t flags, const RmjDiscardTableOut* out) {
@@ -1913,24 +1943,11 @@ int rmj_discard_table(rmj_handle h, const int32_t* index, uint32_t rows, uint32_
     if (flags) return fail(RMJ_ERR_ARG, "rmj_discard_table: unknown flag");
     if (!rows) return RMJ_OK;
     if (!index || !out->d_shanten || !out->d_accept || !out->d_ukeire) return fail(RMJ_ERR_ARG, "null argument");
-    HIPCHK(hipSetDevice(h->cfg.device));
-    const size_t cells = (size_t)rows * RMJ_DTAB_COLS;
-    int32_t* d_index;
     RmjDiscardTableOut d{};
-    rmjh::DevLayout L;
-    L.add(&d_index, (size_t)rows * 4); L.add(&d.d_shanten, cells); L.add(&d.d_accept, cells); L.add(&d.d_ukeire, cells);
-    if (out->d_mask) L.add(&d.d_mask, cells * 8);
-    int rc = scratch_for(h, L);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(d_index, index, (size_t)rows * 4, hipMemcpyHostToDevice));
-    if ((rc = rmj_discard_table_device(h, d_index, rows, nullptr, flags, &d))) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(out->d_shanten, d.d_shanten, cells, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out->d_accept, d.d_accept, cells, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out->d_ukeire, d.d_ukeire, cells, hipMemcpyDeviceToHost));
-    if (out->d_mask) HIPCHK(hipMemcpy(out->d_mask, d.d_mask, cells * 8, hipMemcpyDeviceToHost));
-    return RMJ_OK;
+    return row_call_host(h, index, rows,
+                         {{&d.d_shanten, out->d_shanten, RMJ_DTAB_COLS}, {&d.d_accept, out->d_accept, RMJ_DTAB_COLS}, {&d.d_ukeire, out->d_ukeire, RMJ_DTAB_COLS},
+                          {&d.d_mask, out->d_mask, RMJ_DTAB_COLS * 8}},
+                         [&](const int32_t* d_index) { return rmj_discard_table_device(h, d_index, rows, nullptr, flags, &d); });
 }
 // ---- determinize (rmj_determinize.hip.h) ------------------------------------------------------------------------
 int rmj_determinize_device(rmj_handle h, const int32_t* d_index, uint32_t rows, const uint32_t* d_count, const RmjDeterminize* p) {
@@ -1972,22 +1989,9 @@ int rmj_determinize_ex(rmj_handle h, const int32_t* index, uint32_t rows, const 
         std::sort(games.begin(), games.end());
         if (std::adjacent_find(games.begin(), games.end()) != games.end()) return fail(RMJ_ERR_ARG, "rmj_determinize: two rows name the same game");
     }
-    HIPCHK(hipSetDevice(h->cfg.device));
-    const size_t r = rows;
-    int32_t* d_index;
-    uint8_t *d_hold, *d_status;
-    rmjh::DevLayout L;
-    L.add(&d_index, r * 4); L.add(&d_hold, r); L.add(&d_status, r);
-    int rc = scratch_for(h, L);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(d_index, index, r * 4, hipMemcpyHostToDevice));
-    if (p->d_hold) HIPCHK(hipMemcpy(d_hold, p->d_hold, r, hipMemcpyHostToDevice));
-    RmjDeterminize d{p->seed, p->d_hold ? d_hold : nullptr, d_status};
-    if ((rc = rmj_determinize_ex_device(h, d_index, rows, nullptr, &d, flags))) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (p->d_status) HIPCHK(hipMemcpy(p->d_status, d_status, r, hipMemcpyDeviceToHost));
-    return RMJ_OK;
+    RmjDeterminize d{p->seed, nullptr, nullptr};
+    return row_call_host(h, index, rows, {{&d.d_hold, (void*)p->d_hold, 1, RowArray::UP}, {&d.d_status, p->d_status, 1}},
+                         [&](const int32_t* d_index) { return rmj_determinize_ex_device(h, d_index, rows, nullptr, &d, flags); });
 }
 int rmj_determinize_order(uint64_t seed, uint64_t global_game, uint32_t seat, uint32_t m, uint32_t* perm) {
     if (m > 256u || (m && !perm)) return fail(RMJ_ERR_ARG, "rmj_determinize_order: m <= 256 and a perm array");
@@ -2408,7 +2412,9 @@ int rmj_logreplay_create(rmj_handle h, rmj_logset_handle set, const RmjLogReplay
     if (set->device != h->cfg.device) return fail(RMJ_ERR_ARG, "rmj_logreplay_create: the log set lives on another device");
     const uint32_t n = h->cfg.n_games;
     if (n > set->M) return fail(RMJ_ERR_ARG, "rmj_logreplay_create: more slots (the handle's games) than logs: n_slots <= M");
-    if (cfg->flags & ~(uint32_t)(RMJ_LOGREPLAY_INCLUDE_PASS | RMJ_LOGREPLAY_SKIP_SINGLE_ACTION | RMJ_LOGREPLAY_HIDDEN | RMJ_LOGREPLAY_DANGER | RMJ_LOGREPLAY_DTABLE)) return fail(RMJ_ERR_ARG, "rmj_logreplay_create: unknown flag");
+    uint32_t known = RMJ_LOGREPLAY_INCLUDE_PASS | RMJ_LOGREPLAY_SKIP_SINGLE_ACTION;
+    for (const LogExtra& x : kLogExtras) known |= x.flag;
+    if (cfg->flags & ~known) return fail(RMJ_ERR_ARG, "rmj_logreplay_create: unknown flag");
     uint32_t ch, w, rs;
     float dummy;
     RmjObsBatch b{};
@@ -2456,35 +2462,24 @@ int rmj_logreplay_create(rmj_handle h, rmj_logset_handle set, const RmjLogReplay
         delete r;
         return fail(RMJ_ERR_HIP, "rmj_logreplay_create: no device memory for a pool of " + std::to_string(off >> 20) + " MiB (capacity x row bytes: choose a smaller capacity)");
     }
-    if ((cfg->flags & RMJ_LOGREPLAY_HIDDEN) && hipMalloc(&r->d_hid, (size_t)cap * HID_SLOT_BYTES) != hipSuccess) {
+    for (int i = 0; i < LX_COUNT; i++) {
+        const LogExtra& x = kLogExtras[i];
+        if (!(cfg->flags & x.flag) || hipMalloc(&r->d_extra[i], (size_t)cap * x.slot_bytes) == hipSuccess) continue;
         (void)hipGetLastError();
         hipFree(r->mem);
+        for (uint8_t* q : r->d_extra) if (q) hipFree(q);
         delete r;
-        return fail(RMJ_ERR_HIP, "rmj_logreplay_create: no device memory for the hidden records (capacity x 152 bytes: choose a smaller capacity)");
-    }
-    if ((cfg->flags & RMJ_LOGREPLAY_DANGER) && hipMalloc(&r->d_dng, (size_t)cap * DNG_SLOT_BYTES) != hipSuccess) {
-        (void)hipGetLastError();
-        hipFree(r->mem);
-        if (r->d_hid) hipFree(r->d_hid);
-        delete r;
-        return fail(RMJ_ERR_HIP, "rmj_logreplay_create: no device memory for the danger records (capacity x 224 bytes: choose a smaller capacity)");
-    }
-    if ((cfg->flags & RMJ_LOGREPLAY_DTABLE) && hipMalloc(&r->d_dtb, (size_t)cap * DT_SLOT_BYTES) != hipSuccess) {
-        (void)hipGetLastError();
-        hipFree(r->mem);
-        if (r->d_hid) hipFree(r->d_hid);
-        if (r->d_dng) hipFree(r->d_dng);
-        delete r;
-        return fail(RMJ_ERR_HIP, "rmj_logreplay_create: no device memory for the discard efficiency records (capacity x 112 bytes: choose a smaller capacity)");
+        return fail(RMJ_ERR_HIP, std::string("rmj_logreplay_create: no device memory for the ") + x.noun + " records (capacity x " + std::to_string(x.slot_bytes) +
+                                     " bytes: choose a smaller capacity)");
     }
     uint8_t* m = (uint8_t*)r->mem;
     L.bind(m);
     h->logreplay.push_back(r);
     // everything behind the feature rows starts as zeros (the views show defined values in slots that were never filled)
-    if (hipMemsetAsync(m + o_packed, 0, off - o_packed, h->stream) != hipSuccess ||
-        (r->d_hid && hipMemsetAsync(r->d_hid, 0, (size_t)cap * HID_SLOT_BYTES, h->stream) != hipSuccess) ||
-        (r->d_dng && hipMemsetAsync(r->d_dng, 0, (size_t)cap * DNG_SLOT_BYTES, h->stream) != hipSuccess) ||
-        (r->d_dtb && hipMemsetAsync(r->d_dtb, 0, (size_t)cap * DT_SLOT_BYTES, h->stream) != hipSuccess) || hipStreamSynchronize(h->stream) != hipSuccess ||
+    hipError_t zeroed = hipMemsetAsync(m + o_packed, 0, off - o_packed, h->stream);
+    for (int i = 0; i < LX_COUNT; i++)
+        if (zeroed == hipSuccess && r->d_extra[i]) zeroed = hipMemsetAsync(r->d_extra[i], 0, (size_t)cap * kLogExtras[i].slot_bytes, h->stream);
+    if (zeroed != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
         upload_chain(r->chain, M, R.slot_first, R.slot_logs) != hipSuccess ||
         hipMemcpy(r->d_powers, pw.data(), (size_t)r->n_powers * 8, hipMemcpyHostToDevice) != hipSuccess || (rc = logreplay_clear_impl(r))) {
         rmj_logreplay_destroy(r);
@@ -2501,9 +2496,7 @@ int rmj_logreplay_destroy(rmj_logreplay_handle r) {
     for (size_t i = 0; i < h->logreplay.size(); i++)
         if (h->logreplay[i] == r) { h->logreplay.erase(h->logreplay.begin() + i); break; }
     hipFree(r->mem);
-    if (r->d_hid) hipFree(r->d_hid);
-    if (r->d_dng) hipFree(r->d_dng);
-    if (r->d_dtb) hipFree(r->d_dtb);
+    for (uint8_t* q : r->d_extra) if (q) hipFree(q);
     delete r;
     return RMJ_OK;
 }
@@ -2536,9 +2529,8 @@ int rmj_logreplay_run_device(rmj_logreplay_handle r, uint32_t n_steps, uint32_t*
         else if (feat == RMJ_FEATURES_DISCARD_SHANTEN) RMJ_LAUNCH_RECORD(false, RMJ_FEATURES_DISCARD_SHANTEN);
         else RMJ_LAUNCH_RECORD(false, RMJ_FEATURES_BASE);
 #undef RMJ_LAUNCH_RECORD
-        if (r->d_hid) hipLaunchKernelGGL(k_log_hidden, dim3(n * 4), dim3(64), 0, h->stream, h->d, R, r->d_hid);   // the state is still the one the rows were encoded from
-        if (r->d_dng) hipLaunchKernelGGL(k_log_danger, dim3(n * 4), dim3(64), 0, h->stream, h->d, R, r->d_dng);
-        if (r->d_dtb) dt_launch_log(h->stream, h->d, R, r->d_dtb);
+        for (int x = 0; x < LX_COUNT; x++)   // the state is still the one the rows were encoded from
+            if (r->d_extra[x]) kLogExtras[x].launch(h->stream, h->d, R, r->d_extra[x]);
         launch_log_apply(h, n, R.ev, R.apply_at);
     }
     r->chain.step += todo;
@@ -2572,46 +2564,26 @@ int rmj_logreplay_emit_device(rmj_logreplay_handle r, const RmjLogBatch* out) {
     return RMJ_OK;
 }
 int rmj_logreplay_emit_hidden_device(rmj_logreplay_handle r, const RmjLogHiddenBatch* out) {
-    if (!r || !out) return fail(RMJ_ERR_ARG, "null argument");
-    if (!r->d_hid) return fail(RMJ_ERR_ARG, "rmj_logreplay_emit_hidden_device: the builder was made without RMJ_LOGREPLAY_HIDDEN");
-    if (out->rows && (!out->d_opp_hand || !out->d_opp_shanten || !out->d_opp_waits || !out->d_opp_flags || !out->d_event)) return fail(RMJ_ERR_ARG, "null argument");
-    rmj_env* h = r->env;
-    HIPCHK(hipSetDevice(h->cfg.device));
-    const uint32_t cap = r->R.capacity;
-    LogHiddenOut O{RmjHiddenOut{out->d_opp_hand, out->d_opp_shanten, out->d_opp_waits, out->d_opp_flags}, out->d_event, out->rows};
-    hipLaunchKernelGGL(k_log_emit_scan, dim3((cap + PPO_SCAN_BLOCK - 1) / PPO_SCAN_BLOCK), dim3(PPO_SCAN_BLOCK), 0, h->stream, r->R);
-    hipLaunchKernelGGL(k_log_emit_hidden, ppo_wave_grid(cap), dim3(256), 0, h->stream, r->R, (const uint8_t*)r->d_hid, O);
-    HIPCHK(hipGetLastError());
-    return RMJ_OK;
+    const bool no_array = r && out && out->rows && (!out->d_opp_hand || !out->d_opp_shanten || !out->d_opp_waits || !out->d_opp_flags || !out->d_event);
+    return logreplay_emit_extra(r, LX_HIDDEN, __func__, out, no_array, [&](hipStream_t st, const uint8_t* hid) {
+        LogHiddenOut O{RmjHiddenOut{out->d_opp_hand, out->d_opp_shanten, out->d_opp_waits, out->d_opp_flags}, out->d_event, out->rows};
+        hipLaunchKernelGGL(k_log_emit_hidden, ppo_wave_grid(r->R.capacity), dim3(256), 0, st, r->R, hid, O);
+    });
 }
 int rmj_logreplay_emit_danger_device(rmj_logreplay_handle r, const RmjLogDangerBatch* out) {
-    if (!r || !out) return fail(RMJ_ERR_ARG, "null argument");
-    if (!r->d_dng) return fail(RMJ_ERR_ARG, "rmj_logreplay_emit_danger_device: the builder was made without RMJ_LOGREPLAY_DANGER");
-    if (out->rows && !out->d_danger) return fail(RMJ_ERR_ARG, "null argument");
-    rmj_env* h = r->env;
-    HIPCHK(hipSetDevice(h->cfg.device));
-    const uint32_t cap = r->R.capacity;
-    hipLaunchKernelGGL(k_log_emit_scan, dim3((cap + PPO_SCAN_BLOCK - 1) / PPO_SCAN_BLOCK), dim3(PPO_SCAN_BLOCK), 0, h->stream, r->R);
-    hipLaunchKernelGGL(k_log_emit_danger, ppo_wave_grid(cap), dim3(256), 0, h->stream, r->R, (const uint8_t*)r->d_dng, out->d_danger, out->rows);
-    HIPCHK(hipGetLastError());
-    return RMJ_OK;
+    return logreplay_emit_extra(r, LX_DANGER, __func__, out, r && out && out->rows && !out->d_danger, [&](hipStream_t st, const uint8_t* dng) {
+        hipLaunchKernelGGL(k_log_emit_danger, ppo_wave_grid(r->R.capacity), dim3(256), 0, st, r->R, dng, out->d_danger, out->rows);
+    });
 }
 int rmj_logreplay_emit_dtable_device(rmj_logreplay_handle r, const RmjLogDtableBatch* out) {
-    if (!r || !out) return fail(RMJ_ERR_ARG, "null argument");
-    if (!r->d_dtb) return fail(RMJ_ERR_ARG, "rmj_logreplay_emit_dtable_device: the builder was made without RMJ_LOGREPLAY_DTABLE");
-    if (out->rows && (!out->d_shanten || !out->d_accept || !out->d_ukeire)) return fail(RMJ_ERR_ARG, "null argument");
-    rmj_env* h = r->env;
-    HIPCHK(hipSetDevice(h->cfg.device));
-    const uint32_t cap = r->R.capacity;
-    LogDtableOut O{out->d_shanten, out->d_accept, out->d_ukeire, out->rows};
-    hipLaunchKernelGGL(k_log_emit_scan, dim3((cap + PPO_SCAN_BLOCK - 1) / PPO_SCAN_BLOCK), dim3(PPO_SCAN_BLOCK), 0, h->stream, r->R);
-    dt_launch_log_emit(h->stream, r->R, (const uint8_t*)r->d_dtb, O);
-    HIPCHK(hipGetLastError());
-    return RMJ_OK;
+    const bool no_array = r && out && out->rows && (!out->d_shanten || !out->d_accept || !out->d_ukeire);
+    return logreplay_emit_extra(r, LX_DTABLE, __func__, out, no_array, [&](hipStream_t st, const uint8_t* dtb) {
+        dt_launch_log_emit(st, r->R, dtb, LogDtableOut{out->d_shanten, out->d_accept, out->d_ukeire, out->rows});
+    });
 }
 int rmj_logreplay_hidden_views(rmj_logreplay_handle r, RmjLogHiddenViews* out) {
     if (!r || !out) return fail(RMJ_ERR_ARG, "null argument");
-    *out = RmjLogHiddenViews{r->R.capacity, HID_SLOT_BYTES, r->d_hid};
+    *out = RmjLogHiddenViews{r->R.capacity, (uint32_t)kLogExtras[LX_HIDDEN].slot_bytes, r->d_extra[LX_HIDDEN]};
     return RMJ_OK;
 }
 int rmj_logreplay_views(rmj_logreplay_handle r, RmjLogReplayViews* out) {
@@ -3142,6 +3114,12 @@ static void dt_launch_rows(hipStream_t st, const Env& E, const int32_t* d_index,
 }
 static void dt_launch_hands(const ShantenTables& T, const uint8_t* counts, const uint8_t* visible, uint32_t n, int sanma, const RmjDiscardTableOut& O) {
     hipLaunchKernelGGL(k_dtable_hands<0>, dim3((n + 3) / 4), dim3(256), 0, 0, T, counts, visible, n, sanma, O);
+}
+static void hid_launch_log(hipStream_t st, const Env& E, const LogRun& R, uint8_t* hid) {
+    hipLaunchKernelGGL(k_log_hidden, dim3(R.n * 4), dim3(64), 0, st, E, R, hid);
+}
+static void dng_launch_log(hipStream_t st, const Env& E, const LogRun& R, uint8_t* dng) {
+    hipLaunchKernelGGL(k_log_danger, dim3(R.n * 4), dim3(64), 0, st, E, R, dng);
 }
 static void dt_launch_log(hipStream_t st, const Env& E, const LogRun& R, uint8_t* dtb) {
     hipLaunchKernelGGL(k_log_dtable<0>, dim3(R.n * 4), dim3(64), 0, st, E, R, dtb);

@@ -26,6 +26,7 @@ sample is not emitted; a log in which a decision matches no legal action is drop
 replay raises in MCDataset."""
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import functools
 
@@ -74,6 +75,26 @@ def parse_logs_device(text, ranges=None, num_players=4, masked_ok=False, device=
         return s.tensors()
     finally:
         s.close()
+
+
+# The extra columns a builder can keep beside the plain ones, in the order the library records them: the setting that asks for them, its
+# RMJ_LOGREPLAY_* flag, the row target whose fields they are (abi.ROW_TARGETS) - under `prefix` + the field's name, without the fields
+# in `skip` (the pool does not keep them) - columns of their own, the batch struct (the columns in this order, then rows and a reserved
+# word) with its emit entry, and why a log set with masked tiles is refused.
+_Extra = collections.namedtuple("_Extra", "setting flag target prefix skip more batch emit masked")
+_EXTRAS = (
+    _Extra("hidden", abi.LOGREPLAY_HIDDEN, "hidden", "", (), (abi.RowField("event", "int32", (), 0),), abi.LogHiddenBatch, "rmj_logreplay_emit_hidden_device",
+           "the masked seats' tiles are unknown, so are their hands, shanten and waits"),
+    _Extra("danger", abi.LOGREPLAY_DANGER, "danger", "", (), (), abi.LogDangerBatch, "rmj_logreplay_emit_danger_device",
+           "the masked seats' tiles are unknown, so is what they would win"),
+    _Extra("efficiency", abi.LOGREPLAY_DTABLE, "discard_table", "dt_", ("mask",), (), abi.LogDtableBatch, "rmj_logreplay_emit_dtable_device",
+           "the set does not tell which seats' tiles are masked, and a masked deciding seat has no hand to tabulate"),
+)
+
+
+def _extra_columns(x):
+    """[(sample key, abi.RowField)] of an extra, in the order of its batch struct"""
+    return [(x.prefix + f.name, f) for f in abi.ROW_TARGETS[x.target].fields if f.name not in x.skip] + [(f.name, f) for f in x.more]
 
 
 class LogSampleBuilder:
@@ -178,13 +199,10 @@ class LogSampleBuilder:
         self.logset, self._owned = logset, owned
         try:
             assert self.n_players == logset.num_players, "the log set was made for another number of players"
-            if self.hidden and getattr(logset, "masked_ok", False):
-                raise ValueError("hidden=True over a log set made with masked_ok=True: the masked seats' tiles are unknown, so are their hands, shanten and waits")
-            if self.danger and getattr(logset, "masked_ok", False):
-                raise ValueError("danger=True over a log set made with masked_ok=True: the masked seats' tiles are unknown, so is what they would win")
-            if self.efficiency and getattr(logset, "masked_ok", False):
-                raise ValueError("efficiency=True over a log set made with masked_ok=True: the set does not tell which seats' tiles are masked, and a "
-                                 "masked deciding seat has no hand to tabulate")
+            self._extras = [x for x in _EXTRAS if getattr(self, x.setting)]
+            for x in self._extras:
+                if getattr(logset, "masked_ok", False):
+                    raise ValueError(f"{x.setting}=True over a log set made with masked_ok=True: {x.masked}")
             for k in ("logs", "M", "device", "kyoku_offsets", "n_kyokus", "log_ids", "dropped", "lengths"):
                 setattr(self, k, getattr(logset, k))
             self.host_seconds = dict(logset.host_seconds)
@@ -199,8 +217,7 @@ class LogSampleBuilder:
                 vecenv._chk(L.rmj_set_stream(self.env.h, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream), 0))
             self._powers = gamma_powers(self.gamma, logset.longest_log + 1)
             flags = (abi.LOGREPLAY_INCLUDE_PASS if self.include_pass else 0) | (abi.LOGREPLAY_SKIP_SINGLE_ACTION if self.skip_single_action else 0) | \
-                (abi.LOGREPLAY_HIDDEN if self.hidden else 0) | (abi.LOGREPLAY_DANGER if self.danger else 0) | \
-                (abi.LOGREPLAY_DTABLE if self.efficiency else 0)
+                sum(x.flag for x in self._extras)
             cfg = abi.LogReplayConfig(self._feat, self.capacity, flags, len(self._powers), self.gamma, self._powers.ctypes.data)
             h = C.c_void_p()
             vecenv._chk(L.rmj_logreplay_create(self.env.h, logset.handle, C.byref(cfg), C.byref(h)))
@@ -328,14 +345,9 @@ class LogSampleBuilder:
         self._finalized, self._emitted = False, None
 
     def _empty(self, k):
-        t, d = self.torch, self.device
-        hid = {"opp_hand": t.empty((k, 3, 34), dtype=t.uint8, device=d), "opp_shanten": t.empty((k, 3), dtype=t.int8, device=d),
-               "opp_waits": t.empty((k, 3), dtype=t.int64, device=d), "opp_flags": t.empty((k, 3), dtype=t.uint8, device=d),
-               "event": t.empty((k,), dtype=t.int32, device=d)} if self.hidden else {}
-        dng = {"danger": t.empty((k, 3, abi.DANGER_KINDS), dtype=t.int32, device=d)} if self.danger else {}
-        eff = {"dt_shanten": t.empty((k, abi.DTAB_COLS), dtype=t.int8, device=d), "dt_accept": t.empty((k, abi.DTAB_COLS), dtype=t.uint8, device=d),
-               "dt_ukeire": t.empty((k, abi.DTAB_COLS), dtype=t.uint8, device=d)} if self.efficiency else {}
-        return {**self._empty_plain(k), **hid, **dng, **eff}
+        t = self.torch
+        extra = {key: t.empty((k,) + f.shape, dtype=abi.torch_dtype(t, f.dtype), device=self.device) for x in self._extras for key, f in _extra_columns(x)}
+        return {**self._empty_plain(k), **extra}
 
     def _empty_plain(self, k):
         t, d = self.torch, self.device
@@ -367,16 +379,9 @@ class LogSampleBuilder:
                          out["t"].data_ptr(), cnt.data_ptr(), rows, 0)
         self._pre()
         vecenv._chk(self.L.rmj_logreplay_emit_device(self.h, C.byref(b)))
-        if self.hidden:
-            hb = abi.LogHiddenBatch(out["opp_hand"].data_ptr(), out["opp_shanten"].data_ptr(), out["opp_waits"].data_ptr(), out["opp_flags"].data_ptr(),
-                                    out["event"].data_ptr(), rows, 0)
-            vecenv._chk(self.L.rmj_logreplay_emit_hidden_device(self.h, C.byref(hb)))
-        if self.danger:
-            db = abi.LogDangerBatch(out["danger"].data_ptr(), rows, 0)
-            vecenv._chk(self.L.rmj_logreplay_emit_danger_device(self.h, C.byref(db)))
-        if self.efficiency:
-            eb = abi.LogDtableBatch(out["dt_shanten"].data_ptr(), out["dt_accept"].data_ptr(), out["dt_ukeire"].data_ptr(), rows, 0)
-            vecenv._chk(self.L.rmj_logreplay_emit_dtable_device(self.h, C.byref(eb)))
+        for x in self._extras:
+            xb = x.batch(*(out[key].data_ptr() for key, _ in _extra_columns(x)), rows, 0)
+            vecenv._chk(getattr(self.L, x.emit)(self.h, C.byref(xb)))
         self._sync()
         k = int(cnt[0])
         self._emitted = {name: v[:k] for name, v in out.items()}

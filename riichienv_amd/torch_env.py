@@ -156,47 +156,46 @@ class TorchVecEnv:
         self.sync()
         return self._compact_result(sync_count)
 
+    def _row_index(self, index):
+        """(index as int32 [k] on the device, k)"""
+        idx = index.to(device=self.device, dtype=self.torch.int32).contiguous().reshape(-1)
+        return idx, int(idx.shape[0])
+
+    def _row_call(self, fn, idx, k, count, *args):
+        """a `_device` entry over the rows idx [k] up to the device count tensor `count` (or None).  Stream handling as in copy_games: the
+        caller's tensors were made on torch's stream, and the kernels have read idx before torch's allocator may hand it out again."""
+        if not self.shared:
+            self.torch.cuda.current_stream(self.device).synchronize()
+        vecenv._chk(fn(self.env.h, C.c_void_p(idx.data_ptr()), k, None if count is None else C.c_void_p(count.data_ptr()), *args))
+        self.sync()
+
+    def _row_target(self, target, fn, index, count, out, *flags):
+        """the tensors of abi.ROW_TARGETS[target] for the rows `index`, allocated unless `out` brings them, filled by the entry `fn`"""
+        t, fields = self.torch, abi.ROW_TARGETS[target].fields
+        idx, k = self._row_index(index)
+        if out is None:
+            out = {f.name: t.full((k,) + f.shape, f.fill, dtype=abi.torch_dtype(t, f.dtype), device=self.device) for f in fields}
+        assert all(out[f.name].shape[0] >= k and out[f.name].is_contiguous() for f in fields), "out is too small for the index"
+        if k:
+            self._row_call(fn, idx, k, count, *flags, C.byref(abi.row_struct(target, out)))
+        return out
+
     def hidden_compact(self, index, count=None, out=None):
         """What the observation hides from the rows of a compact batch: index [k] int32 = game * 4 + seat as obs_compact returns it (or
         any other seats, acting or not) -> {"opp_hand" uint8 [k, 3, 34], "opp_shanten" int8 [k, 3], "opp_waits" int64 [k, 3] (bit t =
         tile type t), "opp_flags" uint8 [k, 3] (abi.HIDDEN_* bits, n_melds << 4)} on the device, for the opponents (seat + 1 + r) mod NP
         (rmj_hidden_targets_device; 3P: the third opponent is zeros).  count: the device count tensor of obs_compact(sync_count=False) -
         rows at or behind it are left as they were; out: the dict of an earlier call to write into (no allocation)."""
-        t = self.torch
-        idx = index.to(device=self.device, dtype=t.int32).contiguous().reshape(-1)
-        k = int(idx.shape[0])
-        if out is None:
-            out = {"opp_hand": t.zeros((k, 3, 34), dtype=t.uint8, device=self.device), "opp_shanten": t.zeros((k, 3), dtype=t.int8, device=self.device),
-                   "opp_waits": t.zeros((k, 3), dtype=t.int64, device=self.device), "opp_flags": t.zeros((k, 3), dtype=t.uint8, device=self.device)}
-        assert all(out[f].shape[0] >= k and out[f].is_contiguous() for f in ("opp_hand", "opp_shanten", "opp_waits", "opp_flags")), "out is too small for the index"
-        if k:
-            if not self.shared:
-                t.cuda.current_stream(self.device).synchronize()   # the buffers were made on torch's stream
-            b = abi.HiddenOut(*(out[f].data_ptr() for f in ("opp_hand", "opp_shanten", "opp_waits", "opp_flags")))
-            vecenv._chk(self.env.L.rmj_hidden_targets_device(self.env.h, C.c_void_p(idx.data_ptr()), k, None if count is None else C.c_void_p(count.data_ptr()),
-                                                             C.byref(b)))
-            self.sync()
-        return out
+        return self._row_target("hidden", self.env.L.rmj_hidden_targets_device, index, count, out)
 
     def danger_compact(self, index, count=None, ura=False, out=None):
         """Deal-in danger of the rows of a compact batch: index [k] int32 = game * 4 + seat -> int32 [k, 3, 37] on the device, the points
         opponent (seat + 1 + r) mod NP would win by ron if the seat discarded a tile of kind c now (kinds 0..33 tile types, 34..36 copy 0
         of the fives; rmj_danger_targets_device).  count: the device count tensor of obs_compact(sync_count=False) - rows at or behind it
         are left as they were; ura: opponents in riichi count their ura indicators; out: the tensor of an earlier call to write into."""
-        t = self.torch
-        idx = index.to(device=self.device, dtype=t.int32).contiguous().reshape(-1)
-        k = int(idx.shape[0])
-        if out is None:
-            out = t.zeros((k, 3, abi.DANGER_KINDS), dtype=t.int32, device=self.device)
-        assert out.shape[0] >= k and out.is_contiguous() and out.dtype == t.int32, "out is too small for the index"
-        if k:
-            if not self.shared:
-                t.cuda.current_stream(self.device).synchronize()   # the buffers were made on torch's stream
-            b = abi.DangerOut(out.data_ptr())
-            vecenv._chk(self.env.L.rmj_danger_targets_device(self.env.h, C.c_void_p(idx.data_ptr()), k, None if count is None else C.c_void_p(count.data_ptr()),
-                                                             abi.DANGER_URA if ura else 0, C.byref(b)))
-            self.sync()
-        return out
+        assert out is None or out.dtype == self.torch.int32, "out is too small for the index"
+        return self._row_target("danger", self.env.L.rmj_danger_targets_device, index, count, None if out is None else {"danger": out},
+                                abi.DANGER_URA if ura else 0)["danger"]
 
     def discard_table_compact(self, index, count=None, out=None):
         """Discard efficiency table of the rows of a compact batch: index [k] int32 = game * 4 + seat -> {"shanten" int8 [k, 35], "accept"
@@ -204,24 +203,7 @@ class TorchVecEnv:
         after discarding type t (abi.DTAB_NONE: no such discard), the types that then lower it and their live tiles; column 34: the hand
         itself (rmj_discard_table_device).  count: the device count tensor of obs_compact(sync_count=False) - rows at or behind it are
         left as they were; out: the dict of an earlier call to write into (no allocation)."""
-        t = self.torch
-        idx = index.to(device=self.device, dtype=t.int32).contiguous().reshape(-1)
-        k = int(idx.shape[0])
-        names = ("shanten", "accept", "ukeire", "mask")
-        if out is None:
-            out = {"shanten": t.full((k, abi.DTAB_COLS), abi.DTAB_NONE, dtype=t.int8, device=self.device),
-                   "accept": t.zeros((k, abi.DTAB_COLS), dtype=t.uint8, device=self.device),
-                   "ukeire": t.zeros((k, abi.DTAB_COLS), dtype=t.uint8, device=self.device),
-                   "mask": t.zeros((k, abi.DTAB_COLS), dtype=t.int64, device=self.device)}
-        assert all(out[f].shape[0] >= k and out[f].is_contiguous() for f in names), "out is too small for the index"
-        if k:
-            if not self.shared:
-                t.cuda.current_stream(self.device).synchronize()   # the buffers were made on torch's stream
-            b = abi.DiscardTableOut(*(out[f].data_ptr() for f in names))
-            vecenv._chk(self.env.L.rmj_discard_table_device(self.env.h, C.c_void_p(idx.data_ptr()), k, None if count is None else C.c_void_p(count.data_ptr()),
-                                                            0, C.byref(b)))
-            self.sync()
-        return out
+        return self._row_target("discard_table", self.env.L.rmj_discard_table_device, index, count, out, 0)
 
     def scores(self):
         vecenv._chk(self.env.L.rmj_scores_device(self.env.h, C.c_void_p(self._scores.data_ptr()), None))
@@ -444,23 +426,18 @@ class TorchVecEnv:
         exchanges (header: the nearest tenpai hand by fewest exchanges from a uniform deal, not a posterior); abi.DET_SWAPPED marks the
         worlds in which a tile was exchanged.  Stream handling as in copy_games."""
         t = self.torch
-        idx = index.to(device=self.device, dtype=t.int32).contiguous().reshape(-1)
-        k = int(idx.shape[0])
+        idx, k = self._row_index(index)
         st = t.zeros((k,), dtype=t.uint8, device=self.device)
         if not k:
             return st
         h = None
         if hold is not None:
             h = (hold.to(device=self.device, dtype=t.uint8) if t.is_tensor(hold) else t.as_tensor(hold, dtype=t.uint8, device=self.device)).expand(k).contiguous()
-        if not self.shared:
-            t.cuda.current_stream(self.device).synchronize()
         d = abi.Determinize(int(seed) & 0xFFFFFFFFFFFFFFFF, None if h is None else h.data_ptr(), st.data_ptr())
-        cnt = None if count is None else C.c_void_p(count.data_ptr())
         if riichi_tenpai:
-            vecenv._chk(self.env.L.rmj_determinize_ex_device(self.env.h, C.c_void_p(idx.data_ptr()), k, cnt, C.byref(d), abi.DETF_RIICHI_TENPAI))
+            self._row_call(self.env.L.rmj_determinize_ex_device, idx, k, count, C.byref(d), abi.DETF_RIICHI_TENPAI)
         else:
-            vecenv._chk(self.env.L.rmj_determinize_device(self.env.h, C.c_void_p(idx.data_ptr()), k, cnt, C.byref(d)))
-        self.sync()   # (own stream: the kernels have read idx / hold before torch's allocator may hand them out again)
+            self._row_call(self.env.L.rmj_determinize_device, idx, k, count, C.byref(d))
         return st
 
     def sample_ids(self, logits=None, seed=0, index=None, count=None):

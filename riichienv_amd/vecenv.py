@@ -359,32 +359,28 @@ class VecRiichiEnv:
             cap_r, cap_e = max(cap_r, nr.value + nr.value // 8), max(cap_e, ne.value + ne.value // 8)
             self._lc_buf = None
 
+    def _row_target(self, target, fn, index, *flags):
+        """the arrays of abi.ROW_TARGETS[target] for the seats `index`, filled by the host entry `fn` (an empty index calls nothing)"""
+        idx = np.ascontiguousarray(index, dtype=np.int32).reshape(-1)
+        k = int(idx.size)
+        out = abi.row_arrays(target, k)
+        if k:
+            _chk(fn(self.h, idx.ctypes.data, k, *flags, C.byref(abi.row_struct(target, out))))
+        return out
+
     def hidden_targets(self, index):
         """What the observation hides from the seats `index` [k] = game * 4 + seat (any seat, acting or not - e.g. legal_compact()'s
         index): {"opp_hand" uint8 [k, 3, 34], "opp_shanten" int8 [k, 3], "opp_waits" int64 [k, 3] (bit t = tile type t), "opp_flags"
         uint8 [k, 3] (abi.HIDDEN_* bits, n_melds << 4)} of the opponents (seat + 1 + r) mod NP, r = 0, 1, 2 - rmj_hidden_targets (header).
         In 3P the third opponent is absent: zeros."""
-        idx = np.ascontiguousarray(index, dtype=np.int32).reshape(-1)
-        k = int(idx.size)
-        out = {"opp_hand": np.zeros((k, 3, 34), np.uint8), "opp_shanten": np.zeros((k, 3), np.int8), "opp_waits": np.zeros((k, 3), np.int64),
-               "opp_flags": np.zeros((k, 3), np.uint8)}
-        if k:
-            b = abi.HiddenOut(*(out[f].ctypes.data for f in ("opp_hand", "opp_shanten", "opp_waits", "opp_flags")))
-            _chk(self.L.rmj_hidden_targets(self.h, idx.ctypes.data, k, C.byref(b)))
-        return out
+        return self._row_target("hidden", self.L.rmj_hidden_targets, index)
 
     def danger_targets(self, index, ura=False):
         """Deal-in danger of the seats `index` [k] = game * 4 + seat: int32 [k, 3, 37], the points opponent (seat + 1 + r) mod NP would win
         by ron if the seat discarded a tile of kind c now - kinds 0..33 the tile types (non-red), 34..36 copy 0 of the 5m / 5p / 5s (the
         red ones where the mode has them); 0 for a tile that is no wait, a furiten opponent, a hand without yaku - rmj_danger_targets
         (header: the definition and where it leaves the settlement).  ura: opponents in riichi count their ura indicators off the wall."""
-        idx = np.ascontiguousarray(index, dtype=np.int32).reshape(-1)
-        k = int(idx.size)
-        out = np.zeros((k, 3, abi.DANGER_KINDS), np.int32)
-        if k:
-            b = abi.DangerOut(out.ctypes.data)
-            _chk(self.L.rmj_danger_targets(self.h, idx.ctypes.data, k, abi.DANGER_URA if ura else 0, C.byref(b)))
-        return out
+        return self._row_target("danger", self.L.rmj_danger_targets, index, abi.DANGER_URA if ura else 0)["danger"]
 
     def discard_table(self, index):
         """Discard efficiency table of the seats `index` [k] = game * 4 + seat (any seat, acting or not): {"shanten" int8 [k, 35],
@@ -392,13 +388,7 @@ class VecRiichiEnv:
         type t from a 3n+2 hand (abi.DTAB_NONE: not held, or no discard to make), the tile types that then lower it (count and bits)
         and how many of them are not visible; column 34: the hand itself, with the maxima rmj_effective_tiles / rmj_best_ukeire give
         - rmj_discard_table (header: the definition).  An index out of range, or seat 3 in 3P, gives an absent row."""
-        idx = np.ascontiguousarray(index, dtype=np.int32).reshape(-1)
-        k = int(idx.size)
-        out = _dtable_arrays(k)
-        if k:
-            b = abi.DiscardTableOut(*(out[f].ctypes.data for f in ("shanten", "accept", "ukeire", "mask")))
-            _chk(self.L.rmj_discard_table(self.h, idx.ctypes.data, k, 0, C.byref(b)))
-        return out
+        return self._row_target("discard_table", self.L.rmj_discard_table, index, 0)
 
     def determinize(self, index, seed, hold=None, riichi_tenpai=False):
         """Re-deal, in place, what the seats `index` [k] = game * 4 + seat (one row per game; the seat must be to act) cannot see: their
@@ -827,11 +817,6 @@ def best_ukeire(counts, visible, sanma=False, device=0):
     return out
 
 
-def _dtable_arrays(k):
-    return {"shanten": np.full((k, abi.DTAB_COLS), abi.DTAB_NONE, np.int8), "accept": np.zeros((k, abi.DTAB_COLS), np.uint8),
-            "ukeire": np.zeros((k, abi.DTAB_COLS), np.uint8), "mask": np.zeros((k, abi.DTAB_COLS), np.uint64)}
-
-
 def discard_table(counts, visible=None, sanma=False, device=0):
     """Discard efficiency table of [n][34] hand type histograms against [n][34] visible histograms (None: nothing visible): the dict of
     VecRiichiEnv.discard_table - rmj_discard_table_hands.  A hand of more than 14 tiles, or a count above 4, gives an absent row."""
@@ -841,9 +826,9 @@ def discard_table(counts, visible=None, sanma=False, device=0):
     if visible is not None:
         visible = np.ascontiguousarray(visible, dtype=np.uint8).reshape(-1, 34)
         assert counts.shape == visible.shape
-    out = _dtable_arrays(n)
-    b = abi.DiscardTableOut(*(out[f].ctypes.data for f in ("shanten", "accept", "ukeire", "mask")))
-    _chk(L.rmj_discard_table_hands(device, counts.ctypes.data, None if visible is None else visible.ctypes.data, n, int(sanma), C.byref(b)))
+    out = abi.row_arrays("discard_table", n)
+    _chk(L.rmj_discard_table_hands(device, counts.ctypes.data, None if visible is None else visible.ctypes.data, n, int(sanma),
+                                   C.byref(abi.row_struct("discard_table", out))))
     return out
 
 

@@ -65,9 +65,9 @@ def live_windows(n_games, windows, calls, with_hidden):
     rows = int(index.shape[0])
     L, h, ix = env.env.L, env.env.h, C.c_void_p(index.data_ptr())
     dng = env.danger_compact(index)
-    db = abi.DangerOut(dng.data_ptr())
+    db = abi.row_struct("danger", {"danger": dng})
     hid = env.hidden_compact(index)
-    hb = abi.HiddenOut(*(hid[f].data_ptr() for f in ("opp_hand", "opp_shanten", "opp_waits", "opp_flags")))
+    hb = abi.row_struct("hidden", hid)
     calls_of = {"danger": lambda: L.rmj_danger_targets_device(h, ix, rows, None, 0, C.byref(db)),
                 "danger_ura": lambda: L.rmj_danger_targets_device(h, ix, rows, None, abi.DANGER_URA, C.byref(db))}
     if with_hidden:

@@ -136,7 +136,7 @@ def main():
     # ---- the same call by the host clock (launch overhead of two kernels included), on games that stay determinized
     det_host = host_windows(lambda: work.determinize(index, seed=5))
     out = src.hidden_compact(index)
-    b = abi.HiddenOut(*(out[f].data_ptr() for f in ("opp_hand", "opp_shanten", "opp_waits", "opp_flags")))
+    b = abi.row_struct("hidden", out)
     hidden = host_windows(lambda: vecenv._chk(L.rmj_hidden_targets_device(src.env.h, C.c_void_p(index.data_ptr()), rows, None, C.byref(b))))
     games = (index >> 2).to(torch.int32).contiguous()
     copy = host_windows(lambda: work.copy_games(games, src, games))

@@ -37,10 +37,11 @@ def live_windows(n_games, windows, calls):
     rows = int(index.shape[0])
     L, h, ix = env.env.L, env.env.h, C.c_void_p(index.data_ptr())
     tab = env.discard_table_compact(index)
-    tb = abi.DiscardTableOut(*(tab[f].data_ptr() for f in ("shanten", "accept", "ukeire", "mask")))
-    tb3 = abi.DiscardTableOut(tab["shanten"].data_ptr(), tab["accept"].data_ptr(), tab["ukeire"].data_ptr(), None)
+    tb = abi.row_struct("discard_table", tab)
+    tb3 = abi.row_struct("discard_table", tab)
+    tb3.mask = None
     hid = env.hidden_compact(index)
-    hb = abi.HiddenOut(*(hid[f].data_ptr() for f in ("opp_hand", "opp_shanten", "opp_waits", "opp_flags")))
+    hb = abi.row_struct("hidden", hid)
     enc_args = env._compact_batch_args()
 
     def encode():

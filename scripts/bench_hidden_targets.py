@@ -111,7 +111,7 @@ def live_entry(n_games, windows, calls):
     _, index = env.obs_compact()
     rows = int(index.shape[0])
     out = env.hidden_compact(index)
-    b = abi.HiddenOut(*(out[f].data_ptr() for f in ("opp_hand", "opp_shanten", "opp_waits", "opp_flags")))
+    b = abi.row_struct("hidden", out)
     L, secs = env.env.L, []
     for w in range(windows + 1):
         torch.cuda.synchronize()
