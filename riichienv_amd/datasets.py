@@ -28,12 +28,12 @@ from __future__ import annotations
 
 import collections
 import ctypes as C
-import functools
 
 import numpy as np
 
 from . import abi, vecenv
 from .logset import _DECISION_TYPES, LogSet, check_on_error, kyoku_tables, pack_logs  # noqa: F401  (re-exported: callers know them by this module)
+from .streams import StreamLink
 
 
 def assign_slots(lengths, n_slots):
@@ -213,19 +213,20 @@ class LogSampleBuilder:
             torch, L = self.torch, self.L
             bits = abi.RULE_MJSOUL if self.rule == "mjsoul" else abi.RULE_TENHOU
             self.env = vecenv.VecRiichiEnv(self.n_slots, game_mode=self.game_mode, seed=0, rule_bits=bits, device=logset.device_index, skip_mjai_logging=True)
+            self.link = StreamLink(torch, self.device, self.env, owner=self)   # stream order and pointer passing of every call: streams.py
             if self.shared:
-                vecenv._chk(L.rmj_set_stream(self.env.h, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream), 0))
+                self.link.bind()
             self._powers = gamma_powers(self.gamma, logset.longest_log + 1)
             flags = (abi.LOGREPLAY_INCLUDE_PASS if self.include_pass else 0) | (abi.LOGREPLAY_SKIP_SINGLE_ACTION if self.skip_single_action else 0) | \
                 sum(x.flag for x in self._extras)
             cfg = abi.LogReplayConfig(self._feat, self.capacity, flags, len(self._powers), self.gamma, self._powers.ctypes.data)
             h = C.c_void_p()
-            vecenv._chk(L.rmj_logreplay_create(self.env.h, logset.handle, C.byref(cfg), C.byref(h)))
+            self.link.call(L.rmj_logreplay_create, self.env.h, logset.handle, C.byref(cfg), C.byref(h))
             self.h = h
             v = abi.LogReplayViews()
             vecenv._chk(L.rmj_logreplay_views(self.h, C.byref(v)))
             self.steps = int(v.steps)
-            wrap = functools.partial(abi.device_tensor, torch, self, self.device)
+            wrap = self.link.wrap
             cap, fl, K = self.capacity, self.channels * self.width, max(self.n_kyokus, 1)
             rows = wrap(v.features, (cap, v.row_stride), "<f4")
             self.pool = {"features": rows[:, :fl].unflatten(-1, (self.channels, self.width)), "mask": wrap(v.mask, (cap, self.A), "|u1"),
@@ -238,20 +239,10 @@ class LogSampleBuilder:
                 hv = abi.LogHiddenViews()
                 vecenv._chk(L.rmj_logreplay_hidden_views(self.h, C.byref(hv)))
                 self.pool["hidden"] = wrap(hv.records, (cap, hv.record_bytes), "|u1")
-            self._sync()
         except Exception:
             self.close()
             raise
         return self
-
-    # ---- stream order (a builder that keeps the library's own stream synchronises around every call)
-    def _pre(self):
-        if not self.shared:
-            self.torch.cuda.current_stream(self.device).synchronize()
-
-    def _sync(self):
-        if not self.shared and self.env is not None:
-            self.env.sync()
 
     def close(self):
         """rmj_logreplay_destroy, the environment, and the log set if the builder made it"""
@@ -276,9 +267,7 @@ class LogSampleBuilder:
         if self.M == 0:
             return 0
         left = C.c_uint32()
-        self._pre()
-        vecenv._chk(self.L.rmj_logreplay_run_device(self.h, int(n_steps), C.byref(left)))
-        self._sync()
+        self.link.call(self.L.rmj_logreplay_run_device, self.h, int(n_steps), C.byref(left))
         self._finalized, self._emitted = False, None
         return int(left.value)
 
@@ -320,9 +309,7 @@ class LogSampleBuilder:
             es = self.logset.device_scores()[1] if self.n_kyokus else t.zeros((1, 4), dtype=t.int32, device=self.device)
         else:
             es = t.as_tensor(self.end_scores if len(self.end_scores) else np.zeros((1, 4), np.int32), dtype=t.int32).to(self.device).contiguous()
-        self._pre()
-        vecenv._chk(self.L.rmj_logreplay_finalize_device(self.h, C.c_void_p(rw.data_ptr()), C.c_void_p(es.data_ptr())))
-        self._sync()
+        self.link.call(self.L.rmj_logreplay_finalize_device, self.h, rw, es)
         if self.shared:
             rw.record_stream(t.cuda.current_stream(self.device))
             es.record_stream(t.cuda.current_stream(self.device))
@@ -340,8 +327,7 @@ class LogSampleBuilder:
     def clear(self):
         """empty the pool and rewind every slot to its first log (rmj_logreplay_clear)"""
         if self.M:
-            vecenv._chk(self.L.rmj_logreplay_clear(self.h))
-            self._sync()
+            self.link.call(self.L.rmj_logreplay_clear, self.h)
         self._finalized, self._emitted = False, None
 
     def _empty(self, k):
@@ -377,12 +363,10 @@ class LogSampleBuilder:
         b = abi.LogBatch(out["features"].data_ptr(), out["mask"].data_ptr(), out["action"].data_ptr(), out["packed"].data_ptr(), out["return"].data_ptr(),
                          out["return64"].data_ptr(), out["rank"].data_ptr(), out["log"].data_ptr(), out["kyoku"].data_ptr(), out["seat"].data_ptr(),
                          out["t"].data_ptr(), cnt.data_ptr(), rows, 0)
-        self._pre()
-        vecenv._chk(self.L.rmj_logreplay_emit_device(self.h, C.byref(b)))
+        self.link.call(self.L.rmj_logreplay_emit_device, self.h, C.byref(b))
         for x in self._extras:
             xb = x.batch(*(out[key].data_ptr() for key, _ in _extra_columns(x)), rows, 0)
-            vecenv._chk(getattr(self.L, x.emit)(self.h, C.byref(xb)))
-        self._sync()
+            self.link.call(getattr(self.L, x.emit), self.h, C.byref(xb))
         k = int(cnt[0])
         self._emitted = {name: v[:k] for name, v in out.items()}
         return self._emitted

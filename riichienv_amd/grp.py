@@ -14,13 +14,13 @@ the element-wise ops around the two calls.
     DeviceRewardPredictor               the [K, 4] reward table LogSampleBuilder.finalize takes, and PPOCollector's reward_fn"""
 from __future__ import annotations
 
-import ctypes as C
 import time
 
 import numpy as np
 
 from . import vecenv
 from .logset import LogSet, check_on_error
+from .streams import stream_ptr
 
 _BUILDER_ONLY = ("features", "n_slots", "capacity", "gamma", "include_pass", "skip_single_action", "rule", "share_stream", "kyoku_scale")
 _KEEP = {"raise": "raise", "drop": "keep"}    # GrpDataset's "drop" keeps the log in the set: its kyokus get rank 255 and tensors() filters them
@@ -35,10 +35,6 @@ def _players(game_mode, kw, on_error="raise"):
     return 3 if vecenv._mode_id(game_mode) >= 3 else 4
 
 
-def _stream_ptr(torch, device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 def live_rows(init, delta, meta, num_players, out=None):
     """rmj_grp_rows_device: init, delta, meta int32 [rows, 4] device tensors -> x [rows, n, 4n + 4] float32 (end = init + delta; meta =
     (chang, ju, ben, liqibang) as TorchVecEnv.round_track gives it).  Asynchronous on torch's current stream."""
@@ -50,8 +46,8 @@ def live_rows(init, delta, meta, num_players, out=None):
     assert init.is_cuda and tuple(init.shape) == tuple(delta.shape) == tuple(meta.shape) == (rows, 4)
     x = torch.empty((rows, n, 4 * n + 4), dtype=torch.float32, device=init.device) if out is None else out
     assert x.is_contiguous() and tuple(x.shape) == (rows, n, 4 * n + 4) and x.dtype == torch.float32
-    vecenv._chk(vecenv.load_lib().rmj_grp_rows_device(init.device.index, C.c_void_p(init.data_ptr()), C.c_void_p(delta.data_ptr()), C.c_void_p(meta.data_ptr()),
-                                                      rows, n, C.c_void_p(x.data_ptr()), _stream_ptr(torch, init.device)))
+    vecenv._chk(vecenv.load_lib().rmj_grp_rows_device(init.device.index, init.data_ptr(), delta.data_ptr(), meta.data_ptr(), rows, n, x.data_ptr(),
+                                                      stream_ptr(torch, init.device)))
     return x
 
 

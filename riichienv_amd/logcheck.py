@@ -21,6 +21,7 @@ import ctypes as C
 import numpy as np
 
 from . import abi, mjai, vecenv
+from .streams import StreamLink
 
 NAMES = list(abi.LOGCHECK_NAMES)
 CODES = {name: i for i, name in enumerate(NAMES)}
@@ -100,29 +101,23 @@ def validate(logset, game_mode=None, rule=None, n_slots=None, share_stream=True)
         raise vecenv.RmjError("the log set is closed")
     bits = abi.RULE_MJSOUL if rule == "mjsoul" else abi.RULE_TENHOU
     env = vecenv.VecRiichiEnv(n, game_mode=mode, seed=0, rule_bits=bits, device=logset.device_index, skip_mjai_logging=True)
-    h = C.c_void_p()
+    link, h = StreamLink(torch, dev, env), C.c_void_p()
     try:
         stream = torch.cuda.current_stream(dev)
         if share_stream:
-            vecenv._chk(L.rmj_set_stream(env.h, C.c_void_p(stream.cuda_stream), 0))
-        else:
-            stream.synchronize()
-        vecenv._chk(L.rmj_logcheck_create(env.h, logset.handle, n, 0, C.byref(h)))
+            link.bind(stream)
+        link.call(L.rmj_logcheck_create, env.h, logset.handle, n, 0, C.byref(h))
         tables = []
         if not logset.owns_tables and logset.n_kyokus:
             from .logset import kyoku_own_end_scores
 
             own = kyoku_own_end_scores(logset.logs, logset.num_players)
             tables = [torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32), device=dev) for a in (logset.start_scores, own)]
-            if not share_stream:
-                torch.cuda.current_stream(dev).synchronize()
-            vecenv._chk(L.rmj_logcheck_set_scores(h, *[C.c_void_p(a.data_ptr()) for a in tables]))
-        vecenv._chk(L.rmj_logcheck_run_device(h, 0, None))
+            link.call(L.rmj_logcheck_set_scores, h, *tables)
+        link.call(L.rmj_logcheck_run_device, h, 0, None)
         v = abi.LogCheckViews()
         vecenv._chk(L.rmj_logcheck_views(h, C.byref(v)))
-        if not share_stream:
-            env.sync()
-        wrap = lambda ptr, shape, ts: abi.device_tensor(torch, None, dev, ptr, shape, ts)   # noqa: E731
+        wrap = link.wrap
         # clones, in stream order behind the replay (the library's memory goes away with the checker below)
         report = LogReport(torch, dev, wrap(v.code, (M,), "|u1").clone(), wrap(v.event, (M,), "<i4").to(torch.int64), wrap(v.kyoku, (M,), "<i4").to(torch.int64),
                            wrap(v.seat, (M,), "|u1").clone(), wrap(v.detail, (M,), "<i4").to(torch.int64),

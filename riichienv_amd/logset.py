@@ -14,6 +14,7 @@ import time
 import numpy as np
 
 from . import abi, vecenv
+from .streams import stream_ptr
 
 _DECISION_TYPES = ("dahai", "chi", "pon", "daiminkan", "kan", "ankan", "kakan", "reach", "hora", "kita", "ryukyoku")
 
@@ -343,14 +344,18 @@ class LogSet:
                "kyoku_offsets": torch.as_tensor(np.asarray(self.kyoku_offsets, dtype=np.int64), device=dev)}
         if not K or not self.handle:
             return out
-        # the set's own tables (NULL), or the host tables uploaded
+        self._grp_call(n, abi.GrpOut(out["meta"].data_ptr(), out["x"].data_ptr(), out["rank"].data_ptr(), out["log_of"].data_ptr()))
+        return out
+
+    def _grp_call(self, n, o):
+        """rmj_logset_grp_device into the abi.GrpOut `o` on torch's current stream, over the set's own tables (NULL) or the host tables
+        uploaded for the call"""
+        torch, dev = self.torch, self.device
         tables = [] if self.owns_tables else [torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32), device=dev) for a in (self.start_scores, self.end_scores)]
-        o = abi.GrpOut(out["meta"].data_ptr(), out["x"].data_ptr(), out["rank"].data_ptr(), out["log_of"].data_ptr())
         stream = torch.cuda.current_stream(dev)
-        vecenv._chk(self.L.rmj_logset_grp_device(self.handle, n, *([C.c_void_p(a.data_ptr()) for a in tables] or [None, None]), C.byref(o), C.c_void_p(stream.cuda_stream)))
+        vecenv._chk(self.L.rmj_logset_grp_device(self.handle, n, *([a.data_ptr() for a in tables] or [None, None]), C.byref(o), stream.cuda_stream))
         for a in tables:
             a.record_stream(stream)
-        return out
 
     def final_ranks(self, num_players=None):
         """uint8 [K, n] device tensor: grp_rows()["rank"] alone - every seat's place (0 = first) in its log's final scores, repeated in
@@ -363,12 +368,7 @@ class LogSet:
             return rank
         if not self.handle:
             raise vecenv.RmjError("the log set is closed")
-        tables = [] if self.owns_tables else [torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32), device=dev) for a in (self.start_scores, self.end_scores)]
-        o = abi.GrpOut(None, None, rank.data_ptr(), None)
-        stream = torch.cuda.current_stream(dev)
-        vecenv._chk(self.L.rmj_logset_grp_device(self.handle, n, *([C.c_void_p(a.data_ptr()) for a in tables] or [None, None]), C.byref(o), C.c_void_p(stream.cuda_stream)))
-        for a in tables:
-            a.record_stream(stream)
+        self._grp_call(n, abi.GrpOut(None, None, rank.data_ptr(), None))
         return rank
 
     def log_of(self):
@@ -394,7 +394,7 @@ class LogSet:
             return out
         if self.owns_tables:
             out["valid"] = self._wrap(self._views().status, (self.M,), "|u1")[log_of] == abi.LOGTEXT_OK
-        vecenv._chk(self.L.rmj_logset_playstats_device(self.handle, n, C.c_void_p(out["rows"].data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        vecenv._chk(self.L.rmj_logset_playstats_device(self.handle, n, out["rows"].data_ptr(), stream_ptr(torch, dev)))
         return out
 
     def validate(self, game_mode=None, rule=None, n_slots=None, share_stream=True):

@@ -34,7 +34,7 @@ class PPOCollector:
     def __init__(self, tenv, capacity, gamma=0.99, gae_lambda=0.95, hero=None, boundary="round", seed=0):
         if boundary not in ("round", "kyoku_idx"):
             raise ValueError("boundary is 'round' or 'kyoku_idx'")
-        self.tenv, self.t = tenv, tenv.torch
+        self.tenv, self.t, self.link = tenv, tenv.torch, tenv.link
         t, L = self.t, tenv.env.L
         self.L = L
         self.n, self.capacity, self.boundary = tenv.n, int(capacity), boundary
@@ -51,10 +51,10 @@ class PPOCollector:
         self._no_hero = t.full((self.n,), NO_HERO, dtype=t.uint8, device=dev)
         cfg = abi.PpoConfig(tenv._feat, self.capacity, self.gamma, self.gae_lambda)
         self.h = C.c_void_p()
-        vecenv._chk(L.rmj_ppo_create(tenv.env.h, C.byref(cfg), C.byref(self.h)))
+        self.link.call(L.rmj_ppo_create, tenv.env.h, C.byref(cfg), C.byref(self.h))
         v = abi.PpoViews()
         vecenv._chk(L.rmj_ppo_views(self.h, C.byref(v)))
-        wrap = functools.partial(abi.device_tensor, t, self, dev)
+        wrap = functools.partial(self.link.wrap, owner=self)
         cap, fl = self.capacity, tenv.channels * tenv.width
         self._pool_rows = wrap(v.features, (cap, v.row_stride), "<f4")
         self.pool = {"features": self._pool_rows[:, :fl].unflatten(-1, (tenv.channels, tenv.width)), "mask": wrap(v.mask, (cap, self.A), "|u1"),
@@ -67,15 +67,6 @@ class PPOCollector:
         self._full = None
         self._seed = int(seed) * 1000003
         self._reset_boundary()
-        self._pre()
-
-    # ---- stream order (a TorchVecEnv that keeps the library's own stream synchronises around every call)
-    def _pre(self):
-        if not self.tenv.shared:
-            self.t.cuda.current_stream(self.tenv.device).synchronize()
-
-    def _post(self):
-        self.tenv.sync()
 
     def close(self):
         """rmj_ppo_destroy (the environment's close destroys its collectors too)"""
@@ -102,15 +93,12 @@ class PPOCollector:
         TorchVecEnv.sample_ids, every other acting seat takes the arg-max over its legal ids (ties to the lowest id); hero=None: every
         seat draws; a hero tensor of 255s: every seat takes the arg-max."""
         t = self.t
-        ptr, stride = None, 0
+        stride = 0
         if logits is not None:
             assert logits.dtype == t.float32 and logits.is_contiguous() and tuple(logits.shape[:2]) == (self.n, 4)
-            ptr, stride = C.c_void_p(logits.data_ptr()), int(logits.shape[2])
+            stride = int(logits.shape[2])
         hp = self.hero if isinstance(hero, str) else hero
-        self._pre()
-        vecenv._chk(self.L.rmj_select_ids_device(self.tenv.env.h, ptr, stride, int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                                None if hp is None else C.c_void_p(hp.data_ptr()), C.c_void_p(self._ids.data_ptr())))
-        self._post()
+        self.link.call(self.L.rmj_select_ids_device, self.tenv.env.h, logits, stride, int(seed) & 0xFFFFFFFFFFFFFFFF, hp, self._ids)
         return self._ids
 
     def _batch(self, layout):
@@ -126,23 +114,17 @@ class PPOCollector:
         assert logits.dtype == t.float32 and logits.is_contiguous() and values.dtype == t.float32 and values.is_contiguous()
         b = self._batch(layout)
         hp = self.hero if hero is None else hero
-        self._pre()
-        vecenv._chk(self.L.rmj_ppo_record_device(self.h, C.byref(b), C.c_void_p(hp.data_ptr()), C.c_void_p(ids.data_ptr()), C.c_void_p(logits.data_ptr()),
-                                                 int(logits.shape[-1]), C.c_void_p(values.data_ptr())))
-        self._post()
+        self.link.call(self.L.rmj_ppo_record_device, self.h, C.byref(b), hp, ids, logits, int(logits.shape[-1]), values)
 
     def close_segments(self, ended, reward):
         """rmj_ppo_close_device: ended [n] uint8 (non-zero: the hero's open trajectory of the game ends here), reward [n] float32"""
         t = self.t
         assert ended.dtype == t.uint8 and ended.is_contiguous() and reward.dtype == t.float32 and reward.is_contiguous()
-        self._pre()
-        vecenv._chk(self.L.rmj_ppo_close_device(self.h, C.c_void_p(ended.data_ptr()), C.c_void_p(reward.data_ptr())))
-        self._post()
+        self.link.call(self.L.rmj_ppo_close_device, self.h, ended, reward)
 
     def clear(self):
         """empty the pool and forget the open trajectories (rmj_ppo_clear); the boundary bookkeeping starts afresh"""
-        vecenv._chk(self.L.rmj_ppo_clear(self.h))
-        self._post()
+        self.link.call(self.L.rmj_ppo_clear, self.h)
         self._reset_boundary()
 
     def counts(self):
@@ -256,9 +238,7 @@ class PPOCollector:
         cnt = t.zeros((2,), dtype=t.int32, device=self.tenv.device)
         b = abi.PpoBatch(out["features"].data_ptr(), out["mask"].data_ptr(), out["action"].data_ptr(), out["log_prob"].data_ptr(),
                          out["advantage"].data_ptr(), out["return"].data_ptr(), cnt.data_ptr(), int(rows), 0)
-        self._pre()
-        vecenv._chk(self.L.rmj_ppo_emit_device(self.h, C.byref(b)))
-        self._post()
+        self.link.call(self.L.rmj_ppo_emit_device, self.h, C.byref(b))
         return cnt
 
     def stats(self):
@@ -282,7 +262,7 @@ class PPOCollector:
         by rank, or `rank_rewards`; done [n] bool - False where max_steps ended the loop first)."""
         t, e = self.t, self.tenv
         e.env.reset()
-        vecenv._chk(self.L.rmj_round_track_reset(e.env.h))
+        self.link.call(self.L.rmj_round_track_reset, e.env.h)
         self._obs = None
         seat0 = t.zeros((self.n,), dtype=t.int64, device=e.device)
         obs = e.obs_compact(sync_count=False)

@@ -9,11 +9,11 @@ torch is used for device memory and streams only; all game logic runs in the HIP
 from __future__ import annotations
 
 import ctypes as C
-import functools
 
 import numpy as np
 
 from . import abi, vecenv
+from .streams import StreamLink
 from .abi import _CudaArray  # noqa: F401  (imported from here by tests and scripts)
 
 
@@ -54,9 +54,10 @@ class TorchVecEnv:
         self.extended = features == "extended"
         self.channels = abi.FEATURE_CHANNELS[self._feat]
         self.width = 27 if self.sanma else 34
+        self.link = StreamLink(torch, self.device, self.env, owner=self)   # stream order and pointer passing of every call: streams.py
         v = abi.DeviceViews()
         vecenv._chk(L.rmj_device_views(self.env.h, C.byref(v)))
-        wrap = functools.partial(abi.device_tensor, torch, self, self.device)
+        wrap = self.link.wrap
         self.status_raw = wrap(v.status, (self.n,), "<u4") if hasattr(torch, "uint32") else wrap(v.status, (self.n,), "<i4")
         self.nlegal = wrap(v.nlegal, (self.n, 4), "|u1")
         self.mask = wrap(v.mask, (self.n, 4, abi.ACTION_SPACE_4P), "|u1")      # zero-copy, rewritten by every step
@@ -78,10 +79,18 @@ class TorchVecEnv:
         # row stride of the batch entries (rmj_encode_batch_device): the padded rows of the base set, else C x W (0: 215 x 27 is odd)
         self._batch_stride = self.row_stride if self.pad_rows else 0
         self._scores = torch.zeros((self.n, 4), dtype=torch.int32, device=self.device)
-        self.shared = bool(share_stream)
-        if self.shared:
-            vecenv._chk(L.rmj_set_stream(self.env.h, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream), 0))
+        if share_stream:
+            self.link.bind()
         self.env.reset()
+
+    shared = property(lambda self: self.link.shared)   # the library issues on torch's stream (share_stream, or after bind_stream)
+
+    def _batch(self, compact):
+        """the RmjObsBatch of the resident tensor, or of the compact buffers, by reference"""
+        if compact:
+            return C.byref(self.env.obs_batch(self._feat, self._cobs_buf.data_ptr(), True, self._cidx.data_ptr(), self._cap, self._ccnt.data_ptr(),
+                                              self._batch_stride))
+        return C.byref(self.env.obs_batch(self._feat, self._obs_buf.data_ptr(), row_stride=self._batch_stride))
 
     # ---- status helpers (views, no copies beyond the arithmetic)
     def _status(self):
@@ -105,11 +114,10 @@ class TorchVecEnv:
         if self.features == "discard_shanten":
             if not only_active:
                 raise ValueError("the discard_shanten feature set encodes the acting seats only: obs(only_active=True)")
-            self.env.encode_batch_device(self._feat, self._obs_buf.data_ptr(), row_stride=self._batch_stride)
+            self.link.call(L.rmj_encode_batch_device, self.env.h, self._batch(False))
         else:
             fn = L.rmj_encode_extended_device if self.extended else L.rmj_encode_device
-            vecenv._chk(fn(self.env.h, 2 if only_active else 0, C.c_void_p(self._obs_buf.data_ptr())))
-        self.sync()
+            self.link.call(fn, self.env.h, 2 if only_active else 0, self._obs_buf)
         return self._obs
 
     def _compact_buffers(self, capacity=None):
@@ -123,12 +131,6 @@ class TorchVecEnv:
             self._cidx = t.zeros((cap,), dtype=t.int32, device=self.device)
             self._ccnt = t.zeros((1,), dtype=t.int32, device=self.device)
             self._cap = cap
-            if not self.shared:
-                t.cuda.current_stream(self.device).synchronize()   # the buffers were zeroed on torch's stream
-
-    def _compact_batch_args(self):
-        return dict(compact=True, d_index_ptr=self._cidx.data_ptr(), capacity=self._cap, d_count_ptr=self._ccnt.data_ptr(),
-                    row_stride=self._batch_stride)
 
     def _compact_result(self, sync_count):
         """(obs [k, C, W], index [k]) after an encode into the compact buffers; the buffers grow (and the same state is encoded
@@ -139,8 +141,7 @@ class TorchVecEnv:
         if k > self._cap:                                          # more claimants than rows: grow once and encode again
             self._cobs = None
             self._compact_buffers(k + k // 8)
-            self.env.encode_batch_device(self._feat, self._cobs_buf.data_ptr(), **self._compact_batch_args())
-            self.sync()
+            self.link.call(self.env.L.rmj_encode_batch_device, self.env.h, self._batch(True))
         return self._cobs[:k], self._cidx[:k]
 
     def obs_compact(self, capacity=None, sync_count=True):
@@ -150,24 +151,15 @@ class TorchVecEnv:
         (no host round trip: rows behind the count hold old data).  capacity defaults to n + n // 2 rows and grows on demand."""
         self._compact_buffers(capacity)
         if self.features == "base":
-            self.env.encode_compact_device(self._cobs_buf.data_ptr(), self._cidx.data_ptr(), self._cap, self._ccnt.data_ptr())
+            self.link.call(self.env.L.rmj_encode_compact_device, self.env.h, self._cobs_buf, self._cidx, self._cap, self._ccnt)
         else:
-            self.env.encode_batch_device(self._feat, self._cobs_buf.data_ptr(), **self._compact_batch_args())
-        self.sync()
+            self.link.call(self.env.L.rmj_encode_batch_device, self.env.h, self._batch(True))
         return self._compact_result(sync_count)
 
     def _row_index(self, index):
         """(index as int32 [k] on the device, k)"""
         idx = index.to(device=self.device, dtype=self.torch.int32).contiguous().reshape(-1)
         return idx, int(idx.shape[0])
-
-    def _row_call(self, fn, idx, k, count, *args):
-        """a `_device` entry over the rows idx [k] up to the device count tensor `count` (or None).  Stream handling as in copy_games: the
-        caller's tensors were made on torch's stream, and the kernels have read idx before torch's allocator may hand it out again."""
-        if not self.shared:
-            self.torch.cuda.current_stream(self.device).synchronize()
-        vecenv._chk(fn(self.env.h, C.c_void_p(idx.data_ptr()), k, None if count is None else C.c_void_p(count.data_ptr()), *args))
-        self.sync()
 
     def _row_target(self, target, fn, index, count, out, *flags):
         """the tensors of abi.ROW_TARGETS[target] for the rows `index`, allocated unless `out` brings them, filled by the entry `fn`"""
@@ -177,7 +169,7 @@ class TorchVecEnv:
             out = {f.name: t.full((k,) + f.shape, f.fill, dtype=abi.torch_dtype(t, f.dtype), device=self.device) for f in fields}
         assert all(out[f.name].shape[0] >= k and out[f.name].is_contiguous() for f in fields), "out is too small for the index"
         if k:
-            self._row_call(fn, idx, k, count, *flags, C.byref(abi.row_struct(target, out)))
+            self.link.call(fn, self.env.h, idx, k, count, *flags, C.byref(abi.row_struct(target, out)))
         return out
 
     def hidden_compact(self, index, count=None, out=None):
@@ -206,8 +198,7 @@ class TorchVecEnv:
         return self._row_target("discard_table", self.env.L.rmj_discard_table_device, index, count, out, 0)
 
     def scores(self):
-        vecenv._chk(self.env.L.rmj_scores_device(self.env.h, C.c_void_p(self._scores.data_ptr()), None))
-        self.sync()
+        self.link.call(self.env.L.rmj_scores_device, self.env.h, self._scores, None)
         return self._scores
 
     def points(self, rule_name="basic"):
@@ -218,10 +209,7 @@ class TorchVecEnv:
             raise ValueError(f"Unknown preset rule{' for 3P' if self.sanma else ''}: {rule_name}")
         if not hasattr(self, "_points"):
             self._points = self.torch.zeros((self.n, 4), dtype=self.torch.float64, device=self.device)
-            if not self.shared:
-                self.torch.cuda.current_stream(self.device).synchronize()
-        vecenv._chk(self.env.L.rmj_points_device(self.env.h, rules[rule_name], C.c_void_p(self._points.data_ptr())))
-        self.sync()
+        self.link.call(self.env.L.rmj_points_device, self.env.h, rules[rule_name], self._points)
         return self._points
 
     def ranks(self):
@@ -235,13 +223,7 @@ class TorchVecEnv:
         return out
 
     def step(self, action_ids, auto_reset=True):
-        t = self.torch
-        ids = action_ids.to(device=self.device, dtype=t.int32).contiguous()
-        assert ids.shape == (self.n, 4)
-        if not self.shared:
-            t.cuda.current_stream(self.device).synchronize()  # the ids were produced on torch's stream
-        vecenv._chk(self.env.L.rmj_step_ids_device(self.env.h, C.c_void_p(ids.data_ptr()), int(auto_reset)))
-        self.sync()
+        self.link.call(self.env.L.rmj_step_ids_device, self.env.h, self._ids_in(action_ids), int(auto_reset))
 
     # ---- rewards (rmj_round_track_device): what riichienv-ml's PPO worker derives between steps on the host
     def round_track(self):
@@ -253,12 +235,7 @@ class TorchVecEnv:
         if not hasattr(self, "_rt"):
             self._rt = (t.zeros((self.n,), dtype=t.uint8, device=self.device), t.zeros((self.n, 4), dtype=t.int32, device=self.device),
                         t.zeros((self.n, 4), dtype=t.int32, device=self.device), t.zeros((self.n,), dtype=t.uint8, device=self.device))
-            if not self.shared:
-                t.cuda.current_stream(self.device).synchronize()
-        e, d, m, k = self._rt
-        vecenv._chk(self.env.L.rmj_round_track_device(self.env.h, C.c_void_p(e.data_ptr()), C.c_void_p(d.data_ptr()), C.c_void_p(m.data_ptr()),
-                                                     C.c_void_p(k.data_ptr())))
-        self.sync()
+        self.link.call(self.env.L.rmj_round_track_device, self.env.h, *self._rt)
         return self._rt
 
     RANK_REWARDS_4P = (10.0, 4.0, -4.0, -10.0)   # trainers/_ppo_worker.py:283-291
@@ -296,23 +273,17 @@ class TorchVecEnv:
         t = self.torch
         ids = action_ids.to(device=self.device, dtype=t.int32).contiguous()
         assert ids.shape == (self.n, 4)
-        if not self.shared:
-            t.cuda.current_stream(self.device).synchronize()   # the ids were produced on torch's stream
         return ids
 
     def _logits_in(self, logits):
+        """(logits or None, their row stride), with the resident ids tensor made"""
         t = self.torch
         if not hasattr(self, "_ids"):
             self._ids = t.full((self.n, 4), -1, dtype=t.int32, device=self.device)
-            if not self.shared:
-                t.cuda.current_stream(self.device).synchronize()
-        ptr, stride = None, 0
-        if logits is not None:
-            assert logits.dtype == t.float32 and logits.is_contiguous() and tuple(logits.shape[:2]) == (self.n, 4)
-            ptr, stride = logits.data_ptr(), int(logits.shape[2])
-            if not self.shared:
-                t.cuda.current_stream(self.device).synchronize()
-        return ptr, stride
+        if logits is None:
+            return None, 0
+        assert logits.dtype == t.float32 and logits.is_contiguous() and tuple(logits.shape[:2]) == (self.n, 4)
+        return logits, int(logits.shape[2])
 
     def step_obs(self, action_ids, auto_reset=True):
         """step(action_ids) and obs(only_active=True): returns the resident tensor [n, 4, C, W] whose rows of the seats that are to act
@@ -320,27 +291,21 @@ class TorchVecEnv:
         on one stream (rmj_step_ids_encode_batch_device)."""
         ids = self._ids_in(action_ids)
         if self.features == "base":
-            vecenv._chk(self.env.L.rmj_step_ids_encode_device(self.env.h, C.c_void_p(ids.data_ptr()), int(auto_reset),
-                                                              C.c_void_p(self._obs_buf.data_ptr())))
+            self.link.call(self.env.L.rmj_step_ids_encode_device, self.env.h, ids, int(auto_reset), self._obs_buf)
         else:
-            self.env.step_ids_encode_batch_device(ids.data_ptr(), self._feat, self._obs_buf.data_ptr(), row_stride=self._batch_stride,
-                                                  auto_reset=auto_reset)
-        self.sync()
+            self.link.call(self.env.L.rmj_step_ids_encode_batch_device, self.env.h, ids, int(auto_reset), self._batch(False))
         return self._obs
 
     def step_sample_obs(self, logits=None, seed=0, auto_reset=True):
         """sample_ids(logits, seed) + step_obs(ids): returns (ids [n, 4] int32 - the ids the two calls would have produced -, the resident
         tensor [n, 4, C, W] with the rows of the seats that act next).  logits: float32 [n, 4, A'] (A' >= 82; 60 in 3P) on this device, or
         None for the uniform policy.  Base set: ONE launch (rmj_step_sample_encode_device); the others: rmj_step_sample_encode_batch_device."""
-        ptr, stride = self._logits_in(logits)
+        logits, stride = self._logits_in(logits)
         seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         if self.features == "base":
-            vecenv._chk(self.env.L.rmj_step_sample_encode_device(self.env.h, None if ptr is None else C.c_void_p(ptr), stride, seed, int(auto_reset),
-                                                                 C.c_void_p(self._ids.data_ptr()), C.c_void_p(self._obs_buf.data_ptr())))
+            self.link.call(self.env.L.rmj_step_sample_encode_device, self.env.h, logits, stride, seed, int(auto_reset), self._ids, self._obs_buf)
         else:
-            self.env.step_sample_encode_batch_device(ptr, stride, seed, self._ids.data_ptr(), self._feat, self._obs_buf.data_ptr(),
-                                                     row_stride=self._batch_stride, auto_reset=auto_reset)
-        self.sync()
+            self.link.call(self.env.L.rmj_step_sample_encode_batch_device, self.env.h, logits, stride, seed, int(auto_reset), self._ids, self._batch(False))
         return self._ids, self._obs
 
     def step_obs_compact(self, action_ids, sync_count=True, auto_reset=True):
@@ -349,19 +314,16 @@ class TorchVecEnv:
         device count (obs_compact's form: no host round trip, capturable in a HIP graph once the buffers exist)."""
         ids = self._ids_in(action_ids)
         self._compact_buffers()
-        self.env.step_ids_encode_batch_device(ids.data_ptr(), self._feat, self._cobs_buf.data_ptr(), auto_reset=auto_reset,
-                                              **self._compact_batch_args())
-        self.sync()
+        self.link.call(self.env.L.rmj_step_ids_encode_batch_device, self.env.h, ids, int(auto_reset), self._batch(True))
         return self._compact_result(sync_count)
 
     def step_sample_obs_compact(self, logits=None, seed=0, sync_count=True, auto_reset=True):
         """sample_ids(logits, seed) + step + obs_compact() (rmj_step_sample_encode_batch_device): returns (ids [n, 4], obs [k, C, W],
         index [k]), or (ids, obs, index, count) - the full-capacity buffers and the device count - with sync_count=False."""
-        ptr, stride = self._logits_in(logits)
+        logits, stride = self._logits_in(logits)
         self._compact_buffers()
-        self.env.step_sample_encode_batch_device(ptr, stride, seed, self._ids.data_ptr(), self._feat, self._cobs_buf.data_ptr(),
-                                                 auto_reset=auto_reset, **self._compact_batch_args())
-        self.sync()
+        self.link.call(self.env.L.rmj_step_sample_encode_batch_device, self.env.h, logits, stride, int(seed) & 0xFFFFFFFFFFFFFFFF, int(auto_reset),
+                       self._ids, self._batch(True))
         return (self._ids,) + tuple(self._compact_result(sync_count))
 
     def bind_stream(self, stream=None):
@@ -372,16 +334,12 @@ class TorchVecEnv:
         calls only launch kernels on the bound stream (no allocation, no host synchronisation), and the sampler's noise is keyed by
         every game's own step count, so each replay of the graph draws fresh actions.  `step_obs_compact(sync_count=False)` captures too
         (its buffers must exist before the capture); `obs_compact(sync_count=True)` reads a count on the host and cannot be captured."""
-        t = self.torch
-        s = stream if stream is not None else t.cuda.current_stream(self.device)
-        vecenv._chk(self.env.L.rmj_set_stream(self.env.h, C.c_void_p(s.cuda_stream), 0))
-        self.shared = True
-        return s
+        return self.link.bind(stream)
 
     def sync(self):
         """own stream: wait for the library's work; shared stream: nothing to do, torch's stream orders it"""
         if not self.shared:
-            vecenv._chk(self.env.L.rmj_sync(self.env.h))
+            self.env.sync()
 
     def drain_text(self, seat=-1, cursor=None, peek=False, timings=None):
         """The MJAI text every game logged since the last drain, formatted on the GPU and left there (rmj_drain_text with
@@ -394,7 +352,7 @@ class TorchVecEnv:
         v = self.env._text_call(seat, cursor, peek, True)
         if timings is not None:
             timings[:] = [v.ms[0], v.ms[1], v.ms[2]]
-        wrap = functools.partial(abi.device_tensor, self.torch, self, self.device)
+        wrap = self.link.wrap
         text = wrap(v.text, (int(v.bytes),), "|u1") if v.bytes else self.torch.zeros(0, dtype=self.torch.uint8, device=self.device)
         return text, wrap(v.text_offsets, (v.n_games + 1,), "<i8")
 
@@ -407,13 +365,9 @@ class TorchVecEnv:
         a = dst_idx.to(device=self.device, dtype=t.int32).contiguous()
         b = src_idx.to(device=self.device, dtype=t.int32).contiguous()
         assert a.numel() == b.numel()
-        if not self.shared:
-            t.cuda.current_stream(self.device).synchronize()
-        L = self.env.L
-        vecenv._chk(L.rmj_copy_games_device(self.env.h, C.c_void_p(a.data_ptr()), src_env.env.h, C.c_void_p(b.data_ptr()), int(a.numel())))
         # own stream: torch's caching allocator orders the reuse of `a` / `b` by torch's stream, not by the library's, so the
-        # kernel must have read them before they are released (shared stream: torch's stream orders it)
-        self.sync()
+        # kernel must have read them before they are released - link.call returns after it (shared stream: torch's stream orders it)
+        self.link.call(self.env.L.rmj_copy_games_device, self.env.h, a, src_env.env.h, b, int(a.numel()))
 
     def determinize(self, index, seed, count=None, hold=None, riichi_tenpai=False):
         """rmj_determinize_device: re-deal, in place, what the rows index [k] int32 = game * 4 + seat (as obs_compact returns them; the
@@ -435,9 +389,9 @@ class TorchVecEnv:
             h = (hold.to(device=self.device, dtype=t.uint8) if t.is_tensor(hold) else t.as_tensor(hold, dtype=t.uint8, device=self.device)).expand(k).contiguous()
         d = abi.Determinize(int(seed) & 0xFFFFFFFFFFFFFFFF, None if h is None else h.data_ptr(), st.data_ptr())
         if riichi_tenpai:
-            self._row_call(self.env.L.rmj_determinize_ex_device, idx, k, count, C.byref(d), abi.DETF_RIICHI_TENPAI)
+            self.link.call(self.env.L.rmj_determinize_ex_device, self.env.h, idx, k, count, C.byref(d), abi.DETF_RIICHI_TENPAI)
         else:
-            self._row_call(self.env.L.rmj_determinize_device, idx, k, count, C.byref(d))
+            self.link.call(self.env.L.rmj_determinize_device, self.env.h, idx, k, count, C.byref(d))
         return st
 
     def sample_ids(self, logits=None, seed=0, index=None, count=None):
@@ -452,8 +406,6 @@ class TorchVecEnv:
         Non-finite logits: a -inf or NaN logit is never drawn while a finite one is legal; if every legal id is -inf or NaN the
         lowest legal id is drawn; among several +inf logits the lowest of them wins (step_sample_obs draws the same way)."""
         t = self.torch
-        if not hasattr(self, "_ids"):
-            self._ids = t.full((self.n, 4), -1, dtype=t.int32, device=self.device)
         if logits is not None and index is not None:
             a = int(logits.shape[-1])
             if getattr(self, "_full_logits", None) is None or self._full_logits.shape[-1] != a:
@@ -467,15 +419,8 @@ class TorchVecEnv:
                 raise ValueError("sample_ids: more index rows than (game, seat) pairs - pass the device count of obs_compact(sync_count=False)")
             self._full_logits[dst] = logits.reshape(-1, a)[:k].to(t.float32)
             logits = self._full_logits[: self.n * 4].view(self.n, 4, a)
-        ptr, stride = None, 0
-        if logits is not None:
-            assert logits.dtype == t.float32 and logits.is_contiguous() and tuple(logits.shape[:2]) == (self.n, 4)
-            ptr, stride = C.c_void_p(logits.data_ptr()), int(logits.shape[2])
-            if not self.shared:
-                t.cuda.current_stream(self.device).synchronize()   # the logits were produced on torch's stream
-        vecenv._chk(self.env.L.rmj_sample_ids_device(self.env.h, ptr, stride, int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                                     C.c_void_p(self._ids.data_ptr())))
-        self.sync()
+        logits, stride = self._logits_in(logits)
+        self.link.call(self.env.L.rmj_sample_ids_device, self.env.h, logits, stride, int(seed) & 0xFFFFFFFFFFFFFFFF, self._ids)
         return self._ids
 
     def sample_random_ids(self, generator=None):
@@ -618,7 +563,7 @@ class GymVectorAdapter:
         self._seed = int(seed or 0) * 1000003
         e.env.reset()
         if hasattr(e, "_rt"):
-            vecenv._chk(e.env.L.rmj_round_track_reset(e.env.h))
+            e.link.call(e.env.L.rmj_round_track_reset, e.env.h)
         else:
             e.round_track()
         self._terminated = t.zeros((e.n,), dtype=t.bool, device=e.device)
@@ -630,7 +575,7 @@ class GymVectorAdapter:
         e, t = self.env, self.t
         if bool(self._terminated.any()):   # games that ended in the previous step restart now (their action is ignored)
             e.env.reset(select=self._terminated.to(t.uint8).cpu().numpy())
-            vecenv._chk(e.env.L.rmj_round_track_device(e.env.h, None, None, None, None))   # re-opens the restarted games silently
+            e.link.call(e.env.L.rmj_round_track_device, e.env.h, None, None, None, None)   # re-opens the restarted games silently
             lead = self._terminated
             self._advance(t.full((e.n,), -1, dtype=t.int64, device=e.device), t.zeros((e.n,), dtype=t.float32, device=e.device), ~lead)
         acts = actions.to(device=e.device, dtype=t.int64)

@@ -242,21 +242,19 @@ class VecRiichiEnv:
     def step_random_encode(self, policy_seed, n_steps, d_out_ptr, auto_reset=True, only_active=2):
         """n_steps x (step of every game + encode() of the acting seats into the device tensor at d_out_ptr): header
         rmj_step_random_encode (BASELINE configs[4])."""
-        _chk(self.L.rmj_step_random_encode(self.h, policy_seed, n_steps, int(auto_reset), int(only_active), C.c_void_p(d_out_ptr)))
+        _chk(self.L.rmj_step_random_encode(self.h, policy_seed, n_steps, int(auto_reset), int(only_active), d_out_ptr))
 
     def encode_compact_device(self, d_out_ptr, d_index_ptr, capacity, d_count_ptr):
         """Observation.encode() of the acting seats as one dense batch in (game, seat) order (header: rmj_encode_compact_device);
         all three pointers are device pointers, asynchronous on the handle's stream."""
-        _chk(self.L.rmj_encode_compact_device(self.h, C.c_void_p(d_out_ptr), C.c_void_p(d_index_ptr), capacity, C.c_void_p(d_count_ptr)))
+        _chk(self.L.rmj_encode_compact_device(self.h, d_out_ptr, d_index_ptr, capacity, d_count_ptr))
 
     def step_random_encode_compact(self, policy_seed, n_steps, d_out_ptr, d_index_ptr, capacity, d_count_ptr, auto_reset=True):
-        _chk(self.L.rmj_step_random_encode_compact(self.h, policy_seed, n_steps, int(auto_reset), C.c_void_p(d_out_ptr),
-                                                   C.c_void_p(d_index_ptr), capacity, C.c_void_p(d_count_ptr)))
+        _chk(self.L.rmj_step_random_encode_compact(self.h, policy_seed, n_steps, int(auto_reset), d_out_ptr, d_index_ptr, capacity, d_count_ptr))
 
     def bench_encode_compact(self, d_out_ptr, d_index_ptr, capacity, d_count_ptr, reps=20):
         ms = C.c_double()
-        _chk(self.L.rmj_bench_encode_compact(self.h, C.c_void_p(d_out_ptr), C.c_void_p(d_index_ptr), capacity, C.c_void_p(d_count_ptr),
-                                             reps, C.byref(ms)))
+        _chk(self.L.rmj_bench_encode_compact(self.h, d_out_ptr, d_index_ptr, capacity, d_count_ptr, reps, C.byref(ms)))
         return ms.value
 
     # ---- observation batches (header: rmj_encode_batch_device): one feature set, dense or compact
@@ -287,15 +285,15 @@ class VecRiichiEnv:
                                      row_stride=0, auto_reset=True):
         """rmj_step_ids_device + rmj_encode_batch_device (rmj_step_ids_encode_batch_device)"""
         b = self.obs_batch(features, d_out_ptr, compact, d_index_ptr, capacity, d_count_ptr, row_stride)
-        _chk(self.L.rmj_step_ids_encode_batch_device(self.h, C.c_void_p(d_ids_ptr), int(auto_reset), C.byref(b)))
+        _chk(self.L.rmj_step_ids_encode_batch_device(self.h, d_ids_ptr, int(auto_reset), C.byref(b)))
 
     def step_sample_encode_batch_device(self, d_logits_ptr, stride, seed, d_ids_ptr, features, d_out_ptr, compact=False, d_index_ptr=None,
                                         capacity=0, d_count_ptr=None, row_stride=0, auto_reset=True):
         """rmj_sample_ids_device + rmj_step_ids_device + rmj_encode_batch_device (rmj_step_sample_encode_batch_device); d_logits_ptr None =
         the uniform policy"""
         b = self.obs_batch(features, d_out_ptr, compact, d_index_ptr, capacity, d_count_ptr, row_stride)
-        _chk(self.L.rmj_step_sample_encode_batch_device(self.h, None if d_logits_ptr is None else C.c_void_p(d_logits_ptr), int(stride),
-                                                        int(seed) & 0xFFFFFFFFFFFFFFFF, int(auto_reset), C.c_void_p(d_ids_ptr), C.byref(b)))
+        _chk(self.L.rmj_step_sample_encode_batch_device(self.h, d_logits_ptr, int(stride), int(seed) & 0xFFFFFFFFFFFFFFFF, int(auto_reset), d_ids_ptr,
+                                                        C.byref(b)))
 
     def encode_batch(self, features="base", compact=True):
         """The acting seats' tensors of one feature set on the host (rmj_encode_batch): (obs float32 [k, C, W], index int32 [k] =
@@ -614,7 +612,7 @@ class VecRiichiEnv:
         """rmj_format_events_device: the text of records already on the device (d_events: device address of RmjEvent records, d_offsets:
         device address of [n_games + 1] u32 offsets).  Returns the RmjTextView (on_device=False: host pointers, readable with _host_text)."""
         v = abi.TextView()
-        _chk(self.L.rmj_format_events_device(self.h, C.c_void_p(int(d_events)), C.c_void_p(int(d_offsets)), int(n_games), int(seat),
+        _chk(self.L.rmj_format_events_device(self.h, int(d_events), int(d_offsets), int(n_games), int(seat),
                                              abi.TEXT_ON_DEVICE if on_device else 0, C.byref(v)))
         return v
 
@@ -712,7 +710,7 @@ class VecRiichiEnv:
     def time_rollout_encode(self, policy_seed, steps, d_out_ptr) -> abi.BenchResult:
         """HIP-event time of rmj_step_random_encode(seed, steps, auto_reset, only_active = 2, d_out) (header: rmj_time_rollout_encode)"""
         r = abi.BenchResult()
-        _chk(self.L.rmj_time_rollout_encode(self.h, policy_seed, steps, C.c_void_p(d_out_ptr), C.byref(r)))
+        _chk(self.L.rmj_time_rollout_encode(self.h, policy_seed, steps, d_out_ptr, C.byref(r)))
         return r
 
     def time_rollout_greedy(self, policy_seed, steps, call_rate_256=64) -> abi.BenchResult:
@@ -729,7 +727,7 @@ class VecRiichiEnv:
     def bench_encode(self, d_out_ptr, reps, extended=False, only_active=2) -> float:
         """Average ms of one encoder launch into the device buffer at `d_out_ptr` (header: rmj_bench_encode)."""
         ms = C.c_double()
-        _chk(self.L.rmj_bench_encode(self.h, int(extended), int(only_active), C.c_void_p(d_out_ptr), reps, C.byref(ms)))
+        _chk(self.L.rmj_bench_encode(self.h, int(extended), int(only_active), d_out_ptr, reps, C.byref(ms)))
         return ms.value
 
     def set_rollout_streams(self, k):

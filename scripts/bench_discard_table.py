@@ -42,16 +42,10 @@ def live_windows(n_games, windows, calls):
     tb3.mask = None
     hid = env.hidden_compact(index)
     hb = abi.row_struct("hidden", hid)
-    enc_args = env._compact_batch_args()
-
-    def encode():
-        env.env.encode_batch_device(env._feat, env._cobs_buf.data_ptr(), **enc_args)
-        return 0
-
     calls_of = {"dtable": lambda: L.rmj_discard_table_device(h, ix, rows, None, 0, C.byref(tb)),
                 "dtable_no_mask": lambda: L.rmj_discard_table_device(h, ix, rows, None, 0, C.byref(tb3)),
                 "hidden": lambda: L.rmj_hidden_targets_device(h, ix, rows, None, C.byref(hb)),
-                "encode_extended": encode}
+                "encode_extended": lambda: L.rmj_encode_batch_device(h, env._batch(True))}
     secs = {k: [] for k in calls_of}
     for w in range(windows + 1):          # (window 0 warms up)
         for name, call in calls_of.items():
